@@ -3,16 +3,19 @@
 (BASELINE.json metric; SURVEY.md section 8d / BASELINE.md config C4: MLP 512-256-128-4, lag 10,
 global batch 8192 pairs), frame-sharded over N GPUs.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step is one optimiser step over one global batch of time-lagged pairs.  The matrix is
 generated on the device, standardised by the HIP statistics / normalise kernels and stays
 resident in HBM; the timed region holds exactly K training steps (plus the validation pass at
 every epoch boundary they cross, as the reference's fit loop does) between barriers.  Rank 0
-prints one JSON line.  `value` is the contract configuration (global batch 8192); the same fit at
-a large global batch (524 208 pairs: MFMA-bound instead of latency-bound) is reported beside it
-under `large_batch`, with its own roofline."""
+prints one JSON line.  `value` is the contract configuration (global batch 8192).  A plain run
+measures that and nothing else; --full adds the side measurements: the same fit at a large
+global batch (524 208 pairs: MFMA-bound instead of latency-bound) under `large_batch` with its
+own roofline, the other arithmetic mode, the reference's shuffled loader, the collective
+timings, the torch-CPU baseline and the other single-GPU configurations.  --dump-outputs DIR
+writes what the headline's timed steps computed (model, last gradient, step records) as .npy."""
 import argparse
 import json
 import os
@@ -78,7 +81,34 @@ def parse():
     p.add_argument("--config", choices=["c4", "c2", "ref_small"], default="c4",
                    help="c4 (default): the headline, Deep-TICA on 10M x 512; c2: BASELINE.json configs[1], autoencoder 128-64-32-2-32-64-128 on "
                         "1M x 128 at batch 4096 (its own metric line with roofline and cpu_baseline; one GPU)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="c4: besides the headline, run every side measurement the options above describe (other_gemm_mode, shuffled, "
+                        "large_batch, collective_timing, cpu_baseline and the single-GPU blocks c2 / ref_small / calculator_fit); "
+                        "without it a run sets up, warms up, times the --steps headline steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="c4: after the timed headline steps, write what they computed as DIR/<name>.npy (rank 0): the model's "
+                        "layer<l>_weight / layer<l>_bias (float32), the last step's flat gradient 'grads' (float32) and the "
+                        "per-step records of the timed region 'step_log' (float64: loss, batch, C0, Ct, mean of the TICA head)")
+    a = p.parse_args()
+    if a.dump_outputs is not None and a.config != "c4":
+        p.error("--dump-outputs covers the headline configuration (--config c4)")
+    return a
+
+
+DUMP_LOG_BYTES = 32 << 20   # the step records kept by --dump-outputs (the last ones of the timed region): the whole dump stays under 64 MB
+
+
+def dump_outputs(out_dir, fit, log, n_timed):
+    """What a caller of the timed path receives after its last step: the trained linears, the gradient of that step and the
+    records the timed steps appended to the metrics log (the last `n_timed` records, at most DUMP_LOG_BYTES of them)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for l, (w, b) in enumerate(fit.eng.get_linears()):
+        np.save(os.path.join(out_dir, f"layer{l}_weight.npy"), np.ascontiguousarray(w, dtype=np.float32))
+        np.save(os.path.join(out_dir, f"layer{l}_bias.npy"), np.ascontiguousarray(b, dtype=np.float32))
+    np.save(os.path.join(out_dir, "grads.npy"), fit.gv.detach().cpu().numpy().astype(np.float32))
+    rec = np.ascontiguousarray(log[len(log) - min(n_timed, len(log)):], dtype=np.float64)
+    keep = max(1, DUMP_LOG_BYTES // (rec.shape[1] * 8))
+    np.save(os.path.join(out_dir, "step_log.npy"), rec[-keep:])
 
 
 def init_linears(dims, seed):
@@ -709,11 +739,14 @@ def main():
     elapsed, prof, log = fit.run(a.steps, a.warmup, a.profile_every)
     val_timed = fit.val_timed
     head_roof = fit.roofline(prof, a.gemm_mode, traffic_tables) if rank == 0 else None
+    if a.dump_outputs is not None and rank == 0:   # before the other-mode run below trains the same engine further
+        dump_outputs(a.dump_outputs, fit, log, a.steps + val_timed)
 
+    # ---- --full only from here to the JSON line: the side measurements
     # the same training steps in the other arithmetic mode (a launch-time switch of the library)
     other = "native" if a.gemm_mode == "split" else "split"
     other_res = None
-    if a.other_mode_steps > 0:
+    if a.full and a.other_mode_steps > 0:
         hip.set_gemm_mode(other)
         elo, prof_o, _ = fit.run(a.other_mode_steps, 20, a.profile_every, with_validation=False)
         hip.set_gemm_mode(a.gemm_mode)
@@ -725,7 +758,7 @@ def main():
             if r:
                 other_res["roofline"] = {k: r[k] for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "avg_ms")}
     steps_per_epoch, val_steps = fit.steps_per_epoch, fit.val_steps
-    collectives = fit.time_collectives()
+    collectives = fit.time_collectives() if a.full else None
     comm_world = None
     if dist is not None:
         comm_world = int(hip._lib.load().dcv_comm_world(step_comm.h)) if step_comm is not None else int(dist.get_world_size())
@@ -733,7 +766,7 @@ def main():
 
     # ---- the reference's default loader at the same batch: random split, a fresh permutation per epoch, gathered two-half batches
     shuffled = None
-    if a.shuffled_steps > 0:
+    if a.full and a.shuffled_steps > 0:
         fs = Fit(hip, dist, Xn, dims, acts, lag, a.batch, world, a.lr, linears, n_local, step_comm, shuffled=True, seed=rank)
         es, prof_s, log_s = fs.run(a.shuffled_steps, 20, a.profile_every, with_validation=False)
         if rank == 0:
@@ -749,7 +782,7 @@ def main():
 
     # ---- the same fit at a large global batch (MFMA-bound instead of launch / latency-bound)
     large = None
-    if a.large_batch > 0 and a.large_batch % world == 0 and a.large_batch != a.batch and (n_local - lag) * 0.8 >= a.large_batch // world:
+    if a.full and a.large_batch > 0 and a.large_batch % world == 0 and a.large_batch != a.batch and (n_local - lag) * 0.8 >= a.large_batch // world:
         fl_ = Fit(hip, dist, Xn, dims, acts, lag, a.large_batch, world, a.lr, linears, n_local, step_comm)
         el, prof_l, _ = fl_.run(a.large_steps, 5, a.profile_every)
         if rank == 0:
@@ -801,7 +834,7 @@ def main():
             out["large_batch"] = large
         if shuffled is not None:
             out["shuffled"] = shuffled
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             sample_rows = min(n_local, 40 * a.batch + lag)
             Xh = Xn[:sample_rows].cpu().numpy()
             v, done, dt = cpu_baseline(Xh, dims, acts, lag, min(a.batch, sample_rows - lag), a.lr, a.cpu_seconds, linears)
@@ -811,7 +844,7 @@ def main():
                           f"{sample_rows} frames, {dt:.1f} s",
             }
             settle_host()
-        if world == 1 and dist is None:
+        if a.full and world == 1 and dist is None:
             # bounded runs of the other single-GPU configurations, carried by the same JSON line (the driver records one line)
             del X, Xn
             torch.cuda.empty_cache()

@@ -13,6 +13,7 @@ What is stored is *data* (inputs and expected outputs), never reference source:
 * ``linear_models.npz``     arrays inside input/models/{pca,tica,htica}_model.zip;
 * ``nn_models.npz``         parameters, buffers and outputs of the TorchScript files inside
   input/models/{deep_tica,ae}_model.zip, evaluated here with torch.jit.load;
+* ``nn_model_trees.json``   the module tree of those TorchScript files: (module name, original class name) pairs;
 * ``cluster_golden.npz``    reference/traj_cluster/*.csv (labels, centroid flags) plus the
   outputs of the reference's importable ``statistics`` module (hierarchical as in its tests,
   and k-means, which the reference's tests do not pin) on those CSVs and on seeded
@@ -72,7 +73,7 @@ def main():
     np.savez_compressed(os.path.join(OUT, "linear_models.npz"), **lin)
 
     # ------------------------------------------------------------------ NN models
-    nn = {}
+    nn, trees = {}, {}
     Xt = torch.from_numpy(X)
     for cv in ["deep_tica", "ae"]:
         with zipfile.ZipFile(os.path.join(DATA, "input", "models", f"{cv}_model.zip")) as z:
@@ -84,7 +85,10 @@ def main():
             nn[f"{cv}.buffer.{n}"] = b.detach().numpy()
         with torch.no_grad():
             nn[f"{cv}.output"] = m(Xt).numpy()
+        trees[cv] = [[n, c.original_name] for n, c in m.named_modules()]
     np.savez_compressed(os.path.join(OUT, "nn_models.npz"), **nn)
+    with open(os.path.join(OUT, "nn_model_trees.json"), "w") as f:
+        json.dump(trees, f, indent=1)
 
     # ------------------------------------------------------------------ clustering
     from deep_cartograph.modules.statistics import statistics as ref_stats

@@ -49,7 +49,7 @@ def test_bench_self_launches_its_ranks():
     gloo; the line carries the communicator's world size, the measured all-reduce times, the large-batch and shuffled
     blocks of the N > 1 path."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--frames", "600000", "--batch", "4096",
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--frames", "600000", "--batch", "4096",
             "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--large-batch", "65516", "--large-steps", "3", "--other-mode-steps", "0",
             "--shuffled-steps", "5"]
     p = subprocess.run(args, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
@@ -83,11 +83,11 @@ def test_bench_refuses_more_rccl_ranks_than_gpus():
 
 
 def test_bench_single_gpu_line_carries_every_block():
-    """The driver's form (`python bench.py --gpus 1 --steps K --warmup W`) on a small matrix: ONE JSON line with the contract
+    """The full form (`python bench.py --full --gpus 1 --steps K --warmup W`) on a small matrix: ONE JSON line with the contract
     keys, `roofline` and `cpu_baseline`, and the round-4 blocks (`shuffled`, `large_batch`, `c2`, `ref_small`) -- with the
     epoch loop issued as dcv_mlp_train_steps runs between the sampled steps and the validation passes as dcv_mlp_eval_steps."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--frames", "300000", "--batch", "4096", "--steps", "70", "--warmup", "3",
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--frames", "300000", "--batch", "4096", "--steps", "70", "--warmup", "3",
             "--cpu-seconds", "1", "--large-batch", "65516", "--large-steps", "3", "--other-mode-steps", "4", "--shuffled-steps", "40",
             "--c2-steps", "420", "--ref-small-steps", "12", "--fit-epochs", "2"]
     p = subprocess.run(args, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
@@ -118,6 +118,49 @@ def test_bench_single_gpu_line_carries_every_block():
     assert all(x["ok"] and x["epochs"] == 2 and x["seconds"] > 0 for x in fits)
 
 
+def test_bench_plain_line_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """The driver's form without --full (`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`): the line carries
+    the headline alone, none of the side blocks, and DIR holds what the timed steps computed.  Two runs with the same
+    arguments see the same inputs and write the same arrays."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    lines, dirs = [], []
+    for rep in range(2):
+        d = tmp_path / f"out{rep}"
+        args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--frames", "300000", "--batch", "4096", "--steps", "70",
+                "--warmup", "3", "--dump-outputs", str(d)]
+        p = subprocess.run(args, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        js = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1, p.stdout[-2000:]
+        lines.append(json.loads(js[0]))
+        dirs.append(d)
+    line = lines[0]
+    assert line["n_gpus"] == 1 and line["steps"] == 70 and line["warmup"] == 3 and line["dtype"] == "f32" and line["higher_is_better"]
+    assert abs(line["value"] - 4096 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert line["roofline"] is not None and line["config"]["collective_timing"] is None
+    for key in ("cpu_baseline", "other_gemm_mode", "shuffled", "large_batch", "c2", "ref_small", "calculator_fit"):
+        assert key not in line, key
+    # 300 000 frames, lag 10, 80 % training pairs: 58 steps per epoch -> 70 training records + one validation pass
+    n_timed = 70 + line["config"]["validation_steps_timed"]
+    names = sorted(f.name for f in dirs[0].iterdir())
+    assert names == sorted(["grads.npy", "step_log.npy"] + [f"layer{l}_{k}.npy" for l in range(3) for k in ("weight", "bias")])
+    total = 0
+    for name in names:
+        a, b = np.load(dirs[0] / name), np.load(dirs[1] / name)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.all(np.isfinite(a)), name
+        np.testing.assert_allclose(a, b, rtol=1e-4, atol=1e-6, err_msg=name)
+        total += a.nbytes
+    assert total <= 64 << 20
+    w0 = np.load(dirs[0] / "layer0_weight.npy")
+    assert w0.shape == (256, 512) and np.load(dirs[0] / "grads.npy").size == line["config"]["params"]
+    log = np.load(dirs[0] / "step_log.npy")
+    assert log.shape == (n_timed, 2 + 2 * 16 + 4) and log.dtype == np.float64
+    assert np.all(log[:, 1] == 4096)                     # the batch column of every record
+    assert log[-1, 0] == line["loss_last_train"]         # the last timed step trains (the validation pass came after step 58)
+
+
 @pytest.mark.parametrize("native", [False, True])
 def test_bench_collective_path_on_real_rccl_world1(native):
     """DCV_FORCE_DIST=1: the data-parallel branch of bench.py (dcv_mlp_dp_step, statistics and gradient all-reduces in stream
@@ -127,7 +170,7 @@ def test_bench_collective_path_on_real_rccl_world1(native):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["DCV_FORCE_DIST"] = "1"
     env["MASTER_PORT"] = str(_free_port())
-    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--frames", "300000", "--batch", "4096", "--steps", "12", "--warmup", "3",
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--frames", "300000", "--batch", "4096", "--steps", "12", "--warmup", "3",
             "--no-cpu-baseline", "--large-batch", "0", "--other-mode-steps", "0", "--shuffled-steps", "6", "--c2-steps", "0", "--ref-small-steps", "0", "--fit-epochs", "0"]
     if native:
         args.append("--native-rccl")

@@ -251,7 +251,7 @@ def test_parallel_text_parse_matches_serial(tmp_path):
     assert kept == names[1:]
 
 
-def test_plumed_text_matches_reference_command_module():
+def test_plumed_text_matches_reference_command_module(tmp_path):
     """COMBINE / PRINT / PYTORCH_MODEL lines and the whole linear-CV section against text produced by the reference's
     own modules/plumed/command.py (tests/golden/plumed_text.json, generated by make_golden.py)."""
     import json
@@ -269,7 +269,7 @@ def test_plumed_text_matches_reference_command_module():
     # the linear CV section on the arrays of the reference's pca_model.zip
     lin = load_golden("linear_models.npz")
     names = [str(s) for s in load_golden("features_164x54.npz")["names"]]
-    calc = cv_calculators_map["pca"]({"dimension": 2, "features_normalization": "mean_std"}, "/tmp/x")
+    calc = cv_calculators_map["pca"]({"dimension": 2, "features_normalization": "mean_std"}, str(tmp_path))
     calc.features_ref_labels = names
     calc.features_norm_mean, calc.features_norm_range = lin["pca.features_norm_mean"], lin["pca.features_norm_range"]
     calc.cv = lin["pca.cv_weights"]
@@ -277,31 +277,40 @@ def test_plumed_text_matches_reference_command_module():
     assert calc.plumed_cv_lines() == t["linear_cv_section_pca"]
     assert calc.plumed_cv_labels() == ["norm_pca_0", "norm_pca_1"]
     # neural CVs: PYTORCH_MODEL line
-    nn = cv_calculators_map["deep_tica"]({"dimension": 2}, "/tmp/x")
+    nn = cv_calculators_map["deep_tica"]({"dimension": 2}, str(tmp_path))
     nn.features_ref_labels = names[:5]
     nn.weights_path = "/abs/path/deep_tica_weights.pt"
     assert nn.plumed_cv_lines() == "\n# Collective variable\n" + t["pytorch_model"]
 
 
-def test_read_torchscript_decomposes_the_reference_model_files():
-    """export.read_torchscript on the reference's real deep_tica_model.zip / ae_model.zip (build container only: the files
-    never travel): layers, activations and buffers come out as the arrays captured in nn_models.npz."""
-    import io
-    import tempfile
-    import zipfile
-
+def test_read_torchscript_decomposes_the_reference_model_files(tmp_path):
+    """export.read_torchscript on TorchScript files of the reference's deep_tica_model.zip / ae_model.zip: their module tree
+    (nn_model_trees.json) and arrays (nn_models.npz), both recorded from the reference's files, are rebuilt into a traced
+    file that must carry exactly that tree; layers, activations and buffers come out as the recorded arrays."""
     from deep_cartograph_amd import export
-    from tests.conftest import load_golden
+    from tests.conftest import GOLDEN, load_golden
 
-    base = "/root/reference/deep_cartograph/tests/data/input/models"
-    if not os.path.isdir(base):
-        pytest.skip("reference not present (GPU box)")
     g = load_golden("nn_models.npz")
+    trees = json.load(open(os.path.join(GOLDEN, "nn_model_trees.json")))
+    acts = ["leaky_relu", "leaky_relu", None]
+
+    def ff(prefix):
+        return export.FeedForward([(g[f"{prefix}.{i}.weight"], g[f"{prefix}.{i}.bias"]) for i in (0, 3, 6)], acts, [0.0, 0.0, None])
+
+    def norm(cv, name):
+        return export.Normalization(g[f"{cv}.buffer.{name}.mean"], g[f"{cv}.buffer.{name}.range"])
+
+    models = {"deep_tica": export.DeepTICA(norm("deep_tica", "norm_in"), ff("deep_tica.param.nn.nn"),
+                                           export.TICA(g["deep_tica.buffer.tica.evecs"], g["deep_tica.buffer.tica.mean"]),
+                                           norm("deep_tica", "postprocessing")),
+              "ae": export.AutoEncoderCV(norm("ae", "norm_in"), ff("ae.param.encoder.nn"), ff("ae.param.decoder.nn"), norm("ae", "postprocessing"))}
     for cv, prefix in (("deep_tica", "nn.nn"), ("ae", "encoder.nn")):
-        with zipfile.ZipFile(os.path.join(base, f"{cv}_model.zip")) as z, tempfile.NamedTemporaryFile(suffix=".pt") as f:
-            f.write(z.read("model/cv_weights.pt"))
-            f.flush()
-            parts = export.read_torchscript(f.name)
+        path = str(tmp_path / f"{cv}_cv_weights.pt")
+        export.save_torchscript(models[cv], 54, path)
+        m = torch.jit.load(path)
+        assert [[n, c.original_name] for n, c in m.named_modules()] == trees[cv]
+        assert {n for n, _ in m.named_buffers()} == {k[len(f"{cv}.buffer."):] for k in g.files if k.startswith(f"{cv}.buffer.")}
+        parts = export.read_torchscript(path)
         assert parts["kind"] == cv and parts["acts"] == ["leaky_relu", "leaky_relu", None]
         for (w, b), i in zip(parts["linears"], (0, 3, 6)):
             np.testing.assert_array_equal(w, g[f"{cv}.param.{prefix}.{i}.weight"])
@@ -312,14 +321,14 @@ def test_read_torchscript_decomposes_the_reference_model_files():
             np.testing.assert_array_equal(parts["tica"][1], g["deep_tica.buffer.tica.evecs"])
 
 
-def test_calculators_refuse_cpu():
+def test_calculators_refuse_cpu(tmp_path):
     from deep_cartograph_amd._lib import DcvError
     from deep_cartograph_amd.cv_calculator import cv_calculators_map
 
     if torch.cuda.is_available():
         pytest.skip("GPU present")
     assert set(cv_calculators_map) == {"pca", "tica", "htica", "ae", "deep_tica"}
-    calc = cv_calculators_map["pca"]({"dimension": 2, "features_normalization": "mean_std"}, "/tmp/x")
+    calc = cv_calculators_map["pca"]({"dimension": 2, "features_normalization": "mean_std"}, str(tmp_path))
     with pytest.raises(DcvError):
         calc.set_training_matrix(np.zeros((10, 4), dtype=np.float32))
 
@@ -416,6 +425,49 @@ def test_bench_sampling_plan():
         assert all((i % spe) + c <= spe for i, c, _ in runs)
         assert all((c == 1 and i in picked) if sampled else not any(k in picked for k in range(i, i + c)) for i, c, sampled in runs)
     assert max(c for _, c, _ in bench.Fit.runs(400, bench.Fit.sample_plan(400, 0), 195)) == 3
+
+
+def test_bench_options_and_output_dump(tmp_path):
+    """A plain bench.py run leaves the side measurements to --full; --dump-outputs is a headline option and writes the
+    engine's linears, the last gradient and the timed records as float32 / float64 .npy, the records capped so that the
+    whole dump stays under 64 MB."""
+    import importlib.util
+    import types
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py"]
+        spec.loader.exec_module(bench)
+        a = bench.parse()
+        assert a.full is False and a.dump_outputs is None and a.steps == 2000 and a.warmup == 100
+        sys.argv = ["bench.py", "--full", "--dump-outputs", str(tmp_path / "d")]
+        a = bench.parse()
+        assert a.full is True and a.dump_outputs == str(tmp_path / "d")
+        sys.argv = ["bench.py", "--config", "c2", "--dump-outputs", str(tmp_path / "d")]
+        with pytest.raises(SystemExit):
+            bench.parse()
+    finally:
+        sys.argv = argv
+    rng = np.random.default_rng(0)
+    linears = [(rng.standard_normal((8, 6)).astype(np.float32), rng.standard_normal(8).astype(np.float32)),
+               (rng.standard_normal((2, 8)).astype(np.float32), rng.standard_normal(2).astype(np.float32))]
+    fit = types.SimpleNamespace(eng=types.SimpleNamespace(get_linears=lambda: linears), gv=torch.arange(72, dtype=torch.float32))
+    width = 2 + 2 * 4 + 2
+    log = np.arange(50 * width, dtype=np.float64).reshape(50, width)
+    out = tmp_path / "small"
+    bench.dump_outputs(str(out), fit, log, 20)
+    assert sorted(f.name for f in out.iterdir()) == ["grads.npy", "layer0_bias.npy", "layer0_weight.npy", "layer1_bias.npy",
+                                                      "layer1_weight.npy", "step_log.npy"]
+    np.testing.assert_array_equal(np.load(out / "layer1_weight.npy"), linears[1][0])
+    assert np.load(out / "grads.npy").dtype == np.float32
+    np.testing.assert_array_equal(np.load(out / "step_log.npy"), log[-20:])
+    big = np.zeros((bench.DUMP_LOG_BYTES // (width * 8) + 100, width))
+    bench.dump_outputs(str(tmp_path / "big"), fit, big, len(big))
+    kept = np.load(tmp_path / "big" / "step_log.npy")
+    assert kept.nbytes <= bench.DUMP_LOG_BYTES and len(kept) == bench.DUMP_LOG_BYTES // (width * 8)
 
 
 def test_epoch_loop_host_helpers():
