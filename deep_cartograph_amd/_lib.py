@@ -12,6 +12,7 @@ ACT = {None: 0, "linear": 0, "leaky_relu": 1, "relu": 2, "tanh": 3, "elu": 4, "s
 OPTIMIZER = {"Adam": 0, "AdamW": 1, "SGD": 2, "RMSprop": 3, "Adagrad": 4, "Adamax": 5, "NAdam": 6, "RAdam": 7, "Adadelta": 8, "ASGD": 9, "Rprop": 10}
 MODEL_DEEPTICA = 1
 MODEL_AE = 2
+MODEL_VAE = 3
 
 
 class MlpDesc(C.Structure):
@@ -85,6 +86,10 @@ SIGNATURES = {
     "dcv_gemm_tn_split": (C.c_int, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P]),
     "dcv_mlp_set_row_sharing": (C.c_int, [_P, _I32]),
     "dcv_mlp_set_feature_range": (C.c_int, [_P, _P, _P]),
+    "dcv_mlp_set_kl_beta": (C.c_int, [_P, C.c_double]),
+    "dcv_mlp_set_noise": (C.c_int, [_P, _P, _I64]),
+    "dcv_mlp_noise_position": (_I64, [_P]),
+    "dcv_mlp_latent_sample": (C.c_int, [_P, _I64, _P, _P]),
     "dcv_mlp_forward": (C.c_int, [_P, _P, _I64, _P, _I64, _I32, _I32, _P]),
     "dcv_mlp_stats": (_P, [_P]),
     "dcv_mlp_stats_len": (_I32, [_P]),

@@ -1034,7 +1034,8 @@ __global__ __launch_bounds__(256) void ae_sse_kernel(const float* __restrict__ Y
                                                      const float* __restrict__ range, double* __restrict__ part,
                                                      unsigned* __restrict__ ticket, double* __restrict__ out, double Bg,
                                                      double* __restrict__ log, int* __restrict__ log_count, int log_cap,
-                                                     int log_width, int rows_per_block) {
+                                                     int log_width, int rows_per_block, const double* __restrict__ kpart = nullptr,
+                                                     int kblocks = 0, double beta = 0.0) {
     __shared__ double red[256];
     const int t = threadIdx.x;
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
@@ -1075,13 +1076,24 @@ __global__ __launch_bounds__(256) void ae_sse_kernel(const float* __restrict__ Y
         double tot = 0.0;
         for (int b = t; b < (int)gridDim.x; b += 64) tot += handoff_load(part + b);
         for (int off = 32; off > 0; off >>= 1) tot += __shfl_down(tot, off, 64);
+        double kl = 0.0;   // VAE: the KL partials of the sampling launch (vae_sample_kernel), the same lane / shuffle order
+        if (kpart != nullptr) {
+            for (int b = t; b < kblocks; b += 64) kl += kpart[b];
+            for (int off = 32; off > 0; off >>= 1) kl += __shfl_down(kl, off, 64);
+        }
         if (t == 0) {
             out[0] = tot;
+            if (kpart != nullptr) out[1] = kl;
             if (log != nullptr) {
                 const int slot = *log_count;
                 if (slot < log_cap) {
-                    log[(int64_t)slot * log_width + 0] = tot / (Bg * (double)F);
+                    const double rec = tot / (Bg * (double)F);
+                    log[(int64_t)slot * log_width + 0] = kpart != nullptr ? rec + beta * (kl / Bg) : rec;
                     log[(int64_t)slot * log_width + 1] = Bg;
+                    if (kpart != nullptr) {
+                        log[(int64_t)slot * log_width + 2] = rec;
+                        log[(int64_t)slot * log_width + 3] = kl / Bg;
+                    }
                 }
                 *log_count = slot + 1;
             }
@@ -1122,15 +1134,66 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(float* __restrict__ o
     }
 }
 
+// vae != 0: stats = [SSE | KL sum], record [recon + beta * kl | weight | recon | kl]
 __global__ void ae_log_kernel(const double* __restrict__ stats, double Bg, int F, double* __restrict__ log,
-                              int* __restrict__ log_count, int log_cap, int log_width) {
+                              int* __restrict__ log_count, int log_cap, int log_width, int vae = 0, double beta = 0.0) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const int slot = *log_count;
     if (slot < log_cap) {
-        log[(int64_t)slot * log_width + 0] = stats[0] / (Bg * (double)F);
+        const double rec = stats[0] / (Bg * (double)F);
+        log[(int64_t)slot * log_width + 0] = vae ? rec + beta * (stats[1] / Bg) : rec;
         log[(int64_t)slot * log_width + 1] = Bg;
+        if (vae) {
+            log[(int64_t)slot * log_width + 2] = rec;
+            log[(int64_t)slot * log_width + 3] = stats[1] / Bg;
+        }
     }
     *log_count = slot + 1;
+}
+
+// ------------------------------------------------------------------ variational autoencoder: reparameterisation
+// H = [mu | lv] (2d columns, the two heads of Linear latent_layer - 1), eps [R][d] dense:
+//   z = eps * exp(lv / 2) + mu                       (torch: randn_like(mu) * torch.exp(0.5 * log_var) + mu)
+//   part[block] = sum over the block's rows of -0.5 * sum_j (lv - exp(lv) - mu^2 + 1)   (float64, fixed tree order)
+constexpr int kVaeRows = 256;   // rows per block of the sampling kernels: one thread per row
+__global__ __launch_bounds__(kVaeRows) void vae_sample_kernel(const float* __restrict__ H, int64_t ldh, int64_t R, int d,
+                                                             const float* __restrict__ eps, float* __restrict__ Z, int64_t ldz,
+                                                             double* __restrict__ part) {
+    __shared__ double red[kVaeRows];
+    const int t = threadIdx.x;
+    const int64_t r = (int64_t)blockIdx.x * kVaeRows + t;
+    double kl = 0.0;
+    if (r < R) {
+        for (int j = 0; j < d; ++j) {
+            const float mu = H[r * ldh + j], lv = H[r * ldh + d + j];
+            Z[r * ldz + j] = __fadd_rn(__fmul_rn(eps[r * d + j], expf(0.5f * lv)), mu);
+            kl += (double)lv - exp((double)lv) - (double)mu * (double)mu + 1.0;
+        }
+        kl *= -0.5;
+    }
+    red[t] = kl;
+    __syncthreads();
+    for (int off = kVaeRows / 2; off > 0; off >>= 1) {
+        if (t < off) red[t] += red[t + off];
+        __syncthreads();
+    }
+    if (t == 0) part[blockIdx.x] = red[0];
+}
+
+// in place: G holds dL/dz in columns [0, d) of each row; out: [dL/dmu | dL/dlv] in columns [0, 2d)
+//   dmu = dz + beta * mu / B,  dlv = dz * eps * 0.5 * exp(lv / 2) + beta * 0.5 * (exp(lv) - 1) / B
+__global__ __launch_bounds__(kVaeRows) void vae_sample_backward_kernel(const float* __restrict__ H, int64_t ldh, int64_t R, int d,
+                                                                      const float* __restrict__ eps, float* __restrict__ G, int64_t ldg,
+                                                                      float beta_over_b) {
+    const int64_t r = (int64_t)blockIdx.x * kVaeRows + threadIdx.x;
+    if (r >= R) return;
+    float dz[8];
+    for (int j = 0; j < d; ++j) dz[j] = G[r * ldg + j];
+    for (int j = 0; j < d; ++j) {
+        const float mu = H[r * ldh + j], lv = H[r * ldh + d + j];
+        G[r * ldg + j] = dz[j] + beta_over_b * mu;
+        G[r * ldg + d + j] = dz[j] * eps[r * d + j] * 0.5f * expf(0.5f * lv) + beta_over_b * 0.5f * (expf(lv) - 1.f);
+    }
 }
 
 __global__ void fill_kernel(float* p, int64_t n, float v) {
@@ -1276,6 +1339,7 @@ static void mlp_free(dcv_mlp* m) {
     auto f = [](void* p) { if (p) (void)hipFree(p); };
     f(m->params); f(m->grads); f(m->adam_m); f(m->adam_v); f(m->opt_aux); f(m->dZ[0]); f(m->dZ[1]); f(m->stats); f(m->gradp);
     f(m->spart); f(m->log); f(m->log_count); f(m->ticket); f(m->feat_range); f(m->ident); f(m->zeros_d); f(m->ones_d); f(m->proj_ws);
+    f(m->vae_z); f(m->vae_kpart);
     for (auto& l : m->layers) { f(l.H); f(l.slab); f(l.bpart); f(l.mask); f(l.Y); f(l.rm); f(l.rv); f(l.bn_stat); f(l.bn_part); f(l.bn_gpart); f(l.bn_bpart); }
     g_launch_ev = LaunchEvents{};   // no stale offer of events that are about to be destroyed
     g_launch_taken = nullptr;
@@ -1328,7 +1392,8 @@ extern "C" int dcv_mlp_create(const dcv_mlp_desc* desc, dcv_mlp** out) {
     DCV_REQUIRE(desc && out, "dcv_mlp_create: null argument");
     *out = nullptr;
     const int L = desc->n_layers;
-    DCV_REQUIRE(desc->model == DCV_MODEL_DEEPTICA || desc->model == DCV_MODEL_AE, "dcv_mlp_create: unknown model %d", desc->model);
+    DCV_REQUIRE(desc->model == DCV_MODEL_DEEPTICA || desc->model == DCV_MODEL_AE || desc->model == DCV_MODEL_VAE, "dcv_mlp_create: unknown model %d",
+                desc->model);
     DCV_REQUIRE(L >= 1 && L <= DCV_MAX_LAYERS, "dcv_mlp_create: n_layers=%d out of range", L);
     for (int l = 0; l <= L; ++l) DCV_REQUIRE(desc->dims[l] >= 1, "dcv_mlp_create: dims[%d]=%d", l, desc->dims[l]);
     for (int l = 0; l < L; ++l)
@@ -1344,6 +1409,13 @@ extern "C" int dcv_mlp_create(const dcv_mlp_desc* desc, dcv_mlp** out) {
         DCV_REQUIRE(desc->dims[L] == desc->dims[0], "dcv_mlp_create: autoencoder must map F=%d back to F (got %d)", desc->dims[0], desc->dims[L]);
         DCV_REQUIRE(desc->latent_layer >= 1 && desc->latent_layer < L, "dcv_mlp_create: latent_layer=%d", desc->latent_layer);
         DCV_REQUIRE(desc->dims[desc->latent_layer] <= 16, "dcv_mlp_create: latent dimension %d > 16", desc->dims[desc->latent_layer]);
+        if (desc->model == DCV_MODEL_VAE) {
+            const int h = desc->latent_layer - 1;   // the two heads, concatenated: [mean | log-variance]
+            DCV_REQUIRE(desc->dims[desc->latent_layer] % 2 == 0 && desc->dims[desc->latent_layer] <= 16,
+                        "dcv_mlp_create: VAE head layer %d must output 2 * d <= 16 columns (got %d)", h, desc->dims[desc->latent_layer]);
+            DCV_REQUIRE(desc->act[h] == DCV_ACT_NONE && !(desc->dropout[h] > 0.f) && !desc->batchnorm[h],
+                        "dcv_mlp_create: the VAE heads (Linear %d) take no activation, dropout or batch normalisation", h);
+        }
     }
     dcv_mlp* m = new (std::nothrow) dcv_mlp();
     DCV_REQUIRE(m, "dcv_mlp_create: out of host memory");
@@ -1378,6 +1450,15 @@ extern "C" int dcv_mlp_create(const dcv_mlp_desc* desc, dcv_mlp** out) {
     m->snet_img_floats = 0;
     m->snet_fwd_valid = false;
     m->last_path = 0;
+    m->vae_d = desc->model == DCV_MODEL_VAE ? desc->dims[desc->latent_layer] / 2 : 0;
+    m->vae_z = nullptr;
+    m->ld_z = align_up((size_t)(m->vae_d > 0 ? m->vae_d : 1), 4);
+    m->vae_kpart = nullptr;
+    m->vae_kblocks = 0;
+    m->kl_beta = 0.0;
+    m->noise = nullptr;
+    m->noise_rows = m->noise_pos = 0;
+    m->eps_cur = nullptr;
     m->prof_level = m->prof_cap = 0;
     m->prof_kind_off = 0;
     for (int i = 0; i < 4; ++i) { m->gexec[i] = nullptr; m->gwarm[i] = false; }
@@ -1391,7 +1472,7 @@ extern "C" int dcv_mlp_create(const dcv_mlp_desc* desc, dcv_mlp** out) {
     int rc = DCV_OK;
     for (int l = 0; l < L && rc == DCV_OK; ++l) {
         LayerPlan& p = m->layers[l];
-        p.in = desc->dims[l];
+        p.in = m->vae_d > 0 && l == desc->latent_layer ? m->vae_d : desc->dims[l];   // VAE: the first decoder Linear reads z (d columns)
         p.out = desc->dims[l + 1];
         p.act = desc->act[l];
         p.w_off = off;
@@ -1441,10 +1522,10 @@ extern "C" int dcv_mlp_create(const dcv_mlp_desc* desc, dcv_mlp** out) {
     m->n_params = off;
     m->ld_dz = align_up((size_t)maxdim, 4);
     const int d = m->d_out;
-    m->stats_len = desc->model == DCV_MODEL_DEEPTICA ? 2 * d + 2 * d * d : 1;
-    m->log_width = desc->model == DCV_MODEL_DEEPTICA ? 2 + 2 * d * d + d : 2;
+    m->stats_len = desc->model == DCV_MODEL_DEEPTICA ? 2 * d + 2 * d * d : desc->model == DCV_MODEL_VAE ? 2 : 1;
+    m->log_width = desc->model == DCV_MODEL_DEEPTICA ? 2 + 2 * d * d + d : desc->model == DCV_MODEL_VAE ? 4 : 2;
     m->spart_blocks = desc->model == DCV_MODEL_DEEPTICA ? (int)cdiv(desc->max_batch, kStatBlockRows) : (int)cdiv(m->rows_cap, kSseRows);
-    const int dl = desc->model == DCV_MODEL_AE ? desc->dims[desc->latent_layer] : d;
+    const int dl = desc->model == DCV_MODEL_AE ? desc->dims[desc->latent_layer] : desc->model == DCV_MODEL_VAE ? m->vae_d : d;
     if (rc == DCV_OK) rc = dmalloc(&m->params, (size_t)m->n_params);
     if (rc == DCV_OK) rc = dmalloc(&m->grads, (size_t)m->n_params);
     if (rc == DCV_OK) rc = dmalloc(&m->adam_m, (size_t)m->n_params);
@@ -1460,6 +1541,8 @@ extern "C" int dcv_mlp_create(const dcv_mlp_desc* desc, dcv_mlp** out) {
     if (rc == DCV_OK) rc = dmalloc(&m->log_count, 1);
     if (rc == DCV_OK) rc = dmalloc(&m->ticket, 4);
     if (rc == DCV_OK) rc = dmalloc(&m->feat_range, (size_t)desc->dims[0]);
+    if (rc == DCV_OK && m->vae_d > 0) rc = dmalloc(&m->vae_z, (size_t)m->rows_cap * m->ld_z);
+    if (rc == DCV_OK && m->vae_d > 0) rc = dmalloc(&m->vae_kpart, (size_t)cdiv(m->rows_cap, kVaeRows));
     if (rc == DCV_OK) rc = dmalloc(&m->ident, (size_t)dl * dl);
     if (rc == DCV_OK) rc = dmalloc(&m->zeros_d, (size_t)dl);
     if (rc == DCV_OK) rc = dmalloc(&m->ones_d, (size_t)dl);
@@ -1638,6 +1721,35 @@ extern "C" int dcv_mlp_set_feature_range(dcv_mlp* m, const float* range_h, void*
     return DCV_OK;
 }
 
+extern "C" int dcv_mlp_set_kl_beta(dcv_mlp* m, double beta) {
+    DCV_REQUIRE(m && m->vae_d > 0, "dcv_mlp_set_kl_beta: not a variational autoencoder");
+    m->kl_beta = beta;
+    return DCV_OK;
+}
+
+extern "C" int dcv_mlp_set_noise(dcv_mlp* m, const float* eps_d, int64_t rows) {
+    DCV_REQUIRE(m && m->vae_d > 0, "dcv_mlp_set_noise: not a variational autoencoder");
+    DCV_REQUIRE(rows >= 0 && (eps_d != nullptr || rows == 0), "dcv_mlp_set_noise: bad arguments");
+    m->noise = eps_d;
+    m->noise_rows = rows;
+    m->noise_pos = 0;
+    return DCV_OK;
+}
+
+extern "C" int64_t dcv_mlp_noise_position(const dcv_mlp* m) { return m ? m->noise_pos : -1; }
+
+extern "C" int dcv_mlp_latent_sample(dcv_mlp* m, int64_t rows, float* out_d, void* stream) {
+    DCV_REQUIRE(m && out_d && m->vae_d > 0, "dcv_mlp_latent_sample: bad arguments");
+    DCV_REQUIRE(rows >= 1 && rows <= m->last_batch, "dcv_mlp_latent_sample: rows=%lld outside [1, %d]", (long long)rows, m->last_batch);
+    if (m->last_path != 0) {
+        set_error("dcv_mlp_latent_sample: the last forward ran fused: z never left LDS");
+        return DCV_ESTATE;
+    }
+    DCV_CHECK_HIP(hipMemcpy2DAsync(out_d, (size_t)m->vae_d * sizeof(float), m->vae_z, (size_t)m->ld_z * sizeof(float), (size_t)m->vae_d * sizeof(float),
+                                   (size_t)rows, hipMemcpyDeviceToDevice, as_stream(stream)));
+    return DCV_OK;
+}
+
 extern "C" int dcv_mlp_reset_log(dcv_mlp* m, int32_t capacity, void* stream) {
     DCV_REQUIRE(m && capacity >= 1, "dcv_mlp_reset_log: bad arguments");
     hipStream_t s = as_stream(stream);
@@ -1679,6 +1791,7 @@ static bool next_layer_fusable(const dcv_mlp* m, int l) {
     static const bool off = [] { const char* e = getenv("DCV_NO_HEAD_FUSION"); return e && e[0] == '1'; }();
     if (off || l + 1 >= m->L || m->any_bn) return false;
     if (m->desc.dropout[l + 1] > 0.f) return false;
+    if (m->vae_d > 0 && l + 1 == m->desc.latent_layer) return false;   // the first decoder Linear reads z, sampled in between
     return m->layers[l + 1].out <= 8 && m->layers[l].out <= 128;
 }
 
@@ -1692,7 +1805,16 @@ static int run_forward(dcv_mlp* m, const float* Xn, int64_t ld, const RowMap& ro
     for (int l = 0; l < n_run; ++l) {
         LayerPlan& p = m->layers[l];
         p.mask_rows = -1;
-        Operand A = l == 0 ? make_operand(Xn, ld, p.in, rows_map) : make_operand(layer_out(m, l - 1), m->layers[l - 1].ldh, p.in);
+        const bool from_z = m->vae_d > 0 && l == m->desc.latent_layer;
+        if (from_z) {   // VAE: z = mu + exp(lv / 2) * eps from the heads' output, and the per-block KL partials
+            const LayerPlan& hd = m->layers[l - 1];
+            m->vae_kblocks = (int)cdiv(rows, kVaeRows);
+            hipLaunchKernelGGL(vae_sample_kernel, dim3((unsigned)m->vae_kblocks), dim3(kVaeRows), 0, s, (const float*)hd.H, hd.ldh, rows, m->vae_d,
+                               m->eps_cur, m->vae_z, m->ld_z, m->vae_kpart);
+            DCV_CHECK_LAUNCH();
+        }
+        Operand A = l == 0 ? make_operand(Xn, ld, p.in, rows_map)
+                           : from_z ? make_operand(m->vae_z, m->ld_z, p.in) : make_operand(layer_out(m, l - 1), m->layers[l - 1].ldh, p.in);
         Operand B = make_operand(m->params + p.w_off, p.in, p.in);
         if (l + 1 < n_run && next_layer_fusable(m, l)) {
             // the narrow Linear behind this layer rides in its epilogue (the whole row of H is in the workgroup)
@@ -1769,9 +1891,11 @@ static int run_graphed(dcv_mlp* m, int slot, hipStream_t s, F&& body) {
         int64_t adam_t, drop_step, cur_step;
         double mu_product, eta;
         int64_t bn_batches[DCV_MAX_LAYERS];
+        int64_t noise_pos;        // VAE noise cursor
+        const float* eps_cur;
     };
     auto snap = [&]() {
-        HostStep h{m->adam_t, m->drop_step, m->cur_step, m->nadam_mu_product, m->asgd_eta, {}};
+        HostStep h{m->adam_t, m->drop_step, m->cur_step, m->nadam_mu_product, m->asgd_eta, {}, m->noise_pos, m->eps_cur};
         for (int l = 0; l < m->L; ++l) h.bn_batches[l] = m->layers[l].bn_batches;
         return h;
     };
@@ -1779,6 +1903,7 @@ static int run_graphed(dcv_mlp* m, int slot, hipStream_t s, F&& body) {
         m->adam_t = h.adam_t; m->drop_step = h.drop_step; m->cur_step = h.cur_step;
         m->nadam_mu_product = h.mu_product; m->asgd_eta = h.eta;
         for (int l = 0; l < m->L; ++l) m->layers[l].bn_batches = h.bn_batches[l];
+        m->noise_pos = h.noise_pos; m->eps_cur = h.eps_cur;
     };
     const HostStep h0 = snap();
     const int rc = body();
@@ -1818,15 +1943,41 @@ static int run_graphed(dcv_mlp* m, int slot, hipStream_t s, F&& body) {
 
 // fuse_head: 0 = statistics only (a data-parallel caller all-reduces them before dcv_mlp_backward); 1 / 2 = one-GPU
 // training / evaluation step: the last block of the statistics launch also runs the loss head (batch = global batch)
+// VAE: the eps rows of the next step (each training / evaluation step consumes `batch` rows of the noise buffer); checked
+// before anything is launched
+static int take_noise(dcv_mlp* m, int64_t batch) {
+    if (m->noise == nullptr || m->noise_pos + batch > m->noise_rows) {
+        set_error("dcv_mlp step: the VAE noise buffer holds %lld rows, %lld used, a step of %lld rows needs more (dcv_mlp_set_noise)",
+                  (long long)m->noise_rows, (long long)m->noise_pos, (long long)batch);
+        return DCV_ESTATE;
+    }
+    m->eps_cur = m->noise + m->noise_pos * m->vae_d;
+    m->noise_pos += batch;
+    return DCV_OK;
+}
+
+// VAE, fused paths: point eps_cur at the next `rows` rows without moving the cursor (moved once the launch went out); false
+// when the buffer is too short
+static bool peek_noise(dcv_mlp* m, int64_t rows) {
+    if (m->noise == nullptr || m->noise_pos + rows > m->noise_rows) return false;
+    m->eps_cur = m->noise + m->noise_pos * m->vae_d;
+    return true;
+}
+
 static int forward_impl(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t* idx_d, int64_t row0, int32_t batch,
                         int32_t train, void* stream, int fuse_head = 0) {
     DCV_REQUIRE(m && Xn_d, "dcv_mlp_forward: null argument");
+    DCV_REQUIRE(batch >= 1 && batch <= m->desc.max_batch, "dcv_mlp_forward: batch=%d exceeds max_batch=%d", batch, m->desc.max_batch);
+    DCV_REQUIRE(ld >= m->desc.dims[0], "dcv_mlp_forward: ld=%lld < F=%d", (long long)ld, m->desc.dims[0]);
+    if (fuse_head) DCV_REQUIRE(m->log && m->log_cap > 0, "dcv_mlp step: call dcv_mlp_reset_log first");
+    if (m->vae_d > 0) {   // after every argument check, before any state changes: a refused step leaves the engine as it was
+        const int rcn = take_noise(m, batch);
+        if (rcn) return rcn;
+    }
     g_launch_ev = LaunchEvents{};   // an offer left behind by a launch that failed half way
     m->head_done = false;
     m->fwd_train = train != 0;
     if (m->fwd_train) m->cur_step = m->drop_step++;
-    DCV_REQUIRE(batch >= 1 && batch <= m->desc.max_batch, "dcv_mlp_forward: batch=%d exceeds max_batch=%d", batch, m->desc.max_batch);
-    DCV_REQUIRE(ld >= m->desc.dims[0], "dcv_mlp_forward: ld=%lld < F=%d", (long long)ld, m->desc.dims[0]);
     hipStream_t s = as_stream(stream);
     m->snet_fwd_valid = false;
     m->last_path = 0;
@@ -1894,7 +2045,8 @@ static int forward_impl(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t
         if (fuse_head) {   // one-GPU step: final sum and loss record in the last block of the same launch
             DCV_REQUIRE(m->log && m->log_cap > 0, "dcv_mlp step: call dcv_mlp_reset_log first");
             hipLaunchKernelGGL(ae_sse_kernel, dim3(nb), dim3(256), 0, s, net_out, last.ldh, Xn_d, ld, rm, R, m->desc.dims[0], m->feat_range, m->spart,
-                               m->ticket, m->stats, (double)batch, m->log, m->log_count, m->log_cap, m->log_width, (int)rpb);
+                               m->ticket, m->stats, (double)batch, m->log, m->log_count, m->log_cap, m->log_width, (int)rpb,
+                               (const double*)(m->vae_d > 0 ? m->vae_kpart : nullptr), m->vae_kblocks, m->kl_beta);
             DCV_CHECK_LAUNCH();
             m->head_done = true;
         } else {
@@ -1903,6 +2055,10 @@ static int forward_impl(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t
             DCV_CHECK_LAUNCH();
             hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(64), 0, s, m->spart, nb, 1, m->stats);
             DCV_CHECK_LAUNCH();
+            if (m->vae_d > 0) {   // [SSE | KL sum]
+                hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(64), 0, s, (const double*)m->vae_kpart, m->vae_kblocks, 1, m->stats + 1);
+                DCV_CHECK_LAUNCH();
+            }
         }
     }
     m->last_batch = batch;
@@ -2066,7 +2222,8 @@ static int backward_impl(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_
     } else {
         const int F = m->desc.dims[0];
         if (!m->head_done) {
-            hipLaunchKernelGGL(ae_log_kernel, dim3(1), dim3(64), 0, s, m->stats, (double)global_batch, F, m->log, m->log_count, m->log_cap, m->log_width);
+            hipLaunchKernelGGL(ae_log_kernel, dim3(1), dim3(64), 0, s, m->stats, (double)global_batch, F, m->log, m->log_count, m->log_cap, m->log_width,
+                               m->vae_d > 0 ? 1 : 0, m->kl_beta);
             DCV_CHECK_LAUNCH();
         }
         m->head_done = false;
@@ -2151,6 +2308,44 @@ static int backward_impl(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_
             rd.out = p.out;
             rd.splits = (int)splits;
             rd.bblocks = bblocks;
+            float* tmp = dz_cur;
+            dz_cur = dz_nxt;
+            dz_nxt = tmp;
+            continue;
+        }
+        if (m->vae_d > 0 && l == m->desc.latent_layer) {
+            // VAE, first decoder Linear: wgrad against z; dgrad dL/dz (no activation between the heads and z), turned in
+            // place into [dL/dmu | dL/dlv] by the reparameterisation's backward; the heads' bias partials by a column sum
+            LayerPlan& hd = m->layers[l - 1];
+            Operand A = make_operand(dz_cur, m->ld_dz, p.out);
+            Operand B = make_operand(m->vae_z, m->ld_z, p.in);
+            EpiSlab epi{p.slab, p.out, p.in, 1, 0, quad_ok(p.slab, p.in), p.max_splits};
+            ReduceDesc& rd = ra.l[l];
+            rd.slab = p.slab;
+            rd.bpart = p.bpart;
+            rd.w_off = p.w_off;
+            rd.b_off = p.b_off;
+            rd.w_count = (int64_t)p.out * p.in;
+            rd.out = p.out;
+            rd.splits = (int)splits;
+            rd.bblocks = bblocks;
+            prof_mark(m, l, 1, 0, s);
+            int rc = gemm_tn_slab(A, B, p.out, p.in, R, kc, epi, s);
+            if (rc) return rc;
+            prof_mark(m, l, 1, 1, s);
+            Operand Bd = make_operand(m->params + p.w_off, p.in, p.in);
+            EpiActGrad eg{dz_nxt, m->ld_dz, m->vae_z, m->ld_z, DCV_ACT_NONE, hd.bpart, p.in, quad_ok(dz_nxt, m->ld_dz) && quad_ok(m->vae_z, m->ld_z)};
+            int dblocks = 0;
+            prof_mark(m, l, 2, 0, s);
+            rc = gemm_nn_act_grad(A, Bd, R, p.in, p.out, eg, s, &dblocks, &m->tail);
+            if (rc) return rc;
+            hipLaunchKernelGGL(vae_sample_backward_kernel, dim3((unsigned)cdiv(R, kVaeRows)), dim3(kVaeRows), 0, s, (const float*)hd.H, hd.ldh, R,
+                               m->vae_d, m->eps_cur, dz_nxt, m->ld_dz, (float)(m->kl_beta / (double)global_batch));
+            DCV_CHECK_LAUNCH();
+            bblocks = (int)cdiv(R, kColsumRows);
+            hipLaunchKernelGGL(colsum_kernel, dim3(bblocks), dim3(256), 0, s, (const float*)dz_nxt, R, hd.out, m->ld_dz, hd.bpart);
+            DCV_CHECK_LAUNCH();
+            prof_mark(m, l, 2, 1, s);
             float* tmp = dz_cur;
             dz_cur = dz_nxt;
             dz_nxt = tmp;
@@ -2398,8 +2593,9 @@ static int apply_impl(dcv_mlp* m, void* stream) {
 // One-GPU autoencoder step as ONE fused launch (+ the gradient reduction with the optimiser update) when the network
 // fits in LDS (snet.hip); 1 = not applicable: the caller runs the layer-by-layer path.
 static int snet_step(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t* idx_d, int64_t row0, int32_t batch, int32_t train, void* stream) {
-    if (m->desc.model != DCV_MODEL_AE || m->any_drop || m->any_bn || (m->snet_tried && m->snet == nullptr)) return 1;
+    if ((m->desc.model != DCV_MODEL_AE && m->desc.model != DCV_MODEL_VAE) || m->any_drop || m->any_bn || (m->snet_tried && m->snet == nullptr)) return 1;
     if (!(Xn_d && batch >= 1 && batch <= m->desc.max_batch && ld >= m->desc.dims[0] && m->log && m->log_cap > 0)) return 1;   // the general path reports it
+    if (m->vae_d > 0 && !peek_noise(m, batch)) return 1;   // the general path refuses it
     hipStream_t s = as_stream(stream);
     const RowMap rm = RowMap{idx_d, row0, 0, 0};
     ReduceArgsView v;
@@ -2407,6 +2603,7 @@ static int snet_step(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t* i
     prof_mark(m, 0, 1, 0, s);
     int rc = snet_ae_step(m, Xn_d, ld, rm, batch, batch, train, &v, s);
     if (rc) return rc;
+    if (m->vae_d > 0) m->noise_pos += batch;   // the launch took the rows peek_noise pointed at
     prof_mark(m, 0, 0, 1, s);
     prof_mark(m, 0, 1, 1, s);
     m->fwd_train = train != 0;
@@ -2520,12 +2717,17 @@ extern "C" int dcv_mlp_eval_steps(dcv_mlp* m, const float* Xn_d, int64_t ld, con
         int rc = 1;
         if (nb > 1 && !m->any_drop && !m->any_bn && !prof_on(m, 0)) {   // (a profiled run samples single steps)
             g_launch_ev = LaunchEvents{};
-            if (m->desc.model == DCV_MODEL_AE && !(m->snet_tried && m->snet == nullptr)) {
+            if ((m->desc.model == DCV_MODEL_AE || m->desc.model == DCV_MODEL_VAE) && !(m->snet_tried && m->snet == nullptr)) {
                 const int tr = snet_ae_tile_rows(m, batch);
                 const int64_t per = cdiv((int64_t)batch, tr > 0 ? tr : 16);   // workgroups per batch
                 while (nb > 1 && per * nb > kEvalWorkgroupsPerLaunch) --nb;
+                if (m->vae_d > 0)   // VAE: as many batches as the noise buffer still covers (batch j takes eps rows [j * batch, (j + 1) * batch))
+                    while (nb > 1 && !peek_noise(m, (int64_t)nb * batch)) --nb;
                 if (nb > 1) rc = snet_ae_step(m, Xn_d, ld, RowMap{idx_j, row_j, 0, 0}, batch, batch, 0, nullptr, s, true, nb);
-                if (rc == DCV_OK) m->last_path = 1;
+                if (rc == DCV_OK) {
+                    m->last_path = 1;
+                    if (m->vae_d > 0) m->noise_pos += (int64_t)nb * batch;
+                }
             } else if (m->desc.model == DCV_MODEL_DEEPTICA && !(m->snet_dt_tried && m->snet_dt == nullptr)) {
                 const int64_t per = cdiv((int64_t)batch, 8);   // (an upper bound of the workgroups per batch: tiles of >= 8 pairs)
                 while (nb > 1 && per * nb > kEvalWorkgroupsPerLaunch) --nb;
@@ -2622,6 +2824,11 @@ static int dp_ae_fused(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t*
 extern "C" int dcv_mlp_dp_step(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t* idx_d, int64_t row0, int32_t batch,
                                int64_t global_batch, int32_t train, int32_t overlap, dcv_allreduce_fn fn, void* user, void* stream) {
     DCV_REQUIRE(m && fn, "dcv_mlp_dp_step: null argument");
+    if (m->vae_d > 0 && global_batch != batch) {
+        set_error("dcv_mlp_dp_step: the variational autoencoder is not implemented for data-parallel fits (global batch %lld != local batch %d); "
+                  "fit it on one GPU", (long long)global_batch, batch);
+        return DCV_EINVAL;
+    }
     {
         const int rcf = dp_ae_fused(m, Xn_d, ld, idx_d, row0, batch, global_batch, train, fn, user, stream);
         if (rcf != 1) return rcf;
@@ -2690,13 +2897,13 @@ extern "C" int dcv_mlp_infer(dcv_mlp* m, const float* Xn_d, int64_t n, int64_t l
     DCV_REQUIRE(n <= m->rows_cap, "dcv_mlp_infer: n=%lld exceeds the row capacity %lld (chunk the call)", (long long)n, (long long)m->rows_cap);
     DCV_REQUIRE((tmean_d == nullptr) == (tevecs_d == nullptr), "dcv_mlp_infer: tmean/tevecs must come together");
     hipStream_t s = as_stream(stream);
-    const int n_run = m->desc.model == DCV_MODEL_AE ? m->desc.latent_layer : m->L;
+    const int n_run = m->desc.model == DCV_MODEL_DEEPTICA ? m->L : m->desc.latent_layer;
     const RowMap rm = identity_rows();
     m->fwd_train = false;
     int rc = run_forward(m, Xn_d, ld, rm, n, n_run, s);
     if (rc) return rc;
     const LayerPlan& last = m->layers[n_run - 1];
-    const int d = last.out;
+    const int d = m->vae_d > 0 ? m->vae_d : last.out;   // VAE: the CV is the mean head, the first d of the 2d head columns
     // y = (h - tmean) @ tevecs ; out = (y - pmean) / prange   -- the linear projection kernel
     return dcv_project_linear(layer_out(m, n_run - 1), n, d, last.ldh, tmean_d ? tmean_d : m->zeros_d, m->ones_d, tevecs_d ? tevecs_d : m->ident, d,
                               nullptr, pmean_d, prange_d, out_d, minmax_d, m->proj_ws, m->proj_ws_bytes, stream);
@@ -2722,7 +2929,7 @@ extern "C" int dcv_mlp_input_sensitivity(dcv_mlp* m, const float* Xn_d, int64_t 
     hipStream_t s = as_stream(stream);
     const int F = m->desc.dims[0];
     DCV_REQUIRE(ld >= F, "dcv_mlp_input_sensitivity: ld=%lld < F=%d", (long long)ld, F);
-    const int n_run = m->desc.model == DCV_MODEL_AE ? m->desc.latent_layer : m->L;
+    const int n_run = m->desc.model == DCV_MODEL_DEEPTICA ? m->L : m->desc.latent_layer;
     m->fwd_train = false;
     int rc = run_forward(m, Xn_d, ld, identity_rows(), n, n_run, s);
     if (rc) return rc;

@@ -80,7 +80,18 @@ struct dcv_mlp {
     int64_t graph_launches;    // steps / half-steps that went out as one graph launch
     bool prof_paused;          // profiling armed but skipped for the current calls (dcv_mlp_profile_pause)
     int log_cap, log_width;
-    float* feat_range;         // AE
+    float* feat_range;         // AE, VAE
+    // VAE (DCV_MODEL_VAE): Linear latent_layer - 1 is the two heads [mean | log-variance] (2 * vae_d columns), Linear
+    // latent_layer reads z = mean + exp(log-variance / 2) * eps
+    int vae_d;                 // latent dimension d (0: not a VAE)
+    float* vae_z;              // [rows_cap][ld_z] sampled latent of the last forward
+    int64_t ld_z;
+    double* vae_kpart;         // per-block KL partials of the sampling kernel
+    int vae_kblocks;           // blocks of the last sampling launch
+    double kl_beta;            // weight of the KL term (dcv_mlp_set_kl_beta)
+    const float* noise;        // caller's eps buffer [noise_rows][vae_d] (dcv_mlp_set_noise) or null
+    int64_t noise_rows, noise_pos;
+    const float* eps_cur;      // eps rows of the last forward (noise + its first row * vae_d)
     float *ident, *zeros_d, *ones_d;  // helpers for inference
     float* proj_ws;
     size_t proj_ws_bytes;

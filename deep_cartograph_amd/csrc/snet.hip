@@ -48,6 +48,14 @@ struct SnetArgs {
     double* log;
     int* log_count;
     int log_cap, log_width;
+    // variational autoencoder (DCV_MODEL_VAE): Linear vae_l (the first decoder Linear) reads z = mu + exp(lv / 2) * eps, sampled
+    // from the heads' output H_{vae_l} = [mu | lv] into its own tile Z [TR][pz]; vae_l = -1 for the autoencoder
+    int vae_l, vae_d;
+    int lz, pz;
+    const float* eps;             // eps rows of the launch's first batch (batch j: + j * R * vae_d), dense [rows][vae_d]
+    double beta;                  // weight of the KL term
+    float beta_b;                 // beta / global batch
+    double* kl_part;              // per-workgroup KL partials (beside sse_part, through the same hand-off)
     unsigned long long* stamps;   // diagnostic (dcv_debug_snet_stamps): s_memrealtime of workgroup 0 at the phase boundaries, or null
 };
 #define SNET_STAMP(k)                                                                          \
@@ -55,7 +63,9 @@ struct SnetArgs {
         if (a.stamps != nullptr && blockIdx.x == 0 && threadIdx.x == 0) a.stamps[k] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
 
-template <int TR>
+// VAE: the variational autoencoder's form (z sampling, KL partials, dL/dz -> [dL/dmu | dL/dlv]); a separate instantiation, so the
+// autoencoder's kernel keeps its register budget
+template <int TR, bool VAE>
 __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
     constexpr int NT = kSnetThreads;
     constexpr int RG = TR / 16, CG = kSnetWaves / RG;
@@ -181,12 +191,30 @@ __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
     __syncthreads();
     SNET_STAMP(2);
     // ---- forward chain
-    double sse = 0.0;
+    double sse = 0.0, kl = 0.0;
     for (int l = 0; l < L; ++l) {
         const SnetLayer& y = a.l[l];
-        const float* Hin = sl + a.lh[l];
+        if (VAE && l == a.vae_l) {
+            // VAE: z = eps * exp(lv / 2) + mu into the Z tile (zero padding and rows past the batch), KL terms of the tile's rows
+            const int d = a.vae_d, psh = a.ps[l];
+            const float* Hh = sl + a.lh[l];
+            float* Z = sl + a.lz;
+            const float* ep = a.eps + ((int64_t)bj * a.R + r0) * d;
+            for (int i = t; i < TR * a.pz; i += NT) {
+                const int r = i / a.pz, c = i - r * a.pz;
+                float z = 0.f;
+                if (c < d && r0 + r < a.R) {
+                    const float mu = Hh[r * psh + c], lv = Hh[r * psh + d + c];
+                    z = __fadd_rn(__fmul_rn(ep[r * d + c], expf(0.5f * lv)), mu);
+                    kl += -0.5 * ((double)lv - exp((double)lv) - (double)mu * (double)mu + 1.0);
+                }
+                Z[i] = z;
+            }
+            __syncthreads();
+        }
+        const float* Hin = VAE && l == a.vae_l ? sl + a.lz : sl + a.lh[l];
         float* Hout = sl + a.lh[l + 1];
-        const int psin = a.ps[l], pso = a.ps[l + 1];
+        const int psin = VAE && l == a.vae_l ? a.pz : a.ps[l], pso = a.ps[l + 1];
         const bool last = l == L - 1;
         const float* ap = Hin + (rg * 16 + n) * psin + 4 * q;
         const float* W = sl + y.lw + n * y.pws + 4 * q;
@@ -226,14 +254,24 @@ __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
         // waves by shuffles, the eight wave sums in wave order by one thread (a fixed order: deterministic)
         double* red = reinterpret_cast<double*>(sl + a.lred);
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sse += __shfl_down(sse, off, 64);
-        if (lane == 0) red[wave] = sse;
+        for (int off = 32; off > 0; off >>= 1) {
+            sse += __shfl_down(sse, off, 64);
+            if (VAE) kl += __shfl_down(kl, off, 64);
+        }
+        if (lane == 0) {
+            red[wave] = sse;
+            red[kSnetWaves + wave] = kl;
+        }
         __syncthreads();
         if (t == 0) {
-            double tot = red[0];
+            double tot = red[0], ktot = red[kSnetWaves];
 #pragma unroll
-            for (int w = 1; w < kSnetWaves; ++w) tot += red[w];
+            for (int w = 1; w < kSnetWaves; ++w) {
+                tot += red[w];
+                ktot += red[kSnetWaves + w];
+            }
             handoff_store(a.sse_part + blockIdx.x, tot);
+            if (VAE) handoff_store(a.kl_part + blockIdx.x, ktot);
         }
     }
     SNET_STAMP(20);
@@ -245,6 +283,8 @@ __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
             const float* dZ = sl + a.lh[l + 1];
             float* Hin = sl + a.lh[l];
             const int psz = a.ps[l + 1], psh = a.ps[l];
+            const float* Hw = VAE && l == a.vae_l ? sl + a.lz : Hin;   // input of this Linear (VAE: z for the first decoder Linear)
+            const int psw = VAE && l == a.vae_l ? a.pz : psh;
             // input gradient first, kept in registers
             sv4f dg[kSnetMaxTiles];
             if (l > 0) {
@@ -273,7 +313,7 @@ __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
                     // operands swapped (rows of the MFMA tile = input columns): a lane ends up with four CONSECUTIVE inputs
                     // i of one output o = its 16 bytes of the partial's row -- one global_store_dwordx4 per tile and lane
                     // instead of four 4-byte stores (the partial stores of the two wide layers were what these phases waited on)
-                    const sv4f acc = snet_wgrad_tile<TR>(Hin + q * psh + it * 16 + n, psh, dZ + q * psz + ot * 16 + n, psz);
+                    const sv4f acc = snet_wgrad_tile<TR>(Hw + q * psw + it * 16 + n, psw, dZ + q * psz + ot * 16 + n, psz);
                     const int o = ot * 16 + n, i0 = it * 16 + 4 * q;
                     if (o < y.out) {
                         float* dst = pw + (int64_t)o * y.in + i0;
@@ -305,6 +345,38 @@ __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
             if (l == 0) break;
             __syncthreads();   // every wave is done reading H_l
             const int act_prev = a.l[l - 1].act, out_prev = a.l[l - 1].out;
+            if (VAE && l == a.vae_l) {
+                // dL/dz (no activation between z and this Linear) -> [dL/dmu | dL/dlv] over H_l = [mu | lv]: the thread of column
+                // j < d owns columns j and d + j of its rows, columns [d, 2d) have no thread of their own, the padding is zeroed.
+                const int d = a.vae_d;
+                const float* ep = a.eps + ((int64_t)bj * a.R + r0) * d;
+#pragma unroll
+                for (int j = 0; j < kSnetMaxTiles; ++j) {
+                    const int it = cg + j * CG;
+                    if (it < y.nk_in) {
+                        const int col = it * 16 + n;
+                        float* p = Hin + (rg * 16 + 4 * q) * psh + col;
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) {
+                            const int r = rg * 16 + 4 * q + v;
+                            if (col < d) {
+                                float gm = 0.f, gl = 0.f;
+                                if (r0 + r < a.R) {
+                                    const float mu = p[v * psh], lv = p[v * psh + d], e = ep[r * d + col], dz = dg[j][v];
+                                    gm = dz + a.beta_b * mu;
+                                    gl = dz * e * 0.5f * expf(0.5f * lv) + a.beta_b * 0.5f * (expf(lv) - 1.f);
+                                }
+                                p[v * psh] = gm;
+                                p[v * psh + d] = gl;
+                            } else if (col >= out_prev) {
+                                p[v * psh] = 0.f;
+                            }
+                        }
+                    }
+                }
+                __syncthreads();
+                continue;
+            }
 #pragma unroll
             for (int j = 0; j < kSnetMaxTiles; ++j) {
                 const int it = cg + j * CG;
@@ -334,20 +406,33 @@ __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
         const double* sp = a.sse_part + (int64_t)bj * wgpb;
         for (int b0 = t; b0 < (int)wgpb; b0 += 64) tot += handoff_load(sp + b0);
         for (int off = 32; off > 0; off >>= 1) tot += __shfl_down(tot, off, 64);
+        const bool vae = VAE;
+        double kl = 0.0;   // VAE: the KL partials, the same lane / shuffle order
+        if (vae) {
+            const double* kp = a.kl_part + (int64_t)bj * wgpb;
+            for (int b0 = t; b0 < (int)wgpb; b0 += 64) kl += handoff_load(kp + b0);
+            for (int off = 32; off > 0; off >>= 1) kl += __shfl_down(kl, off, 64);
+        }
         if (t == 0) {
             if (a.nb <= 1) a.stats[0] = tot;
+            if (a.nb <= 1 && vae) a.stats[1] = kl;
             if (a.log != nullptr) {   // (a data-parallel step logs after the all-reduce of the sum: ae_log_kernel)
                 // a batched evaluation appends its records in batch order: every batch's last arriver reads the counter, the last
                 // of those (a second ticket, taken behind the read) moves it
                 const int slot0 = *a.log_count;
                 const int slot = slot0 + bj;
                 if (slot < a.log_cap) {
-                    a.log[(int64_t)slot * a.log_width + 0] = tot / (a.Bg * (double)a.l[0].in);
+                    const double rec = tot / (a.Bg * (double)a.l[0].in);
+                    a.log[(int64_t)slot * a.log_width + 0] = vae ? rec + a.beta * (kl / a.Bg) : rec;
                     a.log[(int64_t)slot * a.log_width + 1] = a.Bg;
+                    if (vae) {
+                        a.log[(int64_t)slot * a.log_width + 2] = rec;
+                        a.log[(int64_t)slot * a.log_width + 3] = kl / a.Bg;
+                    }
                 }
                 if (a.nb <= 1) {
                     *a.log_count = slot + 1;
-                } else {
+                } else if (!VAE) {   // (the VAE's batched pass leaves the counter to snet_log_advance_kernel, launched behind it)
                     asm volatile("s_waitcnt vmcnt(0) ; the counter has been read" ::: "memory");
                     const unsigned prev = __hip_atomic_fetch_add(a.ticket + a.nb, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if (prev == (unsigned)a.nb - 1u) {
@@ -358,6 +443,11 @@ __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
             }
         }
     }
+}
+
+// the log counter behind a batched VAE evaluation launch (whose batches only read it): + nb records
+__global__ void snet_log_advance_kernel(int* __restrict__ log_count, int n) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *log_count += n;
 }
 
 struct SnetPlan {
@@ -373,6 +463,7 @@ struct SnetPlan {
     int64_t ev_sse_n;
     unsigned* ev_ticket; // ... and one ticket per batch + the one that moves the log counter (zero between launches)
     int64_t ev_ticket_n;
+    double* kl_part;     // VAE: KL partials [workgroups of the launch] (kEvalWorkgroupsPerLaunch), or null
 };
 
 // Activation map of a TR-row tile behind the weight images (H_0 .. H_L, the reduction scratch); returns the LDS bytes, 0 when
@@ -385,6 +476,11 @@ static size_t snet_ae_map(SnetArgs& a, int L, int fl, int TR) {
         a.ps[l] = P + 4;
         a.lh[l] = f;
         f += TR * (P + 4);
+    }
+    if (a.vae_l >= 0) {   // the z tile: the decoder's input, apart from the heads' output it is sampled from
+        a.pz = a.l[a.vae_l].pin + 4;
+        a.lz = f;
+        f += TR * a.pz;
     }
     f = (f + 3) / 4 * 4;
     a.lred = f;
@@ -409,15 +505,28 @@ static int snet_ae_pick_tr(const SnetPlan* pl, int64_t R) {
 // Builds the plan once per engine.  Not applicable (returns false): wide layers, dropout, a network that does not fit
 // in LDS with at least 16-row tiles.
 static bool snet_build(dcv_mlp* m) {
-    if (m->desc.model != DCV_MODEL_AE || m->any_drop || snet_disabled()) return false;
+    if ((m->desc.model != DCV_MODEL_AE && m->desc.model != DCV_MODEL_VAE) || m->any_drop || snet_disabled()) return false;
     SnetPlan* pl = new (std::nothrow) SnetPlan();
     if (!pl) return false;
     SnetArgs& a = pl->base;
     a.L = m->L;
+    a.vae_l = m->vae_d > 0 ? m->desc.latent_layer : -1;
+    a.vae_d = m->vae_d;
+    a.lz = a.pz = 0;
+    pl->kl_part = nullptr;
+    if (m->vae_d > 0 && hipMalloc(reinterpret_cast<void**>(&pl->kl_part), (size_t)kEvalWorkgroupsPerLaunch * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        delete pl;
+        return false;
+    }
     int fl = 0;
     int64_t per_wg = 0;
     std::vector<int2> tab;
-    if (!snet_layout(m, a.l, tab, nullptr, fl, per_wg)) { delete pl; return false; }
+    if (!snet_layout(m, a.l, tab, nullptr, fl, per_wg)) {
+        if (pl->kl_part) (void)hipFree(pl->kl_part);
+        delete pl;
+        return false;
+    }
     pl->per_wg = per_wg;
     (void)snet_image_build(m);   // on failure the kernels keep the table-driven staging
     pl->stage_tab = nullptr;
@@ -425,6 +534,7 @@ static bool snet_build(dcv_mlp* m) {
         hipMemcpy(pl->stage_tab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
         if (pl->stage_tab) (void)hipFree(pl->stage_tab);
+        if (pl->kl_part) (void)hipFree(pl->kl_part);
         delete pl;
         return false;
     }
@@ -466,6 +576,7 @@ static bool snet_build(dcv_mlp* m) {
         return true;
     }
     (void)hipFree(pl->stage_tab);
+    if (pl->kl_part) (void)hipFree(pl->kl_part);
     delete pl;
     return false;
 }
@@ -536,6 +647,7 @@ void snet_free(dcv_mlp* m) {
     if (pl->stage_tab) (void)hipFree(pl->stage_tab);
     if (pl->ev_sse) (void)hipFree(pl->ev_sse);
     if (pl->ev_ticket) (void)hipFree(pl->ev_ticket);
+    if (pl->kl_part) (void)hipFree(pl->kl_part);
     delete pl;
     m->snet = nullptr;
 }
@@ -570,6 +682,7 @@ int snet_ae_step(dcv_mlp* m, const float* Xn_d, int64_t ld, const RowMap& rm, in
     if (nb < 1 || (nb > 1 && (train || !write_log))) return 1;
     const int64_t nwg = wgpb * nb;
     if (nb > 1 && (nwg > pl->ev_sse_n || nb + 1 > pl->ev_ticket_n)) return 1;   // (sized by snet_build for the bounds of dcv_mlp_eval_steps)
+    if (m->vae_d > 0 && (pl->kl_part == nullptr || nwg > kEvalWorkgroupsPerLaunch || m->eps_cur == nullptr)) return 1;
     const int64_t part_need = nwg * pl->per_wg + 8 * (int64_t)m->L;   // + the alignment padding of the items
     if (train && pl->part_floats < part_need) {
         if (pl->part) (void)hipFree(pl->part);
@@ -619,10 +732,14 @@ int snet_ae_step(dcv_mlp* m, const float* Xn_d, int64_t ld, const RowMap& rm, in
     a.log_count = m->log_count;
     a.log_cap = m->log_cap;
     a.log_width = m->log_width;
+    a.eps = m->eps_cur;
+    a.beta = m->kl_beta;
+    a.beta_b = (float)(m->kl_beta / (double)batch);
+    a.kl_part = pl->kl_part;
     a.stamps = pl->stamps;
     auto launch = [&](auto kern) -> int {
-        static int attr_state[2] = {0, 0};   // 0 unknown, 1 set, -1 refused by the runtime (the fused form is then off)
-        const int slot = TR == 32 ? 0 : 1;
+        static int attr_state[4] = {0, 0, 0, 0};   // 0 unknown, 1 set, -1 refused by the runtime (the fused form is then off)
+        const int slot = (TR == 32 ? 0 : 1) + (a.vae_l >= 0 ? 2 : 0);
         if (attr_state[slot] == 0) {
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) (void)hipGetLastError();
@@ -640,7 +757,15 @@ int snet_ae_step(dcv_mlp* m, const float* Xn_d, int64_t ld, const RowMap& rm, in
         DCV_CHECK_LAUNCH();
         return DCV_OK;
     };
-    return TR == 32 ? launch(snet_ae_kernel<32>) : launch(snet_ae_kernel<16>);
+    if (a.vae_l >= 0) {
+        const int rc = TR == 32 ? launch(snet_ae_kernel<32, true>) : launch(snet_ae_kernel<16, true>);
+        if (rc == DCV_OK && nb > 1 && a.log != nullptr) {
+            hipLaunchKernelGGL(snet_log_advance_kernel, dim3(1), dim3(64), 0, s, m->log_count, nb);
+            DCV_CHECK_LAUNCH();
+        }
+        return rc;
+    }
+    return TR == 32 ? launch(snet_ae_kernel<32, false>) : launch(snet_ae_kernel<16, false>);
 }
 
 }  // namespace dcv

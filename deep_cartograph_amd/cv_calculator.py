@@ -109,7 +109,7 @@ class CVCalculator(ABC):
             logger.error(f"Metadata file not found in the model: {metadata_path}")
         if not cv_name:
             raise ValueError("Could not determine the CV name from the model file.")
-        klass = cv_calculators_map.get(cv_name)
+        klass = calculator_class(cv_name)
         if not klass:
             raise TypeError(f"Unknown CV calculator name: {cv_name}")
         inst = klass(output_path=output_path)
@@ -688,6 +688,7 @@ class _HostLRScheduler:
         self.monitor = config.get("monitor", "valid_loss")
         self.engine = engine
         self.count = 0
+        self.plateau_from: Optional[int] = None   # VAE: LROnPlateauManager's extra step from this epoch on (set by the calculator)
         self.push()
 
     def push(self):
@@ -722,6 +723,13 @@ class _HostLRScheduler:
     def after_epoch(self, last_valid_loss):
         if self.interval == "epoch":
             self._advance(last_valid_loss)
+
+    def on_validation_end(self, epoch: int, valid_loss: float):
+        """The reference's LROnPlateauManager (VAE, modules/ml/ml.py): at the end of every validation from epoch `plateau_from`
+        on, ReduceLROnPlateau is stepped once more with the validation loss, outside lightning's interval / frequency."""
+        if self.plateau and self.plateau_from is not None and epoch >= self.plateau_from:
+            self.sched.step(valid_loss)
+            self.push()
 
 
 class NonLinear(CVCalculator):
@@ -1092,6 +1100,7 @@ class NonLinear(CVCalculator):
         metrics: Dict[str, list] = {"train_loss": [], "valid_loss": [], "epoch": []}
         if sched is not None:
             metrics["lr"] = []
+        self._fit_begin(sched, n_va, bs)
         best_score, best_state, last_state = float("inf"), None, None
         es_best, wait = float("inf"), 0
         last_valid = None
@@ -1099,7 +1108,7 @@ class NonLinear(CVCalculator):
         for epoch in range(self.max_epochs):
             tb = next_tb if next_tb is not None else self._batches(train_part, bs, dev)
             do_val = (epoch + 1) % self.check_val_every_n_epoch == 0
-            vb = self._batches(val_part, bs, dev) if do_val else []
+            vb = self._epoch_begin(epoch, tb, lambda: self._batches(val_part, bs, dev) if do_val else [])
             self.engine.reset_log(len(tb) + len(vb))
             # (a scheduler stepped per EPOCH -- lightning's default interval -- has nothing to do between the steps of an epoch)
             self._run_batches(Xn_train, tb, True, gb, per_step=sched.after_step if sched is not None and sched.interval == "step" else None)
@@ -1123,6 +1132,11 @@ class NonLinear(CVCalculator):
                 metrics["epoch"].append(epoch)
                 if sched is not None:
                     metrics["lr"].append(sched.lr())
+                self._on_validation(epoch, rec[:len(tb)], rec[len(tb):], valid_loss, metrics,
+                                    lambda: {"linears": self.engine.get_linears(), "tica": buffers, "dims": dims, "acts": acts, "drops": drops,
+                                             "latent": latent, "bn": self.engine.get_bn() if any(getattr(self, "_bn_plan", None) or []) else None})
+                if sched is not None:
+                    sched.on_validation_end(epoch, valid_loss)
                 if eig is not None:
                     for i, v in enumerate(eig):
                         metrics.setdefault(f"valid_eigval_{i + 1}", []).append(float(v))
@@ -1145,20 +1159,36 @@ class NonLinear(CVCalculator):
                 break
         if metrics["valid_loss"] and min(metrics["valid_loss"]) > metrics["valid_loss"][0]:
             logger.warning(f"Try {try_num}: validation loss did not decrease during training.")
-        # _finalize_training (reference :1555-1642): "best" = the checkpoint with the lowest monitored loss and that
-        # loss; "last" = the last checkpoint written, scored with the FINAL validation loss of the run
-        if self.model_to_save == "best" and best_state is not None:
-            state, score = best_state, best_score
-        elif last_state is not None:
-            state, score = last_state, metrics["valid_loss"][-1]
-        else:
+        chosen = self._choose_model(best_state, best_score, last_state, metrics)
+        if chosen is None:
             logger.error("Training finished, but no valid model checkpoint was found.")
             return None
+        state, score = chosen
         if self.cv_name == "deep_tica" and score < -float(self.cv_dimension):
             logger.warning(f"Deep TICA validation loss ({score:.5f}) is below the theoretical minimum "
                            f"({-float(self.cv_dimension):.5f}). Try reducing the learning rate or increasing 'tica_regularization'.")
             return None
         return {"state": state, "score": score, "metrics": metrics}
+
+    # ---- per-model hooks of the epoch loop (the VAE's noise, beta and post-annealing checkpoint; no-ops here)
+    def _fit_begin(self, sched, n_val: int, bs: int):
+        """Before the first epoch (after the model and the split exist)."""
+
+    def _epoch_begin(self, epoch: int, tb, make_val_batches):
+        """Start of an epoch: the training batches exist; returns the validation batches (make_val_batches())."""
+        return make_val_batches()
+
+    def _on_validation(self, epoch: int, rec_train: np.ndarray, rec_val: np.ndarray, valid_loss: float, metrics: Dict, snapshot):
+        """After every validation pass; snapshot() returns the current model state."""
+
+    def _choose_model(self, best_state, best_score, last_state, metrics):
+        """_finalize_training (reference :1555-1642): "best" = the checkpoint with the lowest monitored loss and that loss;
+        "last" = the last checkpoint written, scored with the FINAL validation loss of the run.  (state, score) or None."""
+        if self.model_to_save == "best" and best_state is not None:
+            return best_state, best_score
+        if last_state is not None:
+            return last_state, metrics["valid_loss"][-1]
+        return None
 
     def compute_cv(self):
         if self.train():
@@ -1441,6 +1471,217 @@ class DeepTICACalculator(NonLinear):
         return ok
 
 
+def kl_annealing_settings(section: Optional[Dict], max_epochs: int) -> Dict:
+    """The VAE's KL-annealing parameters (reference VAECalculator.__init__, cv_calculator.py:2645-2660): the configured
+    `training.kl_annealing` section, or the defaults when it is absent.  Checked as KLAAnnealing.__init__ checks them: an
+    unknown type, or a cyclical schedule with fewer annealing epochs than cycles, raises ValueError here."""
+    if section is not None:
+        kl = {"type": section.get("type"), "start_beta": section.get("start_beta"), "max_beta": section.get("max_beta"),
+              "start_epoch": section.get("start_epoch", max_epochs // 2), "n_cycles": section.get("n_cycles"),
+              "n_epochs_anneal": section.get("n_epochs_anneal", max_epochs // 4)}
+    else:
+        kl = {"type": "sigmoid", "start_beta": 1e-06, "max_beta": 0.01, "start_epoch": max_epochs // 2, "n_cycles": 1,
+              "n_epochs_anneal": max_epochs // 4}
+    if kl["type"] not in ("linear", "sigmoid", "cyclical"):
+        raise ValueError("Invalid type for KLAAnnealing. Must be 'linear' or 'cyclical'.")
+    if kl["type"] == "cyclical" and kl["n_epochs_anneal"] < kl["n_cycles"]:
+        raise ValueError("n_epochs_anneal must be greater than or equal to n_cycles for cyclical annealing.")
+    return kl
+
+
+def kl_beta(epoch: int, kl: Dict) -> float:
+    """beta of `epoch` as the reference's KLAAnnealing callback sets it at the start of that epoch (modules/ml/ml.py): start_beta
+    up to and including start_epoch, then the linear / sigmoid / cyclical schedule of the epochs since start_epoch."""
+    kind, b0, b1, start, n_anneal = kl["type"], kl["start_beta"], kl["max_beta"], kl["start_epoch"], kl["n_epochs_anneal"]
+    if kind not in ("linear", "sigmoid", "cyclical"):
+        raise ValueError("Invalid type for KLAAnnealing. Must be 'linear' or 'cyclical'.")
+
+    def linear(e, n):
+        if e >= n:
+            return b1
+        return b0 + (b1 - b0) * (e / n)
+
+    if epoch <= start:
+        return b0
+    e = epoch - start
+    if kind == "linear":
+        return float(linear(e, n_anneal))
+    if kind == "cyclical":
+        if e >= n_anneal:
+            return float(b1)
+        cycle_length = n_anneal // kl["n_cycles"]
+        return float(linear(e % cycle_length, cycle_length // 2))
+    eps = 1e-3
+    midpoint = start + n_anneal // 2
+    steepness = np.log(eps / (1 - eps)) / (start - midpoint)
+    return float(b0 + (b1 - b0) / (1 + np.exp(-steepness * (e + start - midpoint))))
+
+
+def plateau_manager_start(kl: Dict, max_epochs: int) -> int:
+    """First epoch of the reference's LROnPlateauManager for a VAE (cv_calculator.py VAECalculator.get_callbacks): the end of
+    the annealing plus a quarter of the epochs left after it."""
+    end = kl["start_epoch"] + kl["n_epochs_anneal"]
+    return end + (max_epochs - kl["start_epoch"] - kl["n_epochs_anneal"]) // 4
+
+
+class VAECalculator(NonLinear):
+    """Variational autoencoder CV (reference :2629-2900, mlcolvar VariationalAutoEncoderCV): encoder [F] + layers (every Linear
+    with its activation and dropout), two heads mean_nn / log_var_nn (h -> d, no activation), decoder [d] + layers + [F];
+    loss = reconstruction (the AE's) + beta * KL, z = mu + exp(lv / 2) * eps, beta annealed per epoch.  The CV is the mean
+    head.  In the engine the heads are ONE Linear of 2d outputs (mean rows, then log-variance rows: dcv.h DCV_MODEL_VAE).
+    eps is drawn on the host from torch's global generator, one randn(batch, d) per batch in loader order (training batches,
+    then validation batches), and uploaded once per epoch.  Lightning runs its sanity validation before epoch 0 inside
+    isolate_rng() (trainer._run_stage), so it leaves the generator where it was and draws nothing here.  Dropout masks come
+    from the engine's own generator, as for the AE."""
+
+    model_kind = "vae"
+
+    def __init__(self, configuration: Optional[Dict] = None, output_path: Optional[str] = None):
+        super().__init__(configuration, output_path)
+        self.cv_name = "vae"
+        self.kl = kl_annealing_settings(self.training_config.get("kl_annealing"), self.max_epochs)
+        self._post_best: Optional[Tuple[float, Dict]] = None
+
+    def _encoder_options(self):
+        n = len(self.encoder_hidden_layers)
+        act, drop, bn = self._layer_options(self.encoder_config, n)
+        return act[:n], drop[:n], bn[:n]   # the heads take the place of the last-layer entries (set_up_encoder_last_layer)
+
+    def layer_plan(self):
+        if self.comm.world > 1:
+            raise ValueError("the VAE is not supported in a frame-sharded (multi-GPU) fit: run this CV on one GPU")
+        enc_act, enc_drop, enc_bn = self._encoder_options()
+        dec_cfg = self.decoder_config if self.decoder_config is not None else self.encoder_config
+        dec_act, dec_drop, dec_bn = self._layer_options(dec_cfg, len(self.decoder_hidden_layers))
+        if self.feats_norm_mode == "min_max_range1" and dec_act[-1] != "custom_sigmoid":
+            logger.warning(f"The last layer activation function of the decoder is set to {dec_act[-1]}, but the features are "
+                           "normalized using min max with range [0, 1]. Changing the activation function to 'sigmoid'.")
+            dec_act[-1] = "custom_sigmoid"
+        elif self.feats_norm_mode == "min_max_range2" and dec_act[-1] != "tanh":
+            logger.warning(f"The last layer activation function of the decoder is set to {dec_act[-1]}, but the features are "
+                           "normalized using min max with range [-1, 1]. Changing the activation function to 'tanh'.")
+            dec_act[-1] = "tanh"
+        if dec_drop[-1]:
+            logger.warning("Dropout in the last layer of the decoder is not recommended.")
+        self._bn_plan = enc_bn + [False] + dec_bn
+        enc = [self.num_features] + self.encoder_hidden_layers + [2 * self.cv_dimension]
+        dec = [self.cv_dimension] + self.decoder_hidden_layers + [self.num_features]
+        return enc + dec[1:], enc_act + [None] + dec_act, enc_drop + [0.0] + dec_drop, len(enc) - 1
+
+    def _init_linears(self, dims):
+        """Construction order of VariationalAutoEncoderCV: encoder Linears, mean_nn, log_var_nn, decoder Linears (global RNG);
+        the heads are concatenated into the engine's one 2d-output Linear."""
+        L = len(self.encoder_hidden_layers) + 1   # the first decoder Linear
+        d = self.cv_dimension
+        lins = [torch.nn.Linear(dims[i], dims[i + 1]) for i in range(L - 1)]
+        mean, log_var = torch.nn.Linear(dims[L - 1], d), torch.nn.Linear(dims[L - 1], d)
+        dec = [torch.nn.Linear(d if i == L else dims[i], dims[i + 1]) for i in range(L, len(dims) - 1)]
+        out = [(l.weight.detach().numpy().copy(), l.bias.detach().numpy().copy()) for l in lins]
+        out.append((torch.cat([mean.weight, log_var.weight]).detach().numpy().copy(), torch.cat([mean.bias, log_var.bias]).detach().numpy().copy()))
+        return out + [(l.weight.detach().numpy().copy(), l.bias.detach().numpy().copy()) for l in dec]
+
+    def n_samples_local(self) -> int:
+        return self.training_data.shape[0]
+
+    def n_val_samples_local(self) -> int:
+        return self.validation_data.shape[0]
+
+    def _records_to_metrics(self, rec, need_eig: bool = True):
+        w = rec[:, 1]
+        return float((rec[:, 0] * w).sum() / w.sum()), None, None
+
+    # ---- the epoch loop's hooks
+    def _noise_for(self, batches) -> List[torch.Tensor]:
+        return [torch.randn(batches.size(i), self.cv_dimension) for i in range(len(batches))]
+
+    def _fit_begin(self, sched, n_val: int, bs: int):
+        self.engine.set_feature_range(self.features_norm_range)
+        self._post_best = None
+        if sched is not None and sched.plateau:
+            sched.plateau_from = plateau_manager_start(self.kl, self.max_epochs)
+
+    def _epoch_begin(self, epoch: int, tb, make_val_batches):
+        self._beta = kl_beta(epoch, self.kl)
+        self.engine.set_kl_beta(self._beta)
+        eps = self._noise_for(tb)
+        vb = make_val_batches()
+        if len(vb):
+            eps += self._noise_for(vb)
+        dev = self.training_normalized.device
+        self.engine.set_noise(torch.cat(eps).to(dev) if eps else torch.zeros(0, self.cv_dimension, device=dev))   # one copy per epoch
+        return vb
+
+    def _on_validation(self, epoch, rec_train, rec_val, valid_loss, metrics, snapshot):
+        for tag, rec in (("train", rec_train), ("valid", rec_val)):
+            w = rec[:, 1]
+            metrics.setdefault(f"{tag}_reconstruction_loss", []).append(float((rec[:, 2] * w).sum() / w.sum()))
+            metrics.setdefault(f"{tag}_kl_loss", []).append(float((rec[:, 3] * w).sum() / w.sum()))
+        metrics.setdefault("beta", []).append(self._beta)
+        # PostAnnealingCheckpoint: the lowest valid_loss from the end of the annealing on (only with an annealing stage)
+        if self.kl["n_epochs_anneal"] > 0 and epoch >= self.kl["start_epoch"] + self.kl["n_epochs_anneal"]:
+            if self._post_best is None or valid_loss < self._post_best[0]:
+                self._post_best = (valid_loss, snapshot())
+
+    def _choose_model(self, best_state, best_score, last_state, metrics):
+        """model_to_save 'best' of a VAE = the best post-annealing checkpoint; without one, the last (reference :1575-1600)."""
+        if self.model_to_save == "best":
+            if self._post_best is not None:
+                return self._post_best[1], self._post_best[0]
+            logger.warning("Best post-annealing model not found, falling back to last model.")
+        if last_state is not None:
+            return last_state, metrics["valid_loss"][-1]
+        return None
+
+    def train(self) -> bool:
+        ok = super().train()
+        if ok:
+            self.cv["norm_in"] = (self.features_norm_mean, self.features_norm_range)
+        return ok
+
+    def plot_training_metrics(self):
+        """training_metrics.zip with the VAE's metrics beside the common ones (reference :2880-2893; no figures)."""
+        if not self.training_config.get("save_loss", True) or self.metrics is None:
+            return
+        paths = []
+        for key in ("train_loss", "valid_loss", "epoch", "train_kl_loss", "valid_kl_loss", "train_reconstruction_loss",
+                    "valid_reconstruction_loss", "beta", "lr"):
+            if key not in self.metrics:
+                if key == "lr":
+                    logger.warning(f"Metric {key} not found in metrics. It will not be saved.")
+                continue
+            p = os.path.join(self.training_output_folder, f"{key}.npy")
+            np.save(p, np.array(self.metrics[key]))
+            paths.append(p)
+        np.savetxt(os.path.join(self.training_output_folder, "model_score.txt"), np.array([self.cv_score]), fmt="%.7g")
+        zip_files(os.path.join(self.training_output_folder, "training_metrics.zip"), *paths)
+        remove_files(*paths)
+
+    # ---- projection / sensitivity / export
+    def summed_cv_gradient(self) -> np.ndarray:
+        """The CV is the mean half of the heads' output: gradient [1 / post range | 0 for the log-variance half]."""
+        d = self.cv_dimension
+        g = np.zeros(2 * d, dtype=np.float64)
+        g[:d] = 1.0 / np.asarray(self.cv["post"][1], dtype=np.float64) if self.cv.get("post") is not None else 1.0
+        return g
+
+    def to_torch_module(self):
+        st = self.cv
+        L = st["latent"]   # the first decoder Linear; L - 1 = the heads
+        d = self.cv_dimension
+        n_enc = L - 1
+        drops = st.get("drops") or [0.0] * len(st["linears"])
+        bn = st.get("bn") or [None] * len(st["linears"])
+        given = self._fit_list(self.encoder_config.get("dropout", [None] * n_enc), n_enc, "dropout") if n_enc else []
+        enc = export.FeedForward(st["linears"][:n_enc], st["acts"][:n_enc], [None if g is None else float(p) for g, p in zip(given, drops[:n_enc])],
+                                 bn[:n_enc])
+        hw, hb = st["linears"][n_enc]
+        dec_cfg = self.decoder_config if self.decoder_config is not None else self.encoder_config
+        dec = export.FeedForward(st["linears"][L:], st["acts"][L:], self._export_dropout(dec_cfg, drops[L:]), bn[L:])
+        norm = export.Normalization(self.features_norm_mean, self.features_norm_range) if self.feats_norm_mode is not None else None
+        post = export.Normalization(*st["post"]) if st.get("post") is not None else None
+        return export.VariationalAutoEncoderCV(norm, enc, (hw[:d], hb[:d]), (hw[d:], hb[d:]), dec, post)
+
+
 cv_calculators_map = {
     "pca": PCACalculator,
     "ae": AECalculator,
@@ -1448,5 +1689,15 @@ cv_calculators_map = {
     "htica": HTICACalculator,
     "deep_tica": DeepTICACalculator,
 }
+# CVs added after the first five; every lookup by name goes through calculator_class
+more_cv_calculators_map = {
+    "vae": VAECalculator,
+}
+
+
+def calculator_class(name: str):
+    """The calculator class of CV `name` (reference cv_calculators_map, cv_calculator.py:2952-2960), or None when this engine
+    does not implement it (umap)."""
+    return cv_calculators_map.get(name) or more_cv_calculators_map.get(name)
 cv_names_map = {"pca": "PCA", "ae": "AE", "tica": "TICA", "htica": "HTICA", "deep_tica": "DeepTICA", "vae": "VAE", "umap": "UMAP"}
 cv_components_map = {"pca": "PC", "ae": "AE", "tica": "TIC", "htica": "HTIC", "deep_tica": "DeepTIC", "vae": "VAE", "umap": "UMAP"}

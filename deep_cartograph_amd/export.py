@@ -1,7 +1,8 @@
 """TorchScript export / import of the neural CVs with the module tree the reference writes to
 ``model/cv_weights.pt``: ``DeepTICA`` = ``norm_in -> nn -> tica ->
 postprocessing``, ``AutoEncoderCV`` = ``norm_in -> encoder -> postprocessing`` (decoder
-parameters present but unused in ``forward``), ``FeedForward.nn`` a ``Sequential`` of
+parameters present but unused in ``forward``), ``VariationalAutoEncoderCV`` = ``norm_in -> encoder -> mean_nn ->
+postprocessing`` (``log_var_nn`` and the decoder present but unused in ``forward``), ``FeedForward.nn`` a ``Sequential`` of
 Linear / activation / Dropout, parameter names ``nn.nn.{i}.weight`` / ``encoder.nn.{i}.weight``.
 PLUMED's ``PYTORCH_MODEL`` consumes the file directly.  torch is export glue here: the numbers
 inside come from the HIP engine."""
@@ -144,6 +145,43 @@ class AutoEncoderCV(torch.nn.Module):
         return x
 
 
+class ELBOGaussiansLoss(torch.nn.Module):
+    def forward(self, target: torch.Tensor, output: torch.Tensor, mean: torch.Tensor, log_variance: torch.Tensor) -> torch.Tensor:
+        kl = -0.5 * (log_variance - log_variance.exp() - mean ** 2 + 1).sum(dim=1)
+        return (output - target).square().mean() + kl.mean()
+
+
+def _linear(w, b) -> torch.nn.Linear:
+    lin = torch.nn.Linear(w.shape[1], w.shape[0])
+    with torch.no_grad():
+        lin.weight.copy_(torch.as_tensor(np.asarray(w), dtype=torch.float32))
+        lin.bias.copy_(torch.as_tensor(np.asarray(b), dtype=torch.float32))
+    return lin
+
+
+class VariationalAutoEncoderCV(torch.nn.Module):
+    """The CV is the mean head: postprocessing(mean_nn(encoder(norm_in(x)))).  ``mean`` / ``log_var``: (weight, bias) of the
+    two heads."""
+
+    def __init__(self, norm_in, encoder, mean, log_var, decoder, postprocessing):
+        super().__init__()
+        self.loss_fn = ELBOGaussiansLoss()
+        self.norm_in = norm_in
+        self.encoder = encoder
+        self.mean_nn = _linear(*mean)
+        self.log_var_nn = _linear(*log_var)
+        self.decoder = decoder
+        self.postprocessing = postprocessing
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.norm_in is not None:
+            x = self.norm_in(x)
+        x = self.mean_nn(self.encoder(x))
+        if self.postprocessing is not None:
+            x = self.postprocessing(x)
+        return x
+
+
 def save_torchscript(model: torch.nn.Module, n_features: int, path: str) -> None:
     """to_torchscript(method='trace') in eval mode, as NonLinear.save_weights does
     (cv_calculator.py:1773-1795)."""
@@ -179,7 +217,7 @@ def _sequential_layers(seq):
 
 def read_torchscript(path: str) -> dict:
     """Decompose a reference-format cv_weights.pt into arrays the HIP engine can run:
-    kind ('deep_tica' | 'ae'), linears, acts, norm_in (mean, range) or None, tica (mean, evecs)
+    kind ('deep_tica' | 'ae' | 'vae'), linears, acts (VAE: the encoder chain, then mean_nn with no activation), norm_in (mean, range) or None, tica (mean, evecs)
     or None, postprocessing (mean, range) or None."""
     m = torch.jit.load(path, map_location="cpu")
     m.eval()
@@ -196,9 +234,16 @@ def read_torchscript(path: str) -> dict:
         out["kind"] = "deep_tica"
         out["linears"], out["acts"], out["bn"] = _sequential_layers(kids["nn"].nn)
         out["tica"] = (buf["tica.mean"], buf["tica.evecs"])
+    elif "encoder" in kids and "mean_nn" in kids:
+        out["kind"] = "vae"
+        out["linears"], out["acts"], out["bn"] = _sequential_layers(kids["encoder"].nn)
+        mn = kids["mean_nn"]
+        out["linears"].append((mn.weight.detach().cpu().numpy().copy(), mn.bias.detach().cpu().numpy().copy()))
+        out["acts"].append(None)
+        out["bn"].append(None)
     elif "encoder" in kids:
         out["kind"] = "ae"
         out["linears"], out["acts"], out["bn"] = _sequential_layers(kids["encoder"].nn)
     else:
-        raise ValueError("unrecognised TorchScript CV model (expected a DeepTICA or AutoEncoderCV tree)")
+        raise ValueError("unrecognised TorchScript CV model (expected a DeepTICA, AutoEncoderCV or VariationalAutoEncoderCV tree)")
     return out

@@ -347,7 +347,8 @@ class RcclComm:
 
 
 class Mlp:
-    """Owner of a ``dcv_mlp`` handle (Deep-TICA or autoencoder chain of Linear layers).
+    """Owner of a ``dcv_mlp`` handle (Deep-TICA, autoencoder or variational autoencoder chain of Linear layers; for "vae"
+    the Linear at ``latent_layer - 1`` is the two heads [mean | log-variance] concatenated, see dcv.h DCV_MODEL_VAE).
 
     ``dims`` = [F, ..., out]; ``acts`` one activation name per Linear.  Parameters are kept
     in the library's flat device buffer; ``set_linear`` / ``get_linear`` move torch-layout
@@ -372,7 +373,7 @@ class Mlp:
         if len(self.acts) != L:
             raise DcvError("one activation per Linear layer expected")
         desc = _lib.MlpDesc()
-        desc.model = {"deep_tica": _lib.MODEL_DEEPTICA, "ae": _lib.MODEL_AE}[model]
+        desc.model = {"deep_tica": _lib.MODEL_DEEPTICA, "ae": _lib.MODEL_AE, "vae": _lib.MODEL_VAE}[model]
         desc.n_layers = L
         for i, v in enumerate(self.dims):
             desc.dims[i] = v
@@ -413,6 +414,8 @@ class Mlp:
         self.h = h
         self.L = L
         self.latent_layer = desc.latent_layer
+        # input width of each Linear: dims[l], except the VAE's first decoder Linear, which reads z (half the heads' 2d outputs)
+        self.in_dims = [self.dims[l] // 2 if model == "vae" and l == self.latent_layer else self.dims[l] for l in range(L)]
         self.max_batch = int(max_batch)
         self.rows_cap = 2 * self.max_batch if model == "deep_tica" else self.max_batch
         self.n_params = self.lib.dcv_mlp_num_params(self.h)
@@ -425,6 +428,7 @@ class Mlp:
         self._upper_thunk = None   # ctypes thunk of backward(on_upper_grads=...)
         self._upper_fn = None
         self._upper_err = None
+        self._noise = None         # VAE: the device noise buffer the engine reads (kept alive here)
 
     def close(self):
         if getattr(self, "h", None):
@@ -452,8 +456,8 @@ class Mlp:
         for l, (w, b) in enumerate(linears):
             w = np.asarray(w, dtype=np.float32)
             b = np.asarray(b, dtype=np.float32)
-            if w.shape != (self.dims[l + 1], self.dims[l]) or b.shape != (self.dims[l + 1],):
-                raise DcvError(f"layer {l}: expected weight {(self.dims[l + 1], self.dims[l])}, got {w.shape}")
+            if w.shape != (self.dims[l + 1], self.in_dims[l]) or b.shape != (self.dims[l + 1],):
+                raise DcvError(f"layer {l}: expected weight {(self.dims[l + 1], self.in_dims[l])}, got {w.shape}")
             wo, bo = self.offsets[l]
             flat[wo: wo + w.size] = w.ravel()
             flat[bo: bo + b.size] = b
@@ -493,7 +497,7 @@ class Mlp:
         out = []
         for l in range(self.L):
             wo, bo = self.offsets[l]
-            o, i = self.dims[l + 1], self.dims[l]
+            o, i = self.dims[l + 1], self.in_dims[l]
             out.append((flat[wo: wo + o * i].reshape(o, i).copy(), flat[bo: bo + o].copy()))
         return out
 
@@ -547,6 +551,32 @@ class Mlp:
     def set_feature_range(self, rng):
         r = np.ascontiguousarray(np.asarray(rng, dtype=np.float32))
         check(self.lib.dcv_mlp_set_feature_range(self.h, r.ctypes.data, _stream()), "dcv_mlp_set_feature_range")
+
+    # -- variational autoencoder
+    def set_kl_beta(self, beta: float):
+        """Weight of the KL term of the following VAE steps."""
+        check(self.lib.dcv_mlp_set_kl_beta(self.h, float(beta)), "dcv_mlp_set_kl_beta")
+
+    def set_noise(self, eps: torch.Tensor):
+        """The standard-normal noise of the following VAE steps: a [rows, d] float32 device tensor read as a cursor, each
+        training / evaluation step taking the next `batch` rows (rewinds the cursor; the tensor is kept alive here)."""
+        _require_gpu(eps)
+        eps = eps.to(torch.float32).contiguous()
+        d = self.dims[self.latent_layer] // 2
+        if eps.dim() != 2 or eps.shape[1] != d:
+            raise DcvError(f"set_noise: expected a [rows, {d}] tensor, got {tuple(eps.shape)}")
+        self._noise = eps
+        check(self.lib.dcv_mlp_set_noise(self.h, _ptr(eps), int(eps.shape[0])), "dcv_mlp_set_noise")
+
+    def noise_position(self) -> int:
+        """Noise rows consumed since the last set_noise."""
+        return int(self.lib.dcv_mlp_noise_position(self.h))
+
+    def latent_sample(self, rows: int) -> torch.Tensor:
+        """The sampled latent z of the last forward (test hook, layer-by-layer path)."""
+        out = torch.empty(int(rows), self.dims[self.latent_layer] // 2, dtype=torch.float32, device=self.device)
+        check(self.lib.dcv_mlp_latent_sample(self.h, int(rows), _ptr(out), _stream()), "dcv_mlp_latent_sample")
+        return out
 
     # -- steps
     def _args(self, Xn, idx, row0, batch):
@@ -764,7 +794,7 @@ class Mlp:
         _require_gpu(Xn, tmean, tevecs, pmean, prange)
         _check_matrix(Xn)
         n = Xn.shape[0]
-        d = self.dims[self.latent_layer]
+        d = self.dims[self.latent_layer] // (2 if self.model == "vae" else 1)
         out = torch.empty(n, d, dtype=torch.float32, device=Xn.device) if want_out else None
         mm = None
         for s in range(0, n, self.rows_cap):

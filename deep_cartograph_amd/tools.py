@@ -17,7 +17,7 @@ import pandas as pd
 
 from . import statistics
 from .common import merge_configurations, validate_configuration
-from .cv_calculator import CVCalculator, cv_calculators_map
+from .cv_calculator import CVCalculator, calculator_class
 from .schemas import TrainColvarsSchema, TrajClusterSchema, TrajProjectionSchema
 
 logger = logging.getLogger(__name__)
@@ -35,7 +35,7 @@ def train_colvars(configuration: Dict, train_colvars_paths: Union[str, List[str]
                   sup_traj_names: Optional[List[str]] = None, waypoint_structures: Optional[List[str]] = None,
                   reference_topology: Optional[str] = None, features_list: Optional[List[str]] = None,
                   dimension: Optional[int] = None,
-                  cvs: Optional[List[Literal["pca", "ae", "tica", "htica", "deep_tica"]]] = None,
+                  cvs: Optional[List[Literal["pca", "ae", "tica", "htica", "deep_tica", "vae"]]] = None,
                   frames_per_sample: Optional[int] = 1, output_folder: str = "train_colvars") -> Dict[str, List[str]]:
     """Fit every requested CV, project the training frames, write
     <out>/<cv>/model.zip and <out>/<cv>/traj_data/<traj>/projected_trajectory.csv ('%.4f').
@@ -48,10 +48,10 @@ def train_colvars(configuration: Dict, train_colvars_paths: Union[str, List[str]
     if trajectory_names is None:
         trajectory_names = [Path(p).stem for p in train_colvars_paths]
     cvs_list = list(cvs) if cvs else list(configuration["cvs"])
-    unsupported = [c for c in cvs_list if c not in cv_calculators_map]
+    unsupported = [c for c in cvs_list if calculator_class(c) is None]
     for c in unsupported:
-        logger.warning(f"CV '{c}' is outside the accelerated path (vae / umap) and is skipped.")
-    cvs_list = [c for c in cvs_list if c in cv_calculators_map]
+        logger.warning(f"CV '{c}' is outside the accelerated path (umap) and is skipped.")
+    cvs_list = [c for c in cvs_list if calculator_class(c) is not None]
     logger.info(f"Collective variables to compute: {cvs_list}")
     output_paths: Dict[str, List[str]] = {}
     for cv_name in cvs_list:
@@ -63,7 +63,7 @@ def train_colvars(configuration: Dict, train_colvars_paths: Union[str, List[str]
             output_paths[cv_name] = expected
             continue
         merged = merge_configurations(configuration["common"], configuration.get(cv_name, {}))
-        calc = cv_calculators_map[cv_name](configuration=merged, output_path=output_folder)
+        calc = calculator_class(cv_name)(configuration=merged, output_path=output_folder)
         calc.load_training_data(train_colvars_paths, train_topologies, reference_topology, features_list)
         if val_colvars_paths:
             calc.load_validation_data(val_colvars_paths, val_topologies, reference_topology, features_list)

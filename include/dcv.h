@@ -1,6 +1,6 @@
 /*
  * dcv.h -- C-ABI of libdcv.so, the MI355X (gfx950) engine behind deep_cartograph's CV-fit
- * hot path (train_colvars: pca / tica / htica / ae / deep_tica, projection, k-means).
+ * hot path (train_colvars: pca / tica / htica / ae / deep_tica / vae, projection, k-means).
  *
  * The reference has no FFI for this path: the seam is the Python class set in
  * deep_cartograph/modules/cv_learning/cv_calculator.py and the functions of
@@ -146,6 +146,16 @@ int dcv_project_linear(const float* X_d, int64_t n, int32_t F, int64_t ld,
 
 #define DCV_MODEL_DEEPTICA 1 /* loss = -sum(eig^2) of the batch TICA of nn(x_t), nn(x_lag) */
 #define DCV_MODEL_AE 2       /* loss = mean(((dec(enc(xn)) - xn) * range)^2) */
+/* Variational autoencoder (mlcolvar VariationalAutoEncoderCV, reference cv_calculator.py:2629-2780), in the same descriptor:
+ * Linear latent_layer - 1 is the two heads concatenated (mean_nn rows, then log_var_nn rows: dims[latent_layer] = 2d
+ * columns, no activation / dropout / batch normalisation); Linear latent_layer reads z = mu + exp(lv / 2) * eps (d columns).
+ *   loss = reconstruction + beta * kl,  reconstruction = the AE's loss,  kl = mean over the batch of
+ *          -0.5 * sum_j (lv - exp(lv) - mu^2 + 1)
+ * eps comes from the caller (dcv_mlp_set_noise), beta from dcv_mlp_set_kl_beta.  Log records are
+ * [loss | batch | reconstruction | kl], dcv_mlp_stats() holds [SSE | KL sum].  d <= 8.  Not data-parallel: dcv_mlp_dp_step
+ * refuses global_batch != batch (DCV_EINVAL).  Networks that fit in LDS take the fused one-launch step (dcv_mlp_last_path 1, the
+ * validation pass of dcv_mlp_eval_steps many batches per launch, each with its own eps rows), the others the layer-by-layer path. */
+#define DCV_MODEL_VAE 3
 
 typedef struct dcv_mlp_desc {
     int32_t model;                      /* DCV_MODEL_* */
@@ -207,8 +217,18 @@ int dcv_mlp_set_momentum(dcv_mlp* m, double value);
  * roles).  enable = 0 evaluates the two halves separately (2 * batch rows), as gathered batches always
  * are -- used by the parity tests to check that both forms agree. */
 int dcv_mlp_set_row_sharing(dcv_mlp* m, int32_t enable);
-/* AE only: per-feature range of norm_in (device copy is made); needed by the loss. */
+/* AE / VAE: per-feature range of norm_in (device copy is made); needed by the loss. */
 int dcv_mlp_set_feature_range(dcv_mlp* m, const float* range_h, void* stream);
+/* VAE only: weight beta of the KL term in the following steps (the reference's KL annealing sets it per epoch). */
+int dcv_mlp_set_kl_beta(dcv_mlp* m, double beta);
+/* VAE only: the standard-normal noise of the following steps, a cursor over the caller's device buffer eps_d
+ * (rows x d float32, row-major, not copied: it must stay valid while steps run).  Every VAE training or evaluation step
+ * (dcv_mlp_forward, *_step, *_steps) takes the next `batch` rows, in call order; a step that would read past row `rows`
+ * returns DCV_ESTATE before anything is launched.  The call rewinds the cursor; dcv_mlp_noise_position returns it. */
+int dcv_mlp_set_noise(dcv_mlp* m, const float* eps_d, int64_t rows);
+int64_t dcv_mlp_noise_position(const dcv_mlp* m);
+/* VAE test hook: the sampled latent z of the last forward (rows x d floats, dense, device). */
+int dcv_mlp_latent_sample(dcv_mlp* m, int64_t rows, float* out_d, void* stream);
 
 /* One optimisation / evaluation step, split in phases so that a data-parallel caller can
  * all-reduce between them.  Samples of the batch: idx_d != NULL => sample j uses row
@@ -359,7 +379,7 @@ int dcv_mlp_profile_pause(dcv_mlp* m, int32_t paused);
 int64_t dcv_mlp_graph_launches(const dcv_mlp* m);
 int dcv_mlp_set_graph(dcv_mlp* m, int32_t enable);   /* per-engine switch (default: DCV_GRAPH=1 in the environment) */
 
-/* Whole-matrix inference (project / normalize_cv): y = layers[0..latent_layer)(xn);
+/* Whole-matrix inference (project / normalize_cv): y = layers[0..latent_layer)(xn) (VAE: the first d = mean columns);
  * Deep-TICA additionally y = (y - tmean) @ tevecs (both d floats / d*d row-major, device,
  * may be NULL); then out = (y - pmean)/prange when given.  minmax_d as in
  * dcv_project_linear.  out_d (n x d) may be NULL. */
@@ -372,7 +392,7 @@ int dcv_mlp_infer(dcv_mlp* m, const float* Xn_d, int64_t n, int64_t ld,
  * NonLinear.sensitivity_analysis, cv_calculator.py:1893-1921: for the n rows given (n <= the
  * engine's row capacity; chunk larger matrices and add the results)
  *   sens[i] = sum_r | d(sum_j cv_j)/d xn[r][i] | * scale[i]          (float64, F values, overwritten)
- * gout_d (d_latent floats) is the constant gradient of sum_j cv_j with respect to the output of
+ * gout_d (dims[latent_layer] floats; VAE: 2d, the log-variance half zero) is the constant gradient of sum_j cv_j with respect to the output of
  * the network layers (the TICA projection and the post-normalisation behind them are affine);
  * scale_d (F floats) is the per-feature factor (dataset std / norm_in range). */
 size_t dcv_mlp_input_sensitivity_workspace(const dcv_mlp* m, int64_t n);
