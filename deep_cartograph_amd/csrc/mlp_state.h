@@ -129,6 +129,7 @@ int snet_ae_step(dcv_mlp* m, const float* Xn_d, int64_t ld, const RowMap& rm, in
                  hipStream_t s, bool write_log = true, int nb = 1);   // nb > 1: that many evaluation batches of R rows in one launch
 int snet_ae_tile_rows(dcv_mlp* m, int64_t R = 0);   // rows per workgroup of the fused kernel for batches of R rows (builds the plan on first use); 0: not applicable
 void snet_free(dcv_mlp* m);
+int snet_ae_last_tile_rows(const dcv_mlp* m);   // rows per workgroup of the last fused autoencoder launch (0: none yet)
 // the weight image both fused small-network plans stage from (snet.hip); repack: after the parameters were written by anyone
 // but the optimiser (dcv_mlp_set_params)
 bool snet_image_build(dcv_mlp* m);
@@ -140,6 +141,7 @@ int snet_dt_forward(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t* id
                     hipStream_t s, int nb = 1);
 int snet_dt_backward(dcv_mlp* m, int32_t batch, int64_t global_batch, bool head, ReduceArgsView* ra, hipStream_t s);
 void snet_dt_free(dcv_mlp* m);
+int snet_dt_last_tile_rows(const dcv_mlp* m);   // rows per workgroup of the last fused Deep-TICA forward (0: none yet)
 // bn.hip
 int bn_forward(dcv_mlp* m, int l, int64_t row0, int64_t rows, bool train, hipStream_t s);
 int bn_backward(dcv_mlp* m, int l, float* dz, int64_t ld_dz, int halves, int64_t rows_half, int act, float hscale, const DropCfg& drop,

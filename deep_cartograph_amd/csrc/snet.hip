@@ -464,6 +464,7 @@ struct SnetPlan {
     unsigned* ev_ticket; // ... and one ticket per batch + the one that moves the log counter (zero between launches)
     int64_t ev_ticket_n;
     double* kl_part;     // VAE: KL partials [workgroups of the launch] (kEvalWorkgroupsPerLaunch), or null
+    int last_tr;         // tile rows of the last launch (dcv_debug_snet_tile_rows)
 };
 
 // Activation map of a TR-row tile behind the weight images (H_0 .. H_L, the reduction scratch); returns the LDS bytes, 0 when
@@ -557,6 +558,7 @@ static bool snet_build(dcv_mlp* m) {
         pl->ev_sse_n = 0;
         pl->ev_ticket = nullptr;
         pl->ev_ticket_n = 0;
+        pl->last_tr = 0;
         // batched validation passes: partials and tickets for the bounds of dcv_mlp_eval_steps (33 KB); without them the
         // passes go batch by batch
         if (hipMalloc(reinterpret_cast<void**>(&pl->ev_sse), (size_t)kEvalWorkgroupsPerLaunch * sizeof(double)) == hipSuccess &&
@@ -652,6 +654,11 @@ void snet_free(dcv_mlp* m) {
     m->snet = nullptr;
 }
 
+int snet_ae_last_tile_rows(const dcv_mlp* m) {
+    const SnetPlan* pl = static_cast<const SnetPlan*>(m->snet);
+    return pl ? pl->last_tr : 0;
+}
+
 // Rows per workgroup the fused autoencoder kernel takes for batches of R rows (R = 0: its largest tile); the plan is built on
 // first use; 0: the fused form does not apply.
 int snet_ae_tile_rows(dcv_mlp* m, int64_t R) {
@@ -737,6 +744,7 @@ int snet_ae_step(dcv_mlp* m, const float* Xn_d, int64_t ld, const RowMap& rm, in
     a.beta_b = (float)(m->kl_beta / (double)batch);
     a.kl_part = pl->kl_part;
     a.stamps = pl->stamps;
+    pl->last_tr = TR;
     auto launch = [&](auto kern) -> int {
         static int attr_state[4] = {0, 0, 0, 0};   // 0 unknown, 1 set, -1 refused by the runtime (the fused form is then off)
         const int slot = (TR == 32 ? 0 : 1) + (a.vae_l >= 0 ? 2 : 0);
@@ -780,4 +788,14 @@ extern "C" int dcv_debug_snet_stamps(dcv_mlp* m, unsigned long long* out_h) {
     DCV_CHECK_HIP(hipDeviceSynchronize());
     DCV_CHECK_HIP(hipMemcpy(out_h, pl->stamps, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return DCV_OK;
+}
+
+// diagnostic (tests; not part of include/dcv.h): rows per workgroup of the last fused small-network launch (16 / 32 / 64 / 128),
+// 0 when the last step or forward ran layer by layer
+extern "C" int dcv_debug_snet_tile_rows(const dcv_mlp* m) {
+    using namespace dcv;
+    if (!m) return DCV_EINVAL;
+    if (m->last_path == 1) return snet_ae_last_tile_rows(m);
+    if (m->last_path == 2) return snet_dt_last_tile_rows(m);
+    return 0;
 }

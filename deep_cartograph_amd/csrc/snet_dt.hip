@@ -357,9 +357,7 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_bwd_kernel(SnetDtArgs a)
     // critical path (its last arriver, the whole chip waiting) now runs while this wave's staging loads are in flight and
     // the other waves stage theirs.  Every workgroup computes the same matrices (deterministic: same inputs, same code);
     // the first one appends the loss record.
-    bool head_ran = false;
     auto run_head = [&]() {
-        head_ran = true;
         if (!a.fused.on) return;
         if (wave == kSnetWaves - 1) {
             if (lane < NG) s_stat[lane] = a.stats[lane];
@@ -408,7 +406,6 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_bwd_kernel(SnetDtArgs a)
                     }
                 }
             }
-            if (!head_ran) run_head();   // this wave's table, blob and data loads are in flight
             int2 en[12];
     #pragma unroll
             for (int u = 0; u < 12; ++u) {
@@ -423,7 +420,10 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_bwd_kernel(SnetDtArgs a)
         }
     }
     if (!blob_issued) issue_blob();
-    if (!head_ran) run_head();
+    // After the staging loop on both paths: the head is wave-wide (its lanes share data through LDS) and must run with the
+    // whole wave.  Inside the table loop only the lanes with an entry left take the last pass, so a staging table of
+    // 449..511 entries in the backward ran it twice under partial exec masks, each time with part of the statistics.
+    run_head();
     if (a.img != nullptr) vm_wait<0>();   // (the blob loads above are covered too)
     if (!a.fused.on && t < NG) s_g[t] = a.gradp[t];
 #pragma unroll
@@ -703,6 +703,11 @@ void snet_dt_free(dcv_mlp* m) {
     if (pl->stage_tab) (void)hipFree(pl->stage_tab);
     delete pl;
     m->snet_dt = nullptr;
+}
+
+int snet_dt_last_tile_rows(const dcv_mlp* m) {
+    const SnetDtPlan* pl = static_cast<const SnetDtPlan*>(m->snet_dt);
+    return pl ? pl->last_tr : 0;
 }
 
 template <class K>

@@ -687,41 +687,62 @@ def test_native_rccl_communicator_world1():
 
 
 _SWITCH_SCRIPT = r"""
-import hashlib, sys
+import ctypes, hashlib, sys
 import numpy as np, torch
 sys.path.insert(0, {root!r})
-from deep_cartograph_amd import hip
+from deep_cartograph_amd import _lib, hip
+tile_rows = _lib.load().dcv_debug_snet_tile_rows
+tile_rows.restype, tile_rows.argtypes = ctypes.c_int, [ctypes.c_void_p]
 rng = np.random.Generator(np.random.PCG64(5))
 model = sys.argv[1]
+F, n, batches, path = 96, 12000, [1999, 2048] * 4, 2 if model.startswith("deep_tica") else 1
 if model == "deep_tica":
     dims, acts = [96, 64, 32, 3], ["leaky_relu", "tanh", None]
     eng = hip.Mlp("deep_tica", dims, acts, max_batch=2048, lag=7, tica_reg=1e-6, lr=1e-3)
+elif model == "deep_tica_d4":   # d = 4, its backward stages 464 table entries; 16- to 128-row tiles
+    F, n, batches = 54, 20000, [1000, 4000, 6000, 8193, 12000, 1000, 6000, 12000]
+    dims, acts = [54, 32, 32, 16, 4], ["tanh", "tanh", "tanh", None]
+    eng = hip.Mlp("deep_tica", dims, acts, max_batch=12000, lag=7, tica_reg=1e-6, lr=1e-3)
+elif model == "vae":
+    dims, acts = [96, 48, 16, 4, 16, 48, 96], ["leaky_relu", "leaky_relu", None, "leaky_relu", "leaky_relu", None]
+    batches = [1999, 4096] * 4
+    eng = hip.Mlp("vae", dims, acts, max_batch=4096, latent_layer=3, lr=1e-3)
+    eng.set_feature_range(np.ones(96, np.float32))
+    eng.set_kl_beta(0.5)
+    eng.set_noise(torch.from_numpy(rng.standard_normal((sum(batches), 2)).astype(np.float32)).cuda())
 else:
     dims, acts = [96, 48, 16, 2, 16, 48, 96], ["leaky_relu", "leaky_relu", None, "leaky_relu", "leaky_relu", None]
     eng = hip.Mlp("ae", dims, acts, max_batch=2048, latent_layer=3, lr=1e-3)
     eng.set_feature_range(np.ones(96, np.float32))
 torch.manual_seed(3)
 lins = [torch.nn.Linear(dims[i], dims[i + 1]) for i in range(len(dims) - 1)]
+if model == "vae":   # the decoder's first Linear reads z: half the heads' outputs
+    lins[3] = torch.nn.Linear(2, dims[4])
 eng.set_linears([(l.weight.detach().numpy(), l.bias.detach().numpy()) for l in lins])
-X = torch.from_numpy(rng.standard_normal((12000, 96)).astype(np.float32).cumsum(0) * 0.02 + rng.standard_normal((12000, 96)).astype(np.float32)).cuda()
+X = torch.from_numpy(rng.standard_normal((n, F)).astype(np.float32).cumsum(0) * 0.02 + rng.standard_normal((n, F)).astype(np.float32)).cuda()
 eng.reset_log(64)
-for i in range(8):
-    eng.train_step(X, row0=i * 1000, batch=2048 if i % 2 else 1999)
+trs = []
+for i, b in enumerate(batches):
+    eng.train_step(X, row0=i * 1000 if b + 8 <= n - i * 1000 else n - b - 8, batch=b)
+    assert eng.last_path() == path, (model, b, eng.last_path())
+    trs.append(tile_rows(eng.h))
 torch.cuda.synchronize()
 h = hashlib.sha256()
 for w, b in eng.get_linears():
     h.update(np.ascontiguousarray(w).tobytes()); h.update(np.ascontiguousarray(b).tobytes())
-h.update(np.ascontiguousarray(eng.read_log()[:8, 0]).tobytes())
+h.update(np.ascontiguousarray(eng.read_log()[:8]).tobytes())
+print("TILES", trs)
 print("HASH", h.hexdigest())
 """
 
 
-@pytest.mark.parametrize("model", ["deep_tica", "ae"])
+@pytest.mark.parametrize("model", ["deep_tica", "ae", "deep_tica_d4", "vae"])
 def test_launch_time_switches_leave_the_bits_alone(model, tmp_path):
     """The speed switches of the library change how results are stored or summed up in the SAME order, never the results:
     write-through epilogue stores (DCV_WT), the flat-grid gradient reduction (DCV_REDUCE_QUAD), the grouped weight /
-    input gradient launch (DCV_NO_PAIR).  Eight training steps in fresh processes (the switches are read once per
-    process), parameters and losses hashed."""
+    input gradient launch (DCV_NO_PAIR), the table-driven weight staging of the fused small-network kernels in place of the
+    weight image (DCV_SNET_IMG=0).  Eight training steps in fresh processes (the switches are read once per process), every
+    one on the fused kernels; parameters and loss records hashed."""
     import os
     import subprocess
     import sys
@@ -729,15 +750,18 @@ def test_launch_time_switches_leave_the_bits_alone(model, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = tmp_path / "switch_run.py"
     script.write_text(_SWITCH_SCRIPT.format(root=root))
-    hashes = {}
+    hashes, tiles = {}, {}
     for name, env in (("default", {}), ("plain stores", {"DCV_WT": "0"}), ("round-2 reduction", {"DCV_REDUCE_QUAD": "0"}),
-                      ("two launches", {"DCV_NO_PAIR": "1"})):
+                      ("two launches", {"DCV_NO_PAIR": "1"}), ("table staging", {"DCV_SNET_IMG": "0"})):
         e = dict(os.environ)
         e.update(env)
         out = subprocess.run([sys.executable, str(script), model], env=e, capture_output=True, text=True, timeout=300)
         assert out.returncode == 0, out.stderr[-2000:]
         hashes[name] = [l for l in out.stdout.splitlines() if l.startswith("HASH")][-1]
+        tiles[name] = [l for l in out.stdout.splitlines() if l.startswith("TILES")][-1]
     assert len(set(hashes.values())) == 1, hashes
+    expect = {"deep_tica": [32] * 8, "ae": [16] * 8, "vae": [16, 32] * 4, "deep_tica_d4": [16, 32, 64, 128, 128, 16, 64, 128]}[model]
+    assert set(tiles.values()) == {f"TILES {expect}"}, tiles
 
 
 def _fuzz_seeds():

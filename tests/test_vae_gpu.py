@@ -108,9 +108,13 @@ def test_vae_steps_match_float64_restatement(dims, acts, latent, n, batch, beta,
     eps = [torch.randn(len(b), d, generator=g) for b in steps]
     eng.set_noise(torch.cat(eps).cuda())
     eng.reset_log(len(steps))
+    from tests.test_snet_dt_gpu import tile_rows
+
     for b, e in zip(steps, eps):
         eng.train_step(Xd, idx=b.cuda())
         assert eng.last_path() == path
+        # snet_ae_kernel<16, true> up to 2048 rows, <32, true> beyond (the 4096-row case runs both)
+        assert tile_rows(eng) == (0 if path == 0 else (16 if len(b) <= 2048 else 32))
         got_ref.append(ref.step(Xt[b], e.double(), beta))
     assert eng.noise_position() == sum(len(b) for b in steps)
     rec, exp = eng.read_log(), np.array(got_ref)
