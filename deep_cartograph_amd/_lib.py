@@ -65,6 +65,10 @@ SIGNATURES = {
     "dcv_device_info": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(_I64), C.c_char_p, _SZ]),
     "dcv_col_stats_workspace": (_SZ, [_I64, _I32]),
     "dcv_col_stats": (C.c_int, [_P, _I64, _I32, _I64, _P, _P, _SZ, _P]),
+    "dcv_col_histogram_workspace": (_SZ, [_I64, _I32, _I32]),
+    "dcv_col_histogram": (C.c_int, [_P, _I64, _I32, _I64, _P, _I32, _P, _P, _SZ, _P]),
+    "dcv_dip_sorted_workspace": (_SZ, [_I64, _I32]),
+    "dcv_dip_sorted": (C.c_int, [_P, _I64, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
     "dcv_normalize": (C.c_int, [_P, _P, _I64, _I32, _I64, _I64, _P, _P, _P]),
     "dcv_lagged_cov_workspace": (_SZ, [_I64, _I32, _I32]),
     "dcv_lagged_cov": (C.c_int, [_P, _I64, _I32, _I64, _I32, _P, _P, _P, _SZ, _P]),

@@ -105,6 +105,13 @@ def read_features_list(features_path: Optional[str]) -> Optional[List[str]]:
         return [line.strip() for line in f if line.strip()]
 
 
+def save_list(items: List[str], path: str) -> None:
+    """One item per line (the format read_features_list reads)."""
+    with open(path, "w") as f:
+        for item in items:
+            f.write(f"{item}\n")
+
+
 def get_unique_path(path: str) -> str:
     """path, or path_1, path_2 ... if it already exists."""
     if not os.path.exists(path):

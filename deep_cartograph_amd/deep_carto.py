@@ -1,10 +1,11 @@
 """`deep_carto`-style entry point for the accelerated part of the workflow:
-train_colvars -> (traj_projection of supplementary data) -> traj_cluster, starting from
-pre-computed feature matrices (PLUMED COLVAR text or the binary .npy fast path).  The
-reference's steps 0-3 (geometry analysis, augmentation, PLUMED featurisation, feature filtering;
-deep_carto.py:191-305) need MDAnalysis and the plumed binary and are out of scope, so the YAML
-keeps the reference's `train_colvars` / `traj_cluster` sections and the CLI takes colvars
-files where the reference takes trajectories.
+(filter_features) -> train_colvars -> (traj_projection of supplementary data) -> traj_cluster,
+starting from pre-computed feature matrices (PLUMED COLVAR text or the binary .npy fast path).
+The reference's steps 0-2 (geometry analysis, augmentation, PLUMED featurisation;
+deep_carto.py:191-290) need MDAnalysis and the plumed binary and are out of scope, so the YAML
+keeps the reference's `filter_features` / `train_colvars` / `traj_cluster` sections and the CLI
+takes colvars files where the reference takes trajectories.  Feature filtering needs only the
+colvars files: it runs when the YAML has a `filter_features` section and no -features file is given.
 
     python -m deep_cartograph_amd.deep_carto -conf config.yml -colvars a.dat b.dat -out run1 \
            [-dim 2] [-cvs pca tica deep_tica] [-sup_colvars c.dat] [-features feats.txt] [-restart]
@@ -19,7 +20,7 @@ import time
 from typing import Dict, List, Optional
 
 from .common import get_unique_path, read_configuration, read_features_list
-from .tools import traj_cluster, traj_projection, train_colvars
+from .tools import filter_features, traj_cluster, traj_projection, train_colvars
 
 logger = logging.getLogger("deep_cartograph")
 
@@ -27,13 +28,18 @@ logger = logging.getLogger("deep_cartograph")
 def deep_cartograph(configuration: Dict, colvars_paths: List[str], sup_colvars_paths: Optional[List[str]] = None,
                     features_list: Optional[List[str]] = None, dimension: Optional[int] = None, cvs: Optional[List[str]] = None,
                     restart: bool = False, output_folder: Optional[str] = None) -> Dict[str, Dict]:
-    """train_colvars -> traj_projection (supplementary colvars) -> traj_cluster per CV
-    (reference deep_carto.py:307-361).  `restart` reuses the output folder and skips what exists."""
+    """(filter_features) -> train_colvars -> traj_projection (supplementary colvars) -> traj_cluster per CV
+    (reference deep_carto.py:292-361).  A `filter_features` section in the configuration selects the features
+    first unless `features_list` is given.  `restart` reuses the output folder and skips what exists."""
     t0 = time.time()
     output_folder = output_folder or "deep_cartograph"
     if not restart:
         output_folder = get_unique_path(output_folder)
     os.makedirs(output_folder, exist_ok=True)
+    if "filter_features" in configuration and not features_list:
+        features_path = filter_features(configuration=configuration["filter_features"] or {}, colvars_paths=colvars_paths,
+                                        output_folder=os.path.join(output_folder, "filter_features"))
+        features_list = read_features_list(features_path)
     tc_out = os.path.join(output_folder, "train_colvars")
     cv_paths = train_colvars(configuration=configuration.get("train_colvars", {}), train_colvars_paths=colvars_paths,
                              features_list=features_list, dimension=dimension, cvs=cvs, output_folder=tc_out)

@@ -62,6 +62,48 @@ def finalize_stats(raw: torch.Tensor, n: int) -> dict:
             "min": r[2].astype(np.float32), "max": r[3].astype(np.float32)}
 
 
+def col_histogram(X: torch.Tensor, edges: torch.Tensor) -> torch.Tensor:
+    """[F, bins] int64 counts of every column of X over its own bin edges ([F, bins + 1] float32), with
+    np.histogram's semantics (dcv_col_histogram)."""
+    _require_gpu(X, edges)
+    _check_matrix(X)
+    n, F = X.shape
+    if edges.dim() != 2 or edges.shape[0] != F or edges.shape[1] < 2 or edges.dtype != torch.float32 or not edges.is_contiguous():
+        raise DcvError(f"col_histogram: edges must be a contiguous float32 [F, bins + 1] tensor, got {tuple(edges.shape)} {edges.dtype}")
+    lib = _lib.load()
+    bins = edges.shape[1] - 1
+    counts = torch.empty(F, bins, dtype=torch.int64, device=X.device)
+    ws = _ws(lib.dcv_col_histogram_workspace(n, F, bins), X.device)
+    check(lib.dcv_col_histogram(_ptr(X), n, F, X.stride(0), _ptr(edges), bins, _ptr(counts), _ptr(ws), ws.numel(), _stream()),
+          "dcv_col_histogram")
+    return counts
+
+
+def dip_sorted_workspace_bytes(n: int, C: int) -> int:
+    return int(_lib.load().dcv_dip_sorted_workspace(n, C))
+
+
+def dip_sorted(Xs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dip [C] float64, lo [C] int32, hi [C] int32) of an n x C float32 matrix whose columns are each sorted
+    ascending, e.g. torch.sort(X, dim=0).values (dcv_dip_sorted)."""
+    _require_gpu(Xs)
+    _check_matrix(Xs)
+    n, C = Xs.shape
+    if n == 0 or C == 0:
+        raise DcvError("dip_sorted: empty matrix")
+    # sorted columns: a NaN or an infinity can only sit in the first or the last row
+    if not bool(torch.isfinite(Xs[0]).all() & torch.isfinite(Xs[-1]).all()):
+        raise DcvError("dip_sorted: the matrix holds NaN or infinite values")
+    lib = _lib.load()
+    dip = torch.empty(C, dtype=torch.float64, device=Xs.device)
+    lo = torch.empty(C, dtype=torch.int32, device=Xs.device)
+    hi = torch.empty(C, dtype=torch.int32, device=Xs.device)
+    ws = _ws(lib.dcv_dip_sorted_workspace(n, C), Xs.device)
+    check(lib.dcv_dip_sorted(_ptr(Xs), n, C, Xs.stride(0), _ptr(dip), _ptr(lo), _ptr(hi), _ptr(ws), ws.numel(), _stream()),
+          "dcv_dip_sorted")
+    return dip, lo, hi
+
+
 def normalize(X: torch.Tensor, mean: torch.Tensor, rng: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(x - mean) / range in float32; ``out`` may be X itself (in place)."""
     _require_gpu(X, mean, rng, out)

@@ -1,6 +1,6 @@
 """Configuration contract of the CV-fit path: pydantic models with the field names, defaults
-and `extra` policy of the reference's deep_cartograph/yaml_schemas/{train_colvars,traj_cluster,
-traj_projection}.py.  tests/test_host_cpu.py checks model_dump() of the defaults against the
+and `extra` policy of the reference's deep_cartograph/yaml_schemas/{filter_features,train_colvars,
+traj_cluster,traj_projection}.py.  tests/test_host_cpu.py checks model_dump() of the defaults against the
 reference's own dump (tests/golden/schema_defaults.json)."""
 from __future__ import annotations
 
@@ -179,3 +179,26 @@ class TrajClusterSchema(BaseModel):
 
 class TrajProjectionSchema(BaseModel):
     figures: Figures = Figures()
+
+
+class FilterSettings(BaseModel):
+    # distance threshold to distinguish local contacts, in Angstroms (None skips the filter)
+    local_distance_threshold: Optional[float] = None
+    # significance level of Hartigan's dip test (None skips the filter)
+    diptest_significance_level: Optional[float] = 0.05
+    # entropy quantile below which features are dropped (None skips the filter)
+    entropy_quantile: Optional[float] = None
+    # standard deviation quantile below which features are dropped (None skips the filter)
+    std_quantile: Optional[float] = None
+
+
+class SamplingSettings(BaseModel):
+    # accepted and unused, as in the reference's Filter
+    num_samples: Union[int, None] = None
+    total_num_samples: Union[int, None] = None
+    relaxation_time: int = 1
+
+
+class FilterFeaturesSchema(BaseModel):
+    filter_settings: FilterSettings = FilterSettings()
+    sampling_settings: SamplingSettings = SamplingSettings()

@@ -1,5 +1,5 @@
-"""The three tools of the CV-fit path with the reference's API (argument names, output tree,
-CSV formats): train_colvars (tools/train_colvars/train_colvars.py:20-36), traj_projection
+"""The tools of the CV-fit path with the reference's API (argument names, output tree,
+CSV formats): filter_features (tools/filter_features/filter_features.py:22-31), train_colvars (tools/train_colvars/train_colvars.py:20-36), traj_projection
 (tools/traj_projection/traj_projection.py:19-27), traj_cluster (tools/traj_cluster/traj_cluster.py:
 18-28).  Figures, FES estimation and PDB/XTC extraction (matplotlib / MDAnalysis) are outside the
 accelerated path and are not produced."""
@@ -16,9 +16,9 @@ import numpy as np
 import pandas as pd
 
 from . import statistics
-from .common import merge_configurations, validate_configuration
+from .common import merge_configurations, save_list, validate_configuration
 from .cv_calculator import CVCalculator, calculator_class
-from .schemas import TrainColvarsSchema, TrajClusterSchema, TrajProjectionSchema
+from .schemas import FilterFeaturesSchema, TrainColvarsSchema, TrajClusterSchema, TrajProjectionSchema
 
 logger = logging.getLogger(__name__)
 
@@ -27,6 +27,42 @@ def _as_list(x):
     if x is None:
         return None
     return [x] if isinstance(x, str) else list(x)
+
+
+def filter_features(configuration: Dict, colvars_paths: Union[str, List[str]], waypoint_colvars_paths: Optional[List[str]] = None,
+                    csv_summary: bool = True, topologies: Optional[List[str]] = None, waypoint_topologies: Optional[List[str]] = None,
+                    reference_topology: Optional[str] = None, output_folder: str = "filter_features") -> str:
+    """Select the features that carry information about the transitions: Hartigan's dip test, Shannon entropy and
+    standard deviation filters over the time series, waypoint filters over a few structures.  Writes
+    <out>/all_features.txt, <out>/filter_summary.csv (csv_summary) and <out>/filtered_features.txt and returns the
+    path of the latter -- the `features_list` file train_colvars and the CLI's -features accept.  Returns early when
+    that file exists."""
+    from .features import Filter
+
+    t0 = time.time()
+    output_features_path = os.path.join(output_folder, "filtered_features.txt")
+    if os.path.exists(output_features_path):
+        logger.info(f"Filtered features file already exists: {output_features_path}. Skipping filtering.")
+        return output_features_path
+    os.makedirs(output_folder, exist_ok=True)
+    configuration = validate_configuration(configuration or {}, FilterFeaturesSchema, output_folder)
+    colvars_paths = _as_list(colvars_paths)
+    for path in colvars_paths:
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"Colvars file not found: {path}")
+    if topologies:
+        if reference_topology is None:
+            reference_topology = topologies[0]
+        elif not os.path.exists(reference_topology):
+            logger.error(f"Reference topology file missing: {reference_topology}")
+            sys.exit(1)
+    filtered_features = Filter(settings=configuration["filter_settings"], colvars_paths=colvars_paths,
+                               waypoint_colvars_paths=waypoint_colvars_paths, topologies=topologies,
+                               waypoint_topologies=waypoint_topologies, reference_topology=reference_topology,
+                               output_dir=output_folder).run(csv_summary)
+    save_list(filtered_features, output_features_path)
+    logger.info("Elapsed time (Filter features): %s", time.strftime("%H h %M min %S s", time.gmtime(time.time() - t0)))
+    return output_features_path
 
 
 def train_colvars(configuration: Dict, train_colvars_paths: Union[str, List[str]], train_topologies: Optional[List[str]] = None,

@@ -68,6 +68,28 @@ size_t dcv_col_stats_workspace(int64_t n, int32_t F);
 int dcv_col_stats(const float* X_d, int64_t n, int32_t F, int64_t ld, double* out_d,
                   void* ws_d, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- column histograms (filter_features)
+ * Replaces np.histogram(column, bins) per feature in shannon_entropy, statistics.py:556-564.  One pass
+ * over X (n x F float32).  `edges_d` holds F rows of bins + 1 float32 bin edges (built on the host as
+ * np.histogram builds them from the column's min and max); `counts_d` receives F * bins int64 counts that
+ * are EQUAL to np.histogram's: every bin is [edge_i, edge_i+1), the last one is closed on the right.
+ * 1 <= bins <= 126.  Algorithmic traffic: 4*n*F bytes read, 8*F*bins written.  The workspace is empty
+ * (the query exists for symmetry and returns 0); `ws_d` may be NULL. */
+size_t dcv_col_histogram_workspace(int64_t n, int32_t F, int32_t bins);
+int dcv_col_histogram(const float* X_d, int64_t n, int32_t F, int64_t ld, const float* edges_d, int32_t bins,
+                      int64_t* counts_d, void* ws_d, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- dip statistic (filter_features)
+ * Replaces the statistic of diptest.diptest(column) in dip_test, statistics.py:621-632.  `Xs_d` is n x C
+ * float32 with EVERY COLUMN SORTED ascending (no NaN).  `dip_d` receives C float64 dip statistics
+ * (Hartigan & Hartigan 1985 / AS 217 in float64, at least 1/(2n); 0 for a constant column or n < 2),
+ * `lo_d` / `hi_d` the 0-based ends of the modal interval.  n < 2^31 - 1.  The workspace holds four int32
+ * arrays of (n + 1) * C.  Algorithmic traffic: two hull scans and the interval search, about
+ * 4*n*C bytes read of Xs and 8*n*C bytes of hull links written per scan; latency-bound. */
+size_t dcv_dip_sorted_workspace(int64_t n, int32_t C);
+int dcv_dip_sorted(const float* Xs_d, int64_t n, int32_t C, int64_t ld, double* dip_d, int32_t* lo_d,
+                   int32_t* hi_d, void* ws_d, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- normalisation (a3)
  * Replaces LinearCalculator.normalize_data, cv_calculator.py:833-835
  * (data.sub_(mean).div_(range) in float32).  Y may alias X (in place, as the reference). */
