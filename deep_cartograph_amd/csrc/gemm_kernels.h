@@ -133,6 +133,8 @@ struct EpiBiasAct {  // H = dropout(act(acc + bias[col]))
     __device__ __forceinline__ void one(int, int64_t r, int64_t c, float v) const {
         C[r * ldc + c] = act_fwd(act, v + (bias ? bias[c] : 0.f));
     }
+    // member of a grouped launch (gemm_group_kernel): the outputs move down by `rows` rows (evaluation: no sign mask)
+    __device__ __forceinline__ void shift_rows(int64_t rows) { C += rows * ldc; }
 };
 // Butterfly reduce-scatter of CUR values over the C4 consecutive lanes that share the rows of a thread
 // group: while the count is even each step halves it (a lane keeps the half selected by its lane bit and
@@ -226,6 +228,7 @@ struct EpiBiasActHead {
     }
     __device__ __forceinline__ float* out_ptr(int, int64_t r, int64_t c) const { return C + r * ldc + c; }
     __device__ __forceinline__ void one(int, int64_t, int64_t, float) const {}
+    __device__ __forceinline__ void shift_rows(int64_t rows) { C += rows * ldc; Z += rows * ldz; }   // see EpiBiasAct
 };
 struct EpiActGrad {  // dZ = acc * act'(H) [* dropout mask of H] ; column sums of dZ per row tile -> bias-gradient partials
     static constexpr bool kDrop = true;
@@ -383,6 +386,35 @@ __global__ __launch_bounds__(256, 2) void wgrad_dgrad_kernel(Operand A1, Operand
     }
 }
 
+// A GROUP of row-parallel NT products in one launch: blockIdx.y = member j, each member the product a single launch of
+// gemm_kernel<kNT, ...> computes -- same tiles, same tail cut, same epilogue -- on its own rows: the A operand's logical rows
+// advance by j * a_rows (the row0 or the index list of its RowMap: consecutive batches of one matrix) or its pointer by
+// j * a_floats (stored activations), the outputs by j * out_rows rows, the tail workspace and its tickets by one set per
+// member.  All of it pointer arithmetic at entry; gemm_block is the one every other launch runs.  (A validation pass of the
+// block engine: the members do not depend on each other, and one batch alone cannot fill the chip with large tiles.)
+struct GroupShift {
+    int64_t a_rows = 0;       // logical rows (RowMap::row0 / RowMap::idx entries) between the A operands of consecutive members
+    int64_t a_floats = 0;     // floats between their base pointers
+    int64_t out_rows = 0;     // rows between their outputs (Epi::shift_rows)
+    int64_t tail_floats = 0;  // floats between their tail workspaces (GemmDims::tail_ws)
+    int tail_tickets = 0;     // tickets between their tail counters (GemmDims::tail_cnt)
+};
+template <class Cfg, bool VEC, bool GATHER, class Epi>
+__global__ __launch_bounds__(256, 2) void gemm_group_kernel(Operand A, Operand B, GemmDims d, Epi epi, GroupShift g) {
+    extern __shared__ __attribute__((aligned(16))) float lds_f[];
+    const int64_t j = blockIdx.y;
+    A.p += j * g.a_floats;
+    if (A.rows.idx != nullptr) A.rows.idx += j * g.a_rows;
+    else A.rows.row0 += j * g.a_rows;
+    epi.shift_rows(j * g.out_rows);
+    if (d.tail_split > 0) {
+        d.tail_ws += j * g.tail_floats;
+        d.tail_cnt += j * g.tail_tickets;
+    }
+    const BlockMap bm = map_block<kNT>(d, (int)blockIdx.x);
+    gemm_block<kNT, Cfg, 1, VEC, GATHER, Epi>(A, B, 0, d, bm.tile_m, bm.tile_n, bm.k_begin, bm.k_end, lds_f, epi, bm.tail_chunk);
+}
+
 // Tile configurations, each in two arithmetic flavours (template argument S): the FP32-input MFMA
 // (S = false) and FP32-accurate split products on the BF16 matrix pipe (S = true, gemm.h: split3 / mfma16);
 // gemm_split() picks at launch time (dcv_set_gemm_mode / DCV_GEMM_MODE).
@@ -464,6 +496,10 @@ inline bool alloc_tail_ws(TailWs* tw, int max_tiles_n) {
 #ifndef DCV_TAIL_MINSTAGES
 #define DCV_TAIL_MINSTAGES 2   // stages per tail chunk
 #endif
+inline int xcd_remap_enabled() {   // DCV_XCD_REMAP=0: plain block -> tile order
+    static const int env = [] { const char* e = getenv("DCV_XCD_REMAP"); return e ? atoi(e) : 1; }();
+    return env;
+}
 inline bool tail_split_enabled() {
     static const bool on = [] { const char* e = getenv("DCV_TAIL_KSPLIT"); return !(e && e[0] == '0'); }();
     return on;
@@ -489,8 +525,7 @@ static int prepare_gemm(const Operand& A, const Operand& B, int64_t M, int64_t N
     d.tiles_n = (int)cdiv(N, Cfg::TN);
     if (tiles_m_out) *tiles_m_out = d.tiles_m;
     {
-        static int env = -1;
-        if (env < 0) { const char* e = getenv("DCV_XCD_REMAP"); env = e ? atoi(e) : 1; }
+        const int env = xcd_remap_enabled();
         const int64_t nsplit = (MODE == kTN) ? cdiv(K, d.k_chunk) : 1;
         // Outputs up to 256 MB leave the kernel as write-through stores: the next launch (another set of XCDs) reads them
         // from memory either way, and a launch that ends without dirty lines skips the L2 write-back in front of its
@@ -658,11 +693,107 @@ static int launch_gemm(const Operand& A, const Operand& B, int64_t M, int64_t N,
 #endif
 }
 
+// ---- grouped NT products (gemm_group_kernel)
+template <bool S, bool HEAD, class F>
+static int with_cfg(CfgPick pick, F&& f) {   // the tile family launch_gemm_mode takes for `pick`
+    switch (pick) {
+        case kPickNarrowN: return f(CfgNarrowNT<S>{});
+        case kPickNarrowM: return f(CfgNarrowMT<S>{});
+        case kPickHalfM: return f(CfgHalfMT<S>{});
+        case kPickQuarter:
+            if constexpr (!HEAD) return f(CfgQuarterT<S>{});
+            else return f(CfgHalfMT<S>{});
+        default: return f(CfgBigT<S>{});
+    }
+}
+// (diagnostic) DCV_EVAL_GROUP_TILES=0: every member keeps the tile family of the single-batch launch
+inline bool group_retile_enabled() {
+    static const bool on = [] { const char* e = getenv("DCV_EVAL_GROUP_TILES"); return !(e && e[0] == '0'); }();
+    return on;
+}
+// `members` products of M rows each.  Every member must come out bit for bit as launch_gemm<kNT, Epi>(A, B, M, N, K) leaves
+// it, which fixes two things:
+//   * the ragged last row tile is cut along the contraction exactly when the single launch cuts it, into the same chunks: the
+//     single launch's plan is derived first and its tail plan imposed (the grouped launch's own workgroup count does not
+//     decide).  The chunk partials are summed in chunk order, so the sum does not depend on the tile height -- as long as
+//     the cut tile covers the same rows;
+//   * the tile family follows the group's total row count (sixteen batches of 8202 rows take 128 x 128 tiles where one takes
+//     64 x 64) only where that leaves every row's summation order alone: each family accumulates a 32 x 32 block over the
+//     contraction in the same order, so a regular row does not care, and a cut tail tile must begin at the same row in both
+//     families -- else the single launch's family stays.
+// tw: tail workspace of member 0 (one TailWs-sized set per member, g.tail_floats / g.tail_tickets apart).
+// Returns 1 when the product does not qualify (scalar loads), DCV_OK when it was enqueued, < 0 on error.
+template <bool S, class Epi>
+static int launch_gemm_group_mode(const Operand& A, const Operand& B, int64_t M, int64_t N, int64_t K, const Epi& epi, const GroupShift& g,
+                                  int members, const TailWs* tw, hipStream_t s) {
+    constexpr bool HEAD = Epi::kHead;
+    DCV_REQUIRE(members >= 1 && members < 65536, "gemm: %d members in a grouped launch", members);
+    const CfgPick pick1 = pick_cfg<kNT, HEAD>(M, N, K, 0);
+    GemmPlan single;
+    int64_t tm1 = 0;
+    int rc = with_cfg<S, HEAD>(pick1, [&](auto c) {
+        using C1 = decltype(c);
+        tm1 = C1::TM;
+        return prepare_gemm<kNT, C1, 1, Epi>(A, B, M, N, K, 0, epi, nullptr, tw, &single);
+    });
+    if (rc) return rc;
+    if (!single.vec) return 1;
+    auto go = [&](auto c, const GemmPlan& pl) -> int {
+        using Cfg = decltype(c);
+        constexpr size_t lds = gemm_lds_bytes<Cfg, 1>();
+        static_assert(lds <= 64 * 1024, "grouped launch: LDS beyond the default limit");
+        const GemmDims& d = pl.d;
+        const int64_t blocks = d.tail_split > 0 ? (int64_t)(d.tiles_m - 1 + d.tail_split) * d.tiles_n : (int64_t)d.tiles_m * d.tiles_n;
+        if (pl.gather)
+            hipLaunchKernelGGL((gemm_group_kernel<Cfg, true, true, Epi>), dim3((unsigned)blocks, (unsigned)members), dim3(256), lds, s, A, B, d, epi, g);
+        else
+            hipLaunchKernelGGL((gemm_group_kernel<Cfg, true, false, Epi>), dim3((unsigned)blocks, (unsigned)members), dim3(256), lds, s, A, B, d, epi, g);
+        DCV_CHECK_LAUNCH();
+        return DCV_OK;
+    };
+    const CfgPick pick2 = group_retile_enabled() ? pick_cfg<kNT, HEAD>(M * members, N, K, 0) : pick1;
+    if (pick2 != pick1) {
+        rc = with_cfg<S, HEAD>(pick2, [&](auto c) -> int {
+            using C2 = decltype(c);
+            GemmPlan pl;
+            const int r = prepare_gemm<kNT, C2, 1, Epi>(A, B, M, N, K, 0, epi, nullptr, nullptr, &pl);
+            if (r) return r;
+            if (!pl.vec) return 1;
+            if (single.d.tail_split > 0) {
+                // the cut tile of this family must be the single launch's: same first row, ragged, not the only row tile
+                constexpr int64_t TM2 = C2::TM;
+                const int64_t S1 = single.d.tail_split;
+                if (M % TM2 == 0 || (M / TM2) * TM2 != (M / tm1) * tm1 || pl.d.tiles_m < 2 || K % C2::KB != 0) return 1;
+                if (pl.d.tiles_n > tw->max_tiles_n || (int64_t)pl.d.tiles_n * S1 * C2::FM * C2::FN * 16 * 256 > tw->cap) return 1;
+                pl.d.tail_split = (int)S1;
+                pl.d.k_chunk = single.d.k_chunk;
+                pl.d.tail_ws = single.d.tail_ws;
+                pl.d.tail_cnt = single.d.tail_cnt;
+                pl.d.xcd_remap = xcd_remap_enabled() && (pl.d.tiles_m - 1) % 8 == 0 && pl.d.tiles_n > 1;
+            }
+            return go(c, pl);
+        });
+        if (rc != 1) return rc;
+    }
+    return with_cfg<S, HEAD>(pick1, [&](auto c) { return go(c, single); });
+}
+template <class Epi>
+static int launch_gemm_group(const Operand& A, const Operand& B, int64_t M, int64_t N, int64_t K, const Epi& epi, const GroupShift& g, int members,
+                             const TailWs* tw, hipStream_t s) {
+    if (gemm_split()) return launch_gemm_group_mode<true, Epi>(A, B, M, N, K, epi, g, members, tw, s);
+    return launch_gemm_group_mode<false, Epi>(A, B, M, N, K, epi, g, members, tw, s);
+}
+
 // The engine's products as plain functions, one translation unit per epilogue (inst_*.hip) so that the build compiles
 // them in parallel; each is launch_gemm<MODE, Epi> of the named epilogue.
 int gemm_nt_bias_act(const Operand& A, const Operand& B, int64_t M, int64_t N, int64_t K, const EpiBiasAct& epi, hipStream_t s, const TailWs* tw);
 int gemm_nt_head4(const Operand& A, const Operand& B, int64_t M, int64_t N, int64_t K, const EpiBiasActHead<4>& epi, hipStream_t s, const TailWs* tw);
 int gemm_nt_head8(const Operand& A, const Operand& B, int64_t M, int64_t N, int64_t K, const EpiBiasActHead<8>& epi, hipStream_t s, const TailWs* tw);
+// the first two as grouped launches (launch_gemm_group; same translation units): 1 = not applicable
+int gemm_nt_bias_act_group(const Operand& A, const Operand& B, int64_t M, int64_t N, int64_t K, const EpiBiasAct& epi, const GroupShift& g, int members,
+                           const TailWs* tw, hipStream_t s);
+int gemm_nt_head4_group(const Operand& A, const Operand& B, int64_t M, int64_t N, int64_t K, const EpiBiasActHead<4>& epi, const GroupShift& g, int members,
+                        const TailWs* tw, hipStream_t s);
 int gemm_tn_slab(const Operand& A, const Operand& B, int64_t M, int64_t N, int64_t K, int64_t k_chunk, const EpiSlab& epi, hipStream_t s);
 int gemm_nn_act_grad(const Operand& A, const Operand& B, int64_t M, int64_t N, int64_t K, const EpiActGrad& epi, hipStream_t s,
                      int* tiles_m_out, const TailWs* tw);

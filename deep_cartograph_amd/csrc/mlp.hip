@@ -690,14 +690,17 @@ static TicaGradWaveFn tica_grad_wave_fn(int d) {
 // the chip, few enough partials for the last block's ordered sum.  One launch: the block that finishes last adds the
 // partials up in block order and -- on one GPU, where nothing is all-reduced in between (fused.on) -- goes straight
 // on to the d x d loss head (tica_grad_body), saving the launch of tica_grad_kernel.
-template <int D>
-__global__ __launch_bounds__(256) void tica_stats_rows_kernel(const float* __restrict__ F, int64_t ld, int B, int lag_off,
-                                                              int rows_per_block, double* __restrict__ part, unsigned* __restrict__ ticket,
-                                                              double* __restrict__ out, FusedHead fused) {
+// GROUP: member `member` of `members` batches evaluated side by side (tica_stats_rows_group_kernel): the caller hands in the
+// member's own rows, partials and ticket; its record goes to slot (counter + member), the counter itself stays put.
+template <int D, bool GROUP>
+__device__ __forceinline__ void tica_stats_rows_body(const float* __restrict__ F, int64_t ld, int B, int lag_off, int rows_per_block,
+                                                     double* __restrict__ part, unsigned* __restrict__ ticket, double* __restrict__ out,
+                                                     const FusedHead& fused, int member, int members) {
     constexpr int W = 2 * D + 2 * D * D;
     __shared__ double red[4][W];
     __shared__ TicaWaveLds<D> s_head;
     __shared__ unsigned s_last;
+    __shared__ int s_slot;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     double acc[W];
 #pragma unroll
@@ -765,16 +768,44 @@ __global__ __launch_bounds__(256) void tica_stats_rows_kernel(const float* __res
             double s = 0.0;
 #pragma unroll
             for (int q = 0; q < G; ++q) s += s_grp[q][t];
-            out[t] = s;
+            if (!GROUP || member == members - 1) out[t] = s;   // (a group leaves the statistics of its last batch, as stepping does)
             red[0][t] = s;
         }
         if (fused.on) {
             __syncthreads();
-            if (wave == 0)
-                tica_grad_wave<D>(s_head, &red[0][0], fused.Bg, fused.reg, fused.gradp, fused.log, fused.log_count, fused.log_cap, fused.log_width, lane);
+            if (wave == 0) {
+                if constexpr (!GROUP) {
+                    tica_grad_wave<D>(s_head, &red[0][0], fused.Bg, fused.reg, fused.gradp, fused.log, fused.log_count, fused.log_cap, fused.log_width, lane);
+                } else {
+                    // records in batch order: this head is handed a log base moved by `member` records and a private copy of the
+                    // counter, which nobody moves inside the launch (log_advance_kernel does, behind it, by the group size)
+                    if (lane == 0) s_slot = *fused.log_count;
+                    wave_sync_lds();
+                    tica_grad_wave<D>(s_head, &red[0][0], fused.Bg, fused.reg, fused.gradp, fused.log + (int64_t)member * fused.log_width, &s_slot,
+                                      fused.log_cap - member, fused.log_width, lane);
+                }
+            }
         }
     }
 }
+template <int D>
+__global__ __launch_bounds__(256) void tica_stats_rows_kernel(const float* __restrict__ F, int64_t ld, int B, int lag_off,
+                                                              int rows_per_block, double* __restrict__ part, unsigned* __restrict__ ticket,
+                                                              double* __restrict__ out, FusedHead fused) {
+    tica_stats_rows_body<D, false>(F, ld, B, lag_off, rows_per_block, part, ticket, out, fused, 0, 1);
+}
+// blockIdx.y = member: the network outputs of member j begin f_stride floats behind member j - 1's, its partials are
+// part + j * gridDim.x * W, its ticket is ticket[j] (zero between launches)
+template <int D>
+__global__ __launch_bounds__(256) void tica_stats_rows_group_kernel(const float* __restrict__ F, int64_t ld, int64_t f_stride, int B, int lag_off,
+                                                                    int rows_per_block, double* __restrict__ part, unsigned* __restrict__ ticket,
+                                                                    double* __restrict__ out, FusedHead fused) {
+    constexpr int W = 2 * D + 2 * D * D;
+    const int j = blockIdx.y, n = gridDim.y;
+    tica_stats_rows_body<D, true>(F + (int64_t)j * f_stride, ld, B, lag_off, rows_per_block, part + (int64_t)j * gridDim.x * W, ticket + j, out, fused, j, n);
+}
+// the log counter behind a grouped launch: every head of the group read it, none moved it
+__global__ void log_advance_kernel(int* __restrict__ log_count, int n) { *log_count += n; }
 typedef void (*tica_stats_fn_t)(const float*, int64_t, int, int, int, double*, unsigned*, double*, FusedHead);
 static tica_stats_fn_t tica_stats_rows_fn(int d) {
     switch (d) {
@@ -785,7 +816,17 @@ static tica_stats_fn_t tica_stats_rows_fn(int d) {
         default: return nullptr;
     }
 }
-// rows per block of the kernel above: at most 512 blocks, whole multiples of 256 rows
+typedef void (*tica_stats_group_fn_t)(const float*, int64_t, int64_t, int, int, int, double*, unsigned*, double*, FusedHead);
+static tica_stats_group_fn_t tica_stats_rows_group_fn(int d) {
+    switch (d) {
+        case 1: return tica_stats_rows_group_kernel<1>;
+        case 2: return tica_stats_rows_group_kernel<2>;
+        case 3: return tica_stats_rows_group_kernel<3>;
+        case 4: return tica_stats_rows_group_kernel<4>;
+        default: return nullptr;
+    }
+}
+// rows per block of the kernels above: at most 512 blocks, whole multiples of 256 rows
 static int stats_rows_per_block(int64_t batch) { return (int)(cdiv(cdiv(batch, 256), 256) * 256); }   // <= 256 blocks: each ends on one ticket (~70 ns apiece, serialised)
 
 // Gradient of the loss w.r.t. the network outputs.  Sample i (0 <= i < B) has f_t in row i and f_lag in
@@ -1344,7 +1385,7 @@ static void mlp_free(dcv_mlp* m) {
     g_launch_ev = LaunchEvents{};   // no stale offer of events that are about to be destroyed
     g_launch_taken = nullptr;
     for (hipEvent_t e : m->prof_ev) (void)hipEventDestroy(e);
-    f(m->tail.ws); f(m->tail.cnt);
+    f(m->tail.ws); f(m->tail.cnt); f(m->eval_ws.base);
     for (int i = 0; i < 4; ++i) if (m->gexec[i]) (void)hipGraphExecDestroy(m->gexec[i]);
     delete m;
 }
@@ -1438,6 +1479,8 @@ extern "C" int dcv_mlp_create(const dcv_mlp_desc* desc, dcv_mlp** out) {
     m->upper_cb = nullptr;
     m->upper_cb_user = nullptr;
     m->tail = dcv::TailWs{};
+    m->eval_ws = dcv::EvalGroupWs{};
+    m->last_eval_group = 0;
     m->drop_step = 0;
     m->cur_step = 0;
     m->drop_rank = 0;
@@ -1695,6 +1738,7 @@ extern "C" int dcv_mlp_layer_output(dcv_mlp* m, int32_t layer, int64_t rows, flo
 
 extern "C" int64_t dcv_mlp_dropout_step(const dcv_mlp* m) { return m ? m->drop_step : 0; }
 extern "C" int32_t dcv_mlp_last_path(const dcv_mlp* m) { return m ? m->last_path : -1; }
+extern "C" int32_t dcv_mlp_last_eval_group(const dcv_mlp* m) { return m ? m->last_eval_group : -1; }
 
 extern "C" int dcv_mlp_dropout_mask(dcv_mlp* m, int32_t layer, int64_t step, int64_t rows, float* out_d, void* stream) {
     DCV_REQUIRE(m && out_d && layer >= 0 && layer < m->L && rows >= 1 && step >= 0, "dcv_mlp_dropout_mask: bad arguments");
@@ -2695,11 +2739,151 @@ extern "C" int dcv_mlp_train_steps(dcv_mlp* m, const float* Xn_d, int64_t ld, co
     return DCV_OK;
 }
 
+// ---- grouped validation pass of the block engine
+// DCV_EVAL_GROUP (read once per process): 0 = dcv_mlp_eval_steps steps batch by batch on the block engine, as it did before
+// the grouped pass existed; N >= 2 = at most N members per launch; unset = kEvalBatchesPerLaunch
+static int eval_group_limit() {
+    static const int lim = [] {
+        const char* e = getenv("DCV_EVAL_GROUP");
+        if (!e || !e[0]) return kEvalBatchesPerLaunch;
+        const int v = atoi(e);
+        return v <= 1 ? 0 : (v < kEvalBatchesPerLaunch ? v : kEvalBatchesPerLaunch);
+    }();
+    return lim;
+}
+// The workspace for `members` batches of R rows (`batch` pairs) each: per layer [members][R][ldh] outputs, then per member a
+// tail workspace of the engine's size (TailWs) and the statistics partials, then the tickets (8 tail tickets per member,
+// one statistics ticket per member).  Every region starts on a 256-byte boundary.
+struct EvalGroupLayout {
+    size_t act[DCV_MAX_LAYERS], tail, spart, tickets, ticket_bytes, bytes;
+    size_t stat_tickets;   // index of the first statistics ticket
+    int stat_blocks;
+};
+static EvalGroupLayout eval_group_layout(const dcv_mlp* m, int members, int64_t R, int batch) {
+    EvalGroupLayout lo{};
+    size_t off = 0;
+    auto take = [&](size_t n) { const size_t at = off; off += align_up(n, 256); return at; };
+    for (int l = 0; l < m->L; ++l) lo.act[l] = take((size_t)members * R * m->layers[l].ldh * sizeof(float));
+    lo.tail = take(m->tail.ws ? (size_t)members * m->tail.cap * sizeof(float) : 0);
+    lo.stat_blocks = (int)cdiv(batch, stats_rows_per_block(batch));
+    lo.spart = take((size_t)members * lo.stat_blocks * m->stats_len * sizeof(double));
+    lo.stat_tickets = (size_t)members * 8;
+    lo.ticket_bytes = (lo.stat_tickets + members) * sizeof(unsigned);
+    lo.tickets = take(lo.ticket_bytes);
+    lo.bytes = off;
+    return lo;
+}
+// Up to `want` consecutive evaluation batches (batch j = the pairs [j * batch, (j + 1) * batch) behind idx_d / row0) as ONE
+// launch per layer and one statistics launch: the batches of a validation pass do not depend on each other (the weights
+// stand still), and one batch of a few thousand rows cannot fill the chip with large tiles -- a group can.  Every member is
+// computed exactly as dcv_mlp_eval_step computes it (gemm_kernels.h: launch_gemm_group; tica_stats_rows_group_kernel), into
+// its own segment of a workspace: the engine's activation buffers, sign masks and gradients are not touched.
+// Returns the members launched (>= 2), 0 when the group form does not apply (the caller steps), < 0 on error.
+static int eval_group(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t* idx_d, int64_t row0, int32_t batch, int want, hipStream_t s) {
+    tica_stats_group_fn_t stats_fn = tica_stats_rows_group_fn(m->d_out);
+    if (m->desc.model != DCV_MODEL_DEEPTICA || stats_fn == nullptr || m->any_drop || m->any_bn || m->eval_ws.failed) return 0;
+    if (!(m->snet_dt_tried && m->snet_dt == nullptr)) return 0;   // a single step might take the fused small-network kernels
+    for (int l = 0; l < m->L; ++l)   // a fused narrow layer of 5 - 8 outputs has no grouped instantiation
+        if (l + 1 < m->L && next_layer_fusable(m, l)) {
+            if (m->layers[l + 1].out > 4) return 0;
+            ++l;
+        }
+    int members = want < eval_group_limit() ? want : eval_group_limit();
+    const bool was_train = m->fwd_train;
+    m->fwd_train = false;   // (rows_of / batch_rows ask)
+    const int64_t R = rows_of(m, idx_d, batch);
+    const RowMap rm = batch_rows(m, idx_d, row0, batch);
+    const int lag_off = lag_offset(m, idx_d, batch);
+    m->fwd_train = was_train;
+    const size_t per_member = eval_group_layout(m, 2, R, batch).bytes - eval_group_layout(m, 1, R, batch).bytes;
+    if ((size_t)members * per_member > kEvalGroupBudgetBytes) members = (int)(kEvalGroupBudgetBytes / per_member);
+    if (members < 2) return 0;
+    // The first grouped pass of an engine allocates here (a fit: inside its first validation pass, once: a hipMalloc of up to
+    // kEvalGroupBudgetBytes, about a millisecond); later passes of the same shape find the workspace as it is.  Only a pass
+    // with more members or longer batches than any before frees it (hipFree waits for the device) and allocates again.
+    EvalGroupWs& ws = m->eval_ws;
+    const bool same = ws.base != nullptr && ws.members >= members && ws.rows == R && ws.batch == batch;   // (a smaller group uses the first segments)
+    const EvalGroupLayout lo = eval_group_layout(m, same ? ws.members : members, R, batch);
+    if (!same) {
+        if (ws.bytes < lo.bytes) {
+            if (ws.base) (void)hipFree(ws.base);
+            ws = EvalGroupWs{};
+            void* p = nullptr;
+            if (hipMalloc(&p, lo.bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                ws.failed = true;   // not an error: the pass steps batch by batch
+                return 0;
+            }
+            ws.base = static_cast<char*>(p);
+            ws.bytes = lo.bytes;
+        }
+        // the tickets of this layout (zero between launches from here on: every last arriver resets its own)
+        DCV_CHECK_HIP(hipMemsetAsync(ws.base + lo.tickets, 0, lo.ticket_bytes, s));
+        ws.members = members;
+        ws.rows = R;
+        ws.batch = batch;
+    }
+    auto act_of = [&](int l) { return reinterpret_cast<float*>(ws.base + lo.act[l]); };
+    unsigned* tickets = reinterpret_cast<unsigned*>(ws.base + lo.tickets);
+    TailWs tw{};
+    if (m->tail.ws) tw = TailWs{reinterpret_cast<float*>(ws.base + lo.tail), tickets, m->tail.cap, m->tail.max_tiles_n};
+    g_launch_ev = LaunchEvents{};
+    for (int l = 0; l < m->L; ++l) {
+        const LayerPlan& p = m->layers[l];
+        GroupShift g;
+        g.out_rows = R;
+        g.tail_floats = m->tail.cap;
+        g.tail_tickets = 8;
+        Operand A;
+        if (l == 0) {
+            A = make_operand(Xn_d, ld, p.in, rm);
+            g.a_rows = batch;
+        } else {
+            A = make_operand(act_of(l - 1), m->layers[l - 1].ldh, p.in);
+            g.a_floats = R * m->layers[l - 1].ldh;
+        }
+        Operand B = make_operand(m->params + p.w_off, p.in, p.in);
+        float* H = act_of(l);
+        int rc;
+        if (l + 1 < m->L && next_layer_fusable(m, l)) {   // as run_forward: the narrow Linear behind this layer rides in its epilogue
+            const LayerPlan& nx = m->layers[l + 1];
+            const bool vec = quad_ok(H, p.ldh) && quad_ok(m->params + p.b_off, 4) && quad_ok(m->params + nx.w_off, nx.in);
+            EpiBiasActHead<4> epi{H, p.ldh, m->params + p.b_off, p.act, vec, m->params + nx.w_off, nx.in, m->params + nx.b_off, nx.out, nx.act, act_of(l + 1), nx.ldh};
+            rc = gemm_nt_head4_group(A, B, R, p.out, p.in, epi, g, members, &tw, s);
+            ++l;
+        } else {
+            EpiBiasAct epi{H, p.ldh, m->params + p.b_off, p.act, quad_ok(H, p.ldh) && quad_ok(m->params + p.b_off, 4)};
+            rc = gemm_nt_bias_act_group(A, B, R, p.out, p.in, epi, g, members, &tw, s);
+        }
+        if (rc < 0) return rc;
+        if (rc != DCV_OK) return 0;   // (scalar-load operands: nothing of the group reached the log)
+    }
+    const LayerPlan& last = m->layers[m->L - 1];
+    const FusedHead fh{1, (double)batch, m->desc.tica_reg, nullptr, m->log, m->log_count, m->log_cap, m->log_width};
+    hipLaunchKernelGGL(stats_fn, dim3((unsigned)lo.stat_blocks, (unsigned)members), dim3(256), 0, s, (const float*)act_of(m->L - 1), last.ldh, R * last.ldh,
+                       (int)batch, lag_off, stats_rows_per_block(batch), reinterpret_cast<double*>(ws.base + lo.spart), tickets + lo.stat_tickets, m->stats, fh);
+    DCV_CHECK_LAUNCH();
+    hipLaunchKernelGGL(log_advance_kernel, dim3(1), dim3(1), 0, s, m->log_count, members);
+    DCV_CHECK_LAUNCH();
+    // the engine as the last single evaluation step would leave it
+    for (int l = 0; l < m->L; ++l) m->layers[l].mask_rows = -1;
+    m->fwd_train = false;
+    m->head_done = false;
+    m->snet_fwd_valid = false;
+    m->last_path = 0;
+    m->last_batch = batch;
+    return members;
+}
+
 // nbatches consecutive evaluation steps -- batch j = samples [j * batch, (j + 1) * batch) of the index list (idx_d + j * batch)
 // or of the row range (row0 + j * batch) -- with one loss record each, in batch order: the records dcv_mlp_eval_step would
 // append one call at a time.  A small network (snet.hip / snet_dt.hip) evaluates up to kEvalBatchesPerLaunch batches per
 // launch -- a validation pass is then one launch instead of one (autoencoder) or one (Deep-TICA) per batch, each of which is
-// mostly launch latency and weight staging; every other engine runs the steps one after the other.
+// mostly launch latency and weight staging.  The block engine evaluates a Deep-TICA network (no dropout, no batch
+// normalisation, at most 4 outputs) in groups of up to kEvalBatchesPerLaunch batches, as many as kEvalGroupBudgetBytes of
+// workspace hold: one launch per layer with a member per batch (eval_group), full groups first, then the rest (a single
+// batch left over takes dcv_mlp_eval_step); DCV_EVAL_GROUP=0 turns that off.  Every other engine runs the steps one after
+// the other.  The records are bit for bit those of the single steps on every path.
 extern "C" int dcv_mlp_eval_steps(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t* idx_d, int64_t row0, int32_t batch, int32_t nbatches,
                                   void* stream) {
     DCV_REQUIRE(m && Xn_d, "dcv_mlp_eval_steps: null argument");
@@ -2709,11 +2893,14 @@ extern "C" int dcv_mlp_eval_steps(dcv_mlp* m, const float* Xn_d, int64_t ld, con
     DCV_REQUIRE(m->log && m->log_cap > 0, "dcv_mlp_eval_steps: call dcv_mlp_reset_log first");
     hipStream_t s = as_stream(stream);
     int32_t j = 0;
+    m->last_eval_group = 0;
+    bool grouped = false;
     while (j < nbatches) {
         const int64_t off = (int64_t)j * batch;
         const int64_t* idx_j = idx_d ? idx_d + off : nullptr;
         const int64_t row_j = idx_d ? row0 : row0 + off;
         int nb = nbatches - j < kEvalBatchesPerLaunch ? nbatches - j : kEvalBatchesPerLaunch;
+        const int left = nbatches - j;
         int rc = 1;
         if (nb > 1 && !m->any_drop && !m->any_bn && !prof_on(m, 0)) {   // (a profiled run samples single steps)
             g_launch_ev = LaunchEvents{};
@@ -2742,6 +2929,16 @@ extern "C" int dcv_mlp_eval_steps(dcv_mlp* m, const float* Xn_d, int64_t ld, con
                 m->last_batch = batch;
                 j += nb;
                 continue;
+            }
+            if (left > 1 && eval_group_limit() > 0) {   // the block engine: groups of batches, one launch per layer
+                const int done = eval_group(m, Xn_d, ld, idx_j, row_j, batch, left, s);
+                if (done < 0) return done;
+                if (done > 0) {
+                    if (!grouped) m->last_eval_group = done;
+                    grouped = true;
+                    j += done;
+                    continue;
+                }
             }
         }
         rc = dcv_mlp_eval_step(m, Xn_d, ld, idx_j, row_j, batch, stream);

@@ -7,6 +7,16 @@ namespace dcv {
 
 constexpr int kMaxTicaDim = 16;
 
+// Workspace of a grouped validation pass of the block engine (mlp.hip: eval_group): ONE device allocation, held by the engine
+// from the first grouped pass on and grown only when a later pass wants more members or longer batches than it holds.
+struct EvalGroupWs {
+    char* base = nullptr;
+    size_t bytes = 0;
+    int members = 0, batch = 0;   // the layout it is carved into (eval_group_layout): members, pairs per batch, rows per member
+    int64_t rows = 0;
+    bool failed = false;       // an allocation failed once: the engine keeps stepping batch by batch
+};
+
 struct LayerPlan {
     int in, out, act;
     int64_t w_off, b_off;      // offsets into the flat parameter buffer (floats, 16-byte aligned)
@@ -48,6 +58,8 @@ struct dcv_mlp {
     bool any_bn;               // some layer is followed by a batch normalisation
     bool fwd_train;            // the last forward ran in training mode (dropout active): backward must agree
     dcv::TailWs tail;          // workspace of the contraction-split tail tile of row-tiled products (gemm.h: GemmDims::tail_split)
+    dcv::EvalGroupWs eval_ws;  // grouped validation pass (dcv_mlp_eval_steps, block engine)
+    int last_eval_group;       // members of the first grouped launch of the last dcv_mlp_eval_steps call (0: it stepped batch by batch)
     void (*upper_cb)(void*);   // data-parallel overlap hook (dcv_mlp_set_upper_grads_callback) or null
     void* upper_cb_user;
     bool head_done;            // the last forward already ran the d x d loss head inside its statistics launch (one-GPU steps)
@@ -122,6 +134,11 @@ struct ReduceArgsView {
 // (the plans allocate their per-batch tickets and per-workgroup partials for these bounds when they are built: no allocation
 // lands in a timed validation pass)
 constexpr int kEvalBatchesPerLaunch = 64;
+// The block engine's grouped pass keeps one segment of every layer's output per member, plus the member's tail workspace and
+// statistics partials: as many members as fit this budget.  The headline network (512-256-128-4, batches of 8192 pairs = 8202
+// shared rows) needs 8202 rows x (256 + 128 + 4) floats = 12.7 MB of activations + 2 MB of tail workspace per member:
+// 18 members (16 would be 204 MB of activations).  Measured on that shape: 8 members 21.6 us per batch, 18 members 19.3.
+constexpr size_t kEvalGroupBudgetBytes = 256ull << 20;
 constexpr int64_t kEvalWorkgroupsPerLaunch = 4096;
 // snet.hip: the whole autoencoder step in one launch when the network fits in LDS; 1 = not applicable
 // R rows of this rank, `batch` = the GLOBAL batch (loss scale 2 / (batch * F)); write_log = false: the caller logs (after an all-reduce)

@@ -340,6 +340,9 @@ int dcv_mlp_bn_state(dcv_mlp* m, int32_t layer, float* running_mean_h, float* ru
  * one launch, backward in a second: snet_dt.hip).  The fused forms are taken when every weight fits in one CU's LDS
  * (reference-sized networks, cv_calculator.py:2471-2590); DCV_NO_SNET=1 in the environment forces 0. */
 int32_t dcv_mlp_last_path(const dcv_mlp* m);
+/* Test hook: the batches in the first (largest) grouped launch of the last dcv_mlp_eval_steps call on the block engine, 0 when
+ * that call stepped batch by batch or went through the fused small-network kernels. */
+int32_t dcv_mlp_last_eval_group(const dcv_mlp* m);
 /* Test hook: post-activation output of Linear `layer` in the last forward (rows x dims[layer + 1] floats, dense).
  * DCV_ESTATE after a fused small-network forward (dcv_mlp_last_path != 0: the activations never left LDS). */
 int dcv_mlp_layer_output(dcv_mlp* m, int32_t layer, int64_t rows, float* out_d, void* stream);
@@ -359,7 +362,11 @@ int dcv_mlp_train_steps(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t
  * trainer.fit): `nbatches` evaluation steps of `batch` samples each, batch j = idx_d[j * batch, (j + 1) * batch) -- or the
  * rows row0 + [j * batch, (j + 1) * batch) when idx_d is null -- appending the nbatches loss records dcv_mlp_eval_step
  * would append, in batch order, bit for bit.  Networks small enough for the fused kernels (dcv_mlp_last_path 1 / 2) are
- * evaluated many batches per launch; the others step by step.  A ragged last batch is a separate dcv_mlp_eval_step.
+ * evaluated many batches per launch.  So is a Deep-TICA network on the block engine (dcv_mlp_last_path 0) without dropout or
+ * batch normalisation and with at most 4 outputs: groups of batches, one launch per layer and one for the statistics and loss
+ * heads, each batch computed as the single step computes it, in a workspace the engine allocates on the first such pass
+ * (at most 256 MB; if that fails the pass steps).  DCV_EVAL_GROUP=0 in the environment (read once) turns the block
+ * engine's groups off.  Everything else steps batch by batch.  A ragged last batch is a separate dcv_mlp_eval_step.
  * dcv_mlp_stats() is unspecified afterwards. */
 int dcv_mlp_eval_steps(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t* idx_d, int64_t row0,
                        int32_t batch, int32_t nbatches, void* stream);
