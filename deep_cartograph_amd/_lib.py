@@ -145,6 +145,9 @@ SIGNATURES = {
     "dcv_nearest_rows_workspace": (_SZ, [_I64, _I32, _I32]),
     "dcv_nearest_rows": (C.c_int, [_P, _I64, _I32, _P, _I32, _I64, _P, _P, _P, _SZ, _P]),
     "dcv_nearest_point": (C.c_int, [_P, _I64, _P, _I64, _I32, _P, _P]),
+    "dcv_linkage_workspace": (_SZ, [_I64, _I32]),
+    "dcv_linkage_pdist": (C.c_int, [_P, _I64, _I32, _P, _SZ, _P]),
+    "dcv_linkage": (C.c_int, [_P, _I64, _I32, _I32, _P, C.POINTER(_I64), _P, _SZ, _P]),
     "dcv_gemm_f32": (C.c_int, [_I32, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
 }
 

@@ -347,6 +347,38 @@ def nearest_point(train: torch.Tensor, sup: torch.Tensor) -> torch.Tensor:
     return nn
 
 
+LINKAGE_METHOD = {"complete": 0, "average": 1, "ward": 2}
+
+
+def linkage_workspace_bytes(n: int, d: int) -> int:
+    return int(_lib.load().dcv_linkage_workspace(n, d))
+
+
+def linkage(P: torch.Tensor, method: str = "complete", return_searches: bool = False):
+    """scipy.cluster.hierarchy.linkage(P, method, "euclidean") for method in complete / average / ward on the GPU:
+    the (n - 1) x 4 float64 linkage matrix as a NumPy array, equal to scipy's (dcv_linkage).  P is n x d float64 on
+    the device, finite, n >= 2, d <= 16.  With `return_searches` also the number of row searches the chain ran."""
+    _require_gpu(P)
+    _check_matrix(P, torch.float64)
+    if method not in LINKAGE_METHOD:
+        raise DcvError(f"linkage: method {method!r} is not one of {sorted(LINKAGE_METHOD)}")
+    P = P.contiguous()
+    n, d = P.shape
+    # a NaN never compares below anything: the chain would find no neighbour.  Refused here; the kernels keep their own guard
+    if n > 0 and not bool(torch.isfinite(P).all()):
+        raise DcvError("linkage failed (code -1): the points hold NaN or infinite values")
+    import ctypes as C
+
+    lib = _lib.load()
+    Z = np.empty((max(n - 1, 0), 4), dtype=np.float64)
+    searches = C.c_int64(0)
+    nbytes = lib.dcv_linkage_workspace(n, d)
+    ws = _ws(nbytes, P.device) if nbytes else None   # 0: the arguments are out of range, dcv_linkage says which
+    check(lib.dcv_linkage(_ptr(P), n, d, LINKAGE_METHOD[method], Z.ctypes.data, C.byref(searches), _ptr(ws), nbytes, _stream()),
+          "dcv_linkage")
+    return (Z, int(searches.value)) if return_searches else Z
+
+
 # ------------------------------------------------------------------------------- MLP engine
 class RcclComm:
     """RCCL communicator owned by the library (dcv_comm_*): the collectives of a data-parallel step are then issued by

@@ -5,10 +5,18 @@ deep_cartograph/modules/statistics/statistics.py (optimize_clustering :17-110, c
 k-means runs on the GPU: the Lloyd iterations (assignment, per-cluster sums, inertia, changed
 labels) are one HIP pass each over the float64 points, k-means++ seeding and the convergence
 logic follow scikit-learn's KMeans(random_state=0) step by step on the host (SURVEY.md Appendix
-A.8), so the labels equal the reference's.  Hierarchical clustering and HDBSCAN keep delegating
-to scikit-learn, as the scope table says (O(N^2) tree algorithms, out of scope)."""
+A.8), so the labels equal the reference's.
+
+Hierarchical clustering with complete / average / ward linkage runs on the GPU as well: the
+nearest-neighbour chain of scipy.cluster.hierarchy.linkage over a device-resident distance
+matrix (hip.linkage, csrc/linkage.hip) gives scipy's dendrogram bit for bit, ties included;
+the cut (scikit-learn's _hc_cut) and the centroids are host work over n - 1 merges.
+optimize_clustering builds the tree once for all k and scores every cut with the GPU score
+kernels.  `single` linkage and HDBSCAN keep delegating to scikit-learn, and so does a point
+set whose n x n matrix does not fit the free device memory."""
 from __future__ import annotations
 
+import heapq
 import logging
 import sys
 from typing import Dict, Optional, Tuple
@@ -179,9 +187,71 @@ def kmeans_clustering(feature_matrix: np.ndarray, num_clusters: int, n_init: int
     return labels.cpu().numpy(), centers + pts.mean
 
 
-def cluster_data(features: np.ndarray, settings: Dict, initial_centroids: np.ndarray = None, pts: Optional[_DevicePoints] = None) -> Tuple[np.ndarray, np.ndarray]:
+GPU_LINKAGES = ("complete", "average", "ward")
+LINKAGE_HEADROOM = 0.8   # share of the FREE device memory the distance matrix may take: the cards are shared
+
+
+def hierarchical_tree(features: np.ndarray, linkage: str = "complete") -> Tuple[np.ndarray, np.ndarray]:
+    """The dendrogram of AgglomerativeClustering(linkage=...) on the GPU: (children (n - 1) x 2 int64, heights n - 1),
+    scikit-learn's children_ / distances_ -- scipy.cluster.hierarchy.linkage(features, linkage)[:, :2] and [:, 2]."""
+    P = torch.from_numpy(np.ascontiguousarray(features, dtype=np.float64)).to(_device())
+    Z = hip.linkage(P, linkage)
+    return Z[:, :2].astype(np.int64), Z[:, 2].copy()
+
+
+def cut_tree(children: np.ndarray, n_clusters: int) -> np.ndarray:
+    """Labels of the cut of a dendrogram into `n_clusters` (sklearn.cluster._agglomerative._hc_cut): from the root the
+    highest node is split n_clusters - 1 times (a heap of negated node ids); label i goes to the leaves below the i-th
+    entry of the final heap list."""
+    children = np.asarray(children)
+    n = children.shape[0] + 1
+    if n_clusters > n:
+        raise ValueError(f"Cannot extract more clusters than samples: {n_clusters} clusters were given for a tree with {n} leaves.")
+    if n_clusters < 1:
+        raise ValueError(f"n_clusters = {n_clusters}: at least one cluster")
+    ch = children.tolist()
+    nodes = [-(max(ch[-1]) + 1)]
+    for _ in range(n_clusters - 1):
+        a, b = ch[-nodes[0] - n]
+        heapq.heappush(nodes, -a)
+        heapq.heappushpop(nodes, -b)
+    labels = np.zeros(n, dtype=np.intp)
+    for i, node in enumerate(nodes):
+        stack, leaves = [-node], []
+        while stack:
+            a = stack.pop()
+            if a < n:
+                leaves.append(a)
+            else:
+                stack.extend(ch[a - n])
+        labels[leaves] = i
+    return labels
+
+
+def _linkage_on_gpu(features: np.ndarray, linkage: str) -> bool:
+    """Whether the hierarchical tree of these points is built on the GPU; one log line when it is not."""
+    n, d = features.shape
+    if linkage not in GPU_LINKAGES:
+        logger.info(f"hierarchical clustering with {linkage} linkage is delegated to scikit-learn (GPU: {', '.join(GPU_LINKAGES)})")
+        return False
+    if n < 2 or d > 16:
+        logger.info(f"hierarchical clustering of {n} points in {d} dimensions is delegated to scikit-learn (GPU: n >= 2, d <= 16)")
+        return False
+    _device()
+    need = hip.linkage_workspace_bytes(n, d)
+    free, _ = torch.cuda.mem_get_info()
+    if need > LINKAGE_HEADROOM * free:
+        logger.info(f"hierarchical clustering of {n} points needs {need / 2**30:.1f} GiB of device memory, {free / 2**30:.1f} GiB are free: "
+                    "delegated to scikit-learn")
+        return False
+    return True
+
+
+def cluster_data(features: np.ndarray, settings: Dict, initial_centroids: np.ndarray = None, pts: Optional[_DevicePoints] = None,
+                 tree: Optional[Tuple[np.ndarray, np.ndarray]] = None) -> Tuple[np.ndarray, np.ndarray]:
     """Cluster with the algorithm named in `settings` (defaults filled in place, as the reference
-    does, statistics.py:134-142)."""
+    does, statistics.py:134-142).  `tree`: a dendrogram of these points from hierarchical_tree (optimize_clustering
+    builds it once for all k; False = it has decided to delegate to scikit-learn)."""
     settings["algorithm"] = settings.get("algorithm", "kmeans")
     settings["num_clusters"] = settings.get("num_clusters", 10)
     settings["n_init"] = settings.get("n_init", 10)
@@ -195,10 +265,15 @@ def cluster_data(features: np.ndarray, settings: Dict, initial_centroids: np.nda
     if algo == "kmeans":
         return kmeans_clustering(features, settings["num_clusters"], settings["n_init"], initial_centroids, pts=pts)
     if algo == "hierarchical":
-        from sklearn.cluster import AgglomerativeClustering
+        if tree is None and _linkage_on_gpu(features, settings["linkage"]):
+            tree = hierarchical_tree(features, settings["linkage"])
+        if tree:
+            labels = cut_tree(tree[0], settings["num_clusters"])
+        else:
+            from sklearn.cluster import AgglomerativeClustering
 
-        labels = AgglomerativeClustering(n_clusters=settings["num_clusters"], distance_threshold=None,
-                                         linkage=settings["linkage"]).fit_predict(features)
+            labels = AgglomerativeClustering(n_clusters=settings["num_clusters"], distance_threshold=None,
+                                             linkage=settings["linkage"]).fit_predict(features)
         cents = np.stack([features[labels == i].mean(axis=0) for i in range(len(np.unique(labels)))])
         return labels, cents
     if algo == "hdbscan":
@@ -278,8 +353,9 @@ def clustering_scores(features: np.ndarray, labels: np.ndarray, comm: Optional[C
 
 def optimize_clustering(features: np.ndarray, settings: Dict):
     """k in search_interval (inclusive): cluster, Calinski-Harabasz / Davies-Bouldin / silhouette,
-    min-max normalise each list, best (CH - DB + Sil) / 3 (reference :17-110).  The scores stay
-    on scikit-learn (silhouette is O(N^2): SURVEY.md section 8 f4)."""
+    min-max normalise each list, best (CH - DB + Sil) / 3 (reference :17-110).  k-means and the GPU linkages are scored
+    with clustering_scores on points uploaded once; the hierarchical tree is built once and cut for every k.  Only what
+    is delegated to scikit-learn (single linkage, a matrix that does not fit) is scored there too."""
     if settings["algorithm"] in ("kmeans", "hierarchical"):
         from sklearn.metrics import calinski_harabasz_score, davies_bouldin_score, silhouette_score
 
@@ -288,11 +364,17 @@ def optimize_clustering(features: np.ndarray, settings: Dict):
         ch, db, si, results = [], [], [], []
         # k-means: the points go to the GPU once for the whole scan (each k used to upload them twice: clustering, then scores)
         pts = _DevicePoints(features, Comm()) if settings["algorithm"] == "kmeans" else None
+        tree, P_dev = None, pts.P if pts is not None else None
+        if settings["algorithm"] == "hierarchical":
+            tree = False
+            if _linkage_on_gpu(features, settings.get("linkage", "complete")):
+                tree = hierarchical_tree(features, settings.get("linkage", "complete"))
+                P_dev = torch.from_numpy(np.ascontiguousarray(features, dtype=np.float64)).to(_device())
         for N in ks:
             settings["num_clusters"] = N
-            labels, centroids = cluster_data(features, settings, pts=pts)
-            if settings["algorithm"] == "kmeans":   # scores on the GPU (same definitions: clustering_scores)
-                c_, d_, s_ = clustering_scores(features, labels, silhouette_max_points=settings.get("silhouette_max_points"), P_dev=pts.P)
+            labels, centroids = cluster_data(features, settings, pts=pts, tree=tree)
+            if P_dev is not None:   # scores on the GPU (same definitions: clustering_scores)
+                c_, d_, s_ = clustering_scores(features, labels, silhouette_max_points=settings.get("silhouette_max_points"), P_dev=P_dev)
             else:
                 c_, d_, s_ = (calinski_harabasz_score(features, labels), davies_bouldin_score(features, labels),
                               silhouette_score(features, labels))

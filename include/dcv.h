@@ -506,6 +506,26 @@ int dcv_nearest_rows(const double* P_d, int64_t n, int32_t d, const double* cent
 int dcv_nearest_point(const double* train_d, int64_t n_train, const double* sup_d, int64_t n_sup,
                       int32_t d, int64_t* nn_d, void* stream);
 
+/* ---------------------------------------------------------------- hierarchical clustering
+ * Replaces sklearn.cluster.AgglomerativeClustering(linkage = complete | average | ward) as called by
+ * statistics.cluster_data, statistics.py:146-150, i.e. scipy.cluster.hierarchy.linkage(P, method, "euclidean"):
+ * the nearest-neighbour chain over the full float64 distance matrix, with scipy's arithmetic (no fused
+ * multiply-adds, correctly rounded sqrt and division), scan order and tie rules, so that Z_h -- (n - 1) x 4
+ * float64 in scipy's layout: the two merged ids (smaller first, the i-th merge is node n + i), the height, the
+ * size; sorted by height with a stable sort -- EQUALS scipy's.  P (n x d float64 on the device, n >= 2,
+ * 1 <= d <= 16) must be finite.  method: 0 complete, 1 average, 2 ward.  searches_h (may be NULL) receives the
+ * number of row searches the chain ran (at most 3 (n - 1)).  The workspace holds the SQUARE matrix, rows padded
+ * to 16 doubles: 8 n (n + 15) bytes and a little state.  The call synchronises the stream (it reads the merge
+ * counter between blocks of steps and the merges at the end).  DCV_EINVAL: bad arguments -- before anything is
+ * launched -- or a chain that did not finish (non-finite input); DCV_ENOMEM: workspace too small, nothing
+ * launched.  Latency-bound: about 2.8 n chain steps, one launch each (the row update of the previous merge
+ * and the search of one row), 6 - 8 us per step. */
+size_t dcv_linkage_workspace(int64_t n, int32_t d);
+/* the first stage alone (the distance matrix, written into the workspace): what a benchmark times apart */
+int dcv_linkage_pdist(const double* P_d, int64_t n, int32_t d, void* ws_d, size_t ws_bytes, void* stream);
+int dcv_linkage(const double* P_d, int64_t n, int32_t d, int32_t method, double* Z_h, int64_t* searches_h,
+                void* ws_d, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- building block
  * C[M,N] = op(A).op(B) on the FP32 MFMA engine that the covariance and MLP kernels are built
  * from (v_mfma_f32_32x32x2_f32, exact f32 products, f32 accumulation).  mode 0 (NT):
