@@ -197,7 +197,7 @@ static unsigned bn_ew_blocks(int64_t total) {
     return (unsigned)(b > cap ? cap : (b < 1 ? 1 : b));
 }
 
-// ------------------------------------------------------------------ host entry points (used by mlp.hip)
+// ------------------------------------------------------------------ host entry points (used by mlp.hip and mlp_passes.hip)
 // forward of the batch normalisation behind layer l over rows [row0, row0 + rows) of its activation buffer
 int bn_forward(dcv_mlp* m, int l, int64_t row0, int64_t rows, bool train, hipStream_t s) {
     LayerPlan& p = m->layers[l];

@@ -1,4 +1,4 @@
-"""The block engine's grouped validation pass (mlp.hip: eval_group; gemm_kernels.h: gemm_group_kernel): dcv_mlp_eval_steps
+"""The block engine's grouped validation pass (mlp_passes.hip: eval_group; gemm_kernels.h: gemm_group_kernel): dcv_mlp_eval_steps
 evaluates the batches of a pass side by side, one launch per layer with a member per batch, and must append the records
 dcv_mlp_eval_step appends one call at a time -- BIT FOR BIT.  No tolerance appears in this file: every comparison is
 np.array_equal / torch.equal on what the two paths leave behind.  dcv_mlp_last_eval_group() says which path a call took."""
