@@ -69,6 +69,8 @@ struct dcv_mlp {   // created value-initialised (dcv_mlp_create): every member s
     int64_t cur_step;          // step field of the last training forward
     uint32_t drop_rank;        // mixed into the key of the dropout counters (dcv_mlp_set_rank): the ranks of a data-parallel run draw independent masks
     void* snet;                // plan of the fused small-network step (snet.hip) or null
+                               //   (snet / snet_dt are set while their plan is still being built, so that a failed build is released by
+                               //   snet_free / snet_dt_free: non-null does not mean complete until snet_build / snet_dt_build have returned)
     bool snet_tried;           // the plan was attempted once (null afterwards = not applicable)
     float* snet_img;           // zero-padded LDS image of every weight / bias of the fused small-network kernels, kept current by the
     int* snet_img_idx;         //   optimiser (img[img_idx[i]] mirrors params[i]; -1: not part of the image); null until a plan builds it

@@ -1,9 +1,12 @@
 // Pieces shared by the fused small-network kernels (snet.hip: autoencoder step; snet_dt.hip: Deep-TICA forward / backward):
 // the LDS layout of the zero-padded weight images, the v_mfma_f32_16x16x4_f32 tile products with compile-time contraction
-// lengths, the activation helpers.  See snet.hip for the design notes.
+// lengths, the activation helpers; every phase the kernels have in common (weight staging, forward layer, input / weight /
+// bias gradient of a layer) and the host code their plans share (activation map, partials layout, launch).  What is specific
+// to a model stays in its unit.  See snet.hip for the design notes.
 #pragma once
 #include <hip/hip_ext.h>
 #include "mlp_state.h"
+#include <type_traits>
 #include <vector>
 
 namespace dcv {
@@ -139,15 +142,201 @@ __device__ __forceinline__ sv4f snet_actgrad4(int act, sv4f h) {
 
 constexpr int kSnetMaxTiles = 8;   // column tiles of a layer per wave (input gradients are held in registers across a barrier)
 
-#define SNET_NK_SWITCH(nk, CALL)          \
-    switch (nk) {                         \
-        case 1: { CALL(1) } break;        \
-        case 2: { CALL(2) } break;        \
-        case 4: { CALL(4) } break;        \
-        case 8: { CALL(8) } break;        \
-        default: { CALL(16) } break;      \
+// nk (chunks of 16 of a padded width: 1, 2, 4, 8 or 16) as a compile-time constant: f(std::integral_constant<int, NK>)
+template <class F>
+__device__ __forceinline__ void snet_nk_switch(int nk, F&& f) {
+    switch (nk) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        default: f(std::integral_constant<int, 16>{}); break;
     }
+}
 
+// The kernel arguments are 2 KB (one table entry per layer and phase): touch every 64-byte line with a scalar load at the
+// kernel's start, so that the first use of a layer's entry in the forward chain is a scalar-cache hit (measured with the
+// new wave map: 21.2 -> 19.8 us per evaluation step, 48.2 -> 46.7 per training step on the same box).  The caller keeps
+// the result alive up to the end of its staging: asm volatile("" ::"s"(x)).
+template <int BYTES>
+__device__ __forceinline__ unsigned snet_touch_kernargs() {
+    unsigned x = 0;
+    const __attribute__((address_space(4))) unsigned* kp = (const __attribute__((address_space(4))) unsigned*)__builtin_amdgcn_kernarg_segment_ptr();
+#pragma unroll
+    for (int off = 0; off < BYTES; off += 64) x ^= kp[off / 4];
+    return x;
+}
+
+// A thread's place in a workgroup that works on a TR-row tile.  A wave owns a 16-row group and every CG-th column tile:
+// wave -> (row group, column group) with consecutive waves (= the four SIMDs) on different column groups first, so a narrow
+// layer with one or two column tiles keeps one wave on each SIMD instead of two waves on half of them.
+template <int TR>
+struct SnetCoords {
+    static constexpr int RG = TR / 16, CG = kSnetWaves / RG;
+    int t, lane, wave, rg, cg, q, n;
+    __device__ __forceinline__ SnetCoords()
+        : t(threadIdx.x), lane(t & 63), wave(t >> 6), rg(wave % RG), cg(wave / RG), q(lane >> 4), n(lane & 15) {}
+};
+
+// Table-driven staging of the entries [first, n) of the plan's staging table (snet_layout) into LDS, zero padding included:
+// one flat space of 16-byte units over all layers, twelve independent loads in flight per thread and pass.  The table entries
+// of pass p + 1 are requested behind the data loads of pass p and arrive in the same round trip: one dependent round trip per
+// pass (+ the first table read) instead of two (round 4: 8 -> 5 for the C2 network's four passes).  Per-layer loops cost one
+// L2 round trip per pass (8-11 us).
+// hook(): the caller's ride-along loads, called in EVERY pass (the caller keeps its own "issued" flag) -- ahead of the pass's
+// data loads (HOOK_FIRST: loads return in order, so what must not wait for the data goes first) or behind them (issued
+// earlier, cold rows of X would hold up the table entries; behind, they ride along the data round trip).  Only the lanes with
+// an entry left take the last pass: nothing wave-wide belongs in the hook.
+template <int NT, bool HOOK_FIRST, class Hook>
+__device__ __forceinline__ void snet_stage_table(const int2* tab, int first, int n, const float* params, float* sl, int t, Hook&& hook) {
+    int2 e[12];
+#pragma unroll
+    for (int u = 0; u < 12; ++u) {
+        const int i = first + t + NT * u;
+        e[u] = i < n ? tab[i] : make_int2(-1, -1);
+    }
+    for (int i0 = first + t; i0 < n; i0 += 12 * NT) {
+        float4 v[12];
+        if (HOOK_FIRST) hook();
+#pragma unroll
+        for (int u = 0; u < 12; ++u) {
+            v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (e[u].x >= 0) {
+                const float* src = params + e[u].x;
+                const int nv = (e[u].y >> 20) & 7;
+                if ((e[u].y >> 24) & 1) {
+                    v[u] = *reinterpret_cast<const float4*>(src);
+                } else {
+                    v[u].x = src[0];
+                    if (nv > 1) v[u].y = src[1];
+                    if (nv > 2) v[u].z = src[2];
+                    if (nv > 3) v[u].w = src[3];
+                }
+            }
+        }
+        if (!HOOK_FIRST) hook();
+        int2 en[12];
+#pragma unroll
+        for (int u = 0; u < 12; ++u) {
+            const int i = i0 + 12 * NT + NT * u;
+            en[u] = i < n ? tab[i] : make_int2(-1, -1);
+        }
+#pragma unroll
+        for (int u = 0; u < 12; ++u)
+            if (e[u].y >= 0) *reinterpret_cast<float4*>(sl + (e[u].y & 0xFFFFF)) = v[u];
+#pragma unroll
+        for (int u = 0; u < 12; ++u) e[u] = en[u];
+    }
+}
+
+// Forward of one layer over the tile: Hout = act(Hin W^T + b), padding columns zero.  epilogue(h, col) sees this lane's four
+// rows (rg * 16 + 4 q + v) of column col before they are stored (the autoencoder turns its last layer's output into dZ_L there).
+template <int TR, class Epilogue>
+__device__ __forceinline__ void snet_forward_layer(const SnetCoords<TR>& k, const SnetLayer& y, const float* sl, const float* Hin, int psin,
+                                                   float* Hout, int pso, Epilogue&& epilogue) {
+    const float* ap = Hin + (k.rg * 16 + k.n) * psin + 4 * k.q;
+    const float* W = sl + y.lw + k.n * y.pws + 4 * k.q;
+    snet_nk_switch(y.nk_in, [&](auto nk) {
+        constexpr int NK = decltype(nk)::value;
+        SnetFrags<NK> A;
+        A.load(ap);
+        for (int ct = k.cg; ct < y.nk_out; ct += SnetCoords<TR>::CG) {
+            const sv4f acc = snet_fwd_tile<NK>(A, W + ct * 16 * y.pws);
+            const int col = ct * 16 + k.n;
+            const float bias = sl[y.lb + col];
+            sv4f h = snet_act4(y.act, acc + bias);
+            if (col >= y.out) h = sv4f{0.f, 0.f, 0.f, 0.f};
+            epilogue(h, col);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) Hout[(k.rg * 16 + 4 * k.q + v) * pso + col] = h[v];
+        }
+    });
+}
+
+// Input gradient of one layer, kept in registers: dg[j] = this wave's rows of dZ W, column tile cg + j * CG
+template <int TR>
+__device__ __forceinline__ void snet_dgrad_layer(const SnetCoords<TR>& k, const SnetLayer& y, const float* sl, const float* dZ, int psz,
+                                                 sv4f (&dg)[kSnetMaxTiles]) {
+    const float* ap = dZ + (k.rg * 16 + k.n) * psz + 4 * k.q;
+    const float* W = sl + y.lw + (4 * k.q) * y.pws + k.n;
+    snet_nk_switch(y.nk_out, [&](auto nk) {
+        constexpr int NK = decltype(nk)::value;
+        SnetFrags<NK> A;
+        A.load(ap);
+#pragma unroll
+        for (int j = 0; j < kSnetMaxTiles; ++j) {
+            const int it = k.cg + j * SnetCoords<TR>::CG;
+            if (it < y.nk_in) dg[j] = snet_dgrad_tile<NK>(A, W + it * 16, y.pws);
+        }
+    });
+}
+
+// Weight gradient of the tile into this workgroup's partial: the nk_out x nk_in tiles round-robin over the waves.
+// Hw [TR][psw]: the input of this Linear, dZ [TR][psz]: the gradient of its output.
+template <int TR>
+__device__ __forceinline__ void snet_wgrad_partials(const SnetCoords<TR>& k, const SnetLayer& y, float* part, const float* Hw, int psw,
+                                                    const float* dZ, int psz) {
+    const int nti = y.nk_in, ntot = y.nk_out * nti;
+    float* pw = part + y.pw_off + (int64_t)blockIdx.x * y.pw_stride;
+    const bool vec_ok = (y.in & 3) == 0 && ((y.pw_off + (int64_t)blockIdx.x * y.pw_stride) & 3) == 0;   // part is a hipMalloc base
+    int ot = 0, it = k.wave;
+    while (it >= nti) { it -= nti; ++ot; }
+#pragma unroll 2
+    for (int tile = k.wave; tile < ntot; tile += kSnetWaves) {
+        // operands swapped (rows of the MFMA tile = input columns): a lane ends up with four CONSECUTIVE inputs
+        // i of one output o = its 16 bytes of the partial's row -- one global_store_dwordx4 per tile and lane
+        // instead of four 4-byte stores (the partial stores of the two wide layers were what these phases waited on)
+        const sv4f acc = snet_wgrad_tile<TR>(Hw + k.q * psw + it * 16 + k.n, psw, dZ + k.q * psz + ot * 16 + k.n, psz);
+        const int o = ot * 16 + k.n, i0 = it * 16 + 4 * k.q;
+        if (o < y.out) {
+            float* dst = pw + (int64_t)o * y.in + i0;
+            if (vec_ok && i0 + 4 <= y.in) {
+                handoff_store16(dst, acc);   // write-through: the 10 MB of partials are not left for the write-back at the launch's end (44.3 -> 42.8 us per step)
+            } else {
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                    if (i0 + v < y.in) dst[v] = acc[v];
+            }
+        }
+        it += kSnetWaves;
+        while (it >= nti) { it -= nti; ++ot; }
+    }
+}
+// Bias gradient into this workgroup's partial: column sums of dZ_l over the tile's rows, rows in index order
+// (four threads per column, a quarter of the rows each, combined by two shuffles: a fixed order)
+template <int TR>
+__device__ __forceinline__ void snet_bgrad_partials(const SnetCoords<TR>& k, const SnetLayer& y, float* part, const float* dZ, int psz) {
+    for (int o4 = k.t; o4 < 4 * y.pout; o4 += kSnetThreads) {
+        const int o = o4 >> 2, quarter = o4 & 3;
+        float s = 0.f;
+#pragma unroll
+        for (int r = 0; r < TR / 4; ++r) s += dZ[(quarter * (TR / 4) + r) * psz + o];
+        s += __shfl_xor(s, 1, 64);
+        s += __shfl_xor(s, 2, 64);
+        if (quarter == 0 && o < y.out) part[y.pb_off + (int64_t)blockIdx.x * y.pb_stride + o] = s;
+    }
+}
+
+// dZ_{l-1} = dg * act'(H_l) written over H_l [TR][psh] (every wave is done reading it), zeros in the padding columns;
+// y: layer l, act_prev / out_prev: activation and width of layer l - 1
+template <int TR>
+__device__ __forceinline__ void snet_dz_prev(const SnetCoords<TR>& k, const SnetLayer& y, int act_prev, int out_prev, float* Hin, int psh,
+                                             const sv4f (&dg)[kSnetMaxTiles]) {
+#pragma unroll
+    for (int j = 0; j < kSnetMaxTiles; ++j) {
+        const int it = k.cg + j * SnetCoords<TR>::CG;
+        if (it < y.nk_in) {
+            const int col = it * 16 + k.n;
+            float* p = Hin + (k.rg * 16 + 4 * k.q) * psh + col;
+            sv4f h;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) h[v] = p[v * psh];
+            const sv4f dh = snet_actgrad4(act_prev, h);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) p[v * psh] = col < out_prev ? dg[j][v] * dh[v] : 0.f;
+        }
+    }
+}
 
 // Layer table + staging table of a network whose weight images all live in one CU's LDS.  Every width is padded to
 // 16 * 2^j (compile-time contraction lengths); weight image [pout][pin + 4] (conflict-free 128-bit fragment reads), then the
@@ -215,6 +404,94 @@ __device__ __forceinline__ void snet_stage_image(const float* __restrict__ img, 
         const unsigned ldsw = lds_addr_uniform(sl + 4 * ub);
         if (u < u1) glds16(img + 4 * u, ldsw);
     }
+}
+
+// ---- host side of the fused small-network plans
+
+// Activation map of a TR-row tile: H_0 .. H_L from LDS float f on, row stride = padded width + 4 (H_0 = the input tile);
+// returns the first float behind H_L
+inline int snet_act_map(const SnetLayer* ly, int L, int TR, int f, int* lh, int* ps) {
+    for (int l = 0; l <= L; ++l) {
+        const int P = l == 0 ? ly[0].pin : ly[l - 1].pout;
+        ps[l] = P + 4;
+        lh[l] = f;
+        f += TR * (P + 4);
+    }
+    return f;
+}
+
+// Where the nwg workgroups of a launch leave their gradient partials in `part` (16-byte aligned items: vector stores in the
+// kernels, vector loads in the reduction), and the reduction's descriptors of them
+inline void snet_partials_layout(SnetLayer* ly, int L, int64_t nwg, float* part, ReduceArgsView* ra) {
+    int64_t off = 0;
+    for (int l = 0; l < L; ++l) {
+        SnetLayer& y = ly[l];
+        y.pw_off = off; off += nwg * (int64_t)y.pw_stride;
+        y.pb_off = off; off += nwg * (int64_t)y.pb_stride;
+        if (ra) {
+            ra->slab[l] = part + y.pw_off;
+            ra->bpart[l] = part + y.pb_off;
+            ra->splits[l] = (int)nwg;
+            ra->bblocks[l] = (int)nwg;
+            ra->wstride[l] = y.pw_stride;
+            ra->bstride[l] = y.pb_stride;
+        }
+    }
+}
+
+// A device buffer of at least `need` elements (contents are not kept when it grows)
+template <class T>
+inline bool snet_grow(T** p, int64_t* have, int64_t need) {
+    if (*have >= need) return true;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    if (hipMalloc(reinterpret_cast<void**>(p), (size_t)need * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    *have = need;
+    return true;
+}
+
+// Device copy of the staging table; on failure the caller releases *dev with the rest of its plan
+inline bool snet_upload_table(const std::vector<int2>& tab, int2** dev) {
+    if (hipMalloc(reinterpret_cast<void**>(dev), tab.size() * sizeof(int2)) == hipSuccess &&
+        hipMemcpy(*dev, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice) == hipSuccess)
+        return true;
+    (void)hipGetLastError();
+    return false;
+}
+
+// "Build the plan on first use": true when `plan` is there or `build` has just made it; one attempt per engine
+template <class Build>
+inline bool snet_plan_ready(const void* plan, bool& tried, Build&& build) {
+    if (plan != nullptr) return true;
+    const bool built = !tried && build();
+    tried = true;
+    return built;
+}
+
+// Launch of a fused kernel with up to lds_max bytes of dynamic LDS.  attr_state, one per kernel instantiation: 0 unknown,
+// 1 the attribute is set, -1 refused by the runtime (the fused form is then off: returns 1)
+template <class K, class Args>
+inline int snet_launch(K kern, int& attr_state, size_t lds_max, size_t lds_bytes, const Args& a, int64_t nwg, hipStream_t s) {
+    if (attr_state == 0) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
+        if (e != hipSuccess) (void)hipGetLastError();
+        attr_state = e == hipSuccess ? 1 : -1;
+    }
+    if (attr_state < 0) return 1;
+    if (g_launch_ev.start != nullptr) {   // a profiled launch: events stamped with the kernel's own begin / end (common.h)
+        const LaunchEvents ev = g_launch_ev;
+        g_launch_ev = LaunchEvents{};
+        g_launch_taken = ev.start;
+        hipExtLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(kSnetThreads), (uint32_t)lds_bytes, s, ev.start, ev.stop, 0u, a);
+    } else {
+        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(kSnetThreads), lds_bytes, s, a);
+    }
+    DCV_CHECK_LAUNCH();
+    return DCV_OK;
 }
 
 inline bool snet_disabled() {

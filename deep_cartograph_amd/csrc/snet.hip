@@ -68,23 +68,11 @@ struct SnetArgs {
 template <int TR, bool VAE>
 __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
     constexpr int NT = kSnetThreads;
-    constexpr int RG = TR / 16, CG = kSnetWaves / RG;
     extern __shared__ __attribute__((aligned(16))) float sl[];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    // wave -> (row group, column group): consecutive waves (= the four SIMDs) take different column groups first, so a narrow
-    // layer with one or two column tiles keeps one wave on each SIMD instead of two waves on half of them
-    const int rg = wave % RG, cg = wave / RG;
-    const int q = lane >> 4, n = lane & 15;
+    const SnetCoords<TR> k;
+    const int t = k.t, lane = k.lane, wave = k.wave;
     const int L = a.L;
-    // the kernel arguments are 2 KB (one table entry per layer and phase): touch every 64-byte line with a scalar load now, so
-    // that the first use of a layer's entry in the forward chain is a scalar-cache hit (measured with the new wave map:
-    // 21.2 -> 19.8 us per evaluation step, 48.2 -> 46.7 per training step on the same box)
-    unsigned ka_touch = 0;
-    {
-        const __attribute__((address_space(4))) unsigned* kp = (const __attribute__((address_space(4))) unsigned*)__builtin_amdgcn_kernarg_segment_ptr();
-#pragma unroll
-        for (int off = 0; off < (int)sizeof(SnetArgs); off += 64) ka_touch ^= kp[off / 4];
-    }
+    const unsigned ka_touch = snet_touch_kernargs<(int)sizeof(SnetArgs)>();
     SNET_STAMP(0);
     // ---- input tile H_0 (rows past the batch: zeros): with 16-byte loads the whole tile is at most four units per thread
     //      (TR * pin / 4 <= 4 * NT); they are issued inside the weight staging, behind its data loads, and written to LDS
@@ -105,64 +93,9 @@ __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
     const int x_sh = a.l[0].c4_shift, x_tot = TR << x_sh;
     float4 xv[4];
     bool x_issued = false;
-    // ---- stage every weight image and bias (zero-padded, row stride pin + 4) through the plan's staging table: one flat
-    //      space of 16-byte units over all layers, twelve independent loads in flight per thread and pass -- two dependent
-    //      round trips in all (table entry, then data).  Per-layer loops cost one L2 round trip per pass (8-11 us).
-    if (a.img != nullptr) {
-        // one contiguous LDS-DMA copy of the whole weight image (kept current by the optimiser: OptArgs::img); the input rows
-        // are requested right behind it
-        snet_stage_image<NT>(a.img, sl, 0, a.img_floats, t);
-    } else {
-        // the table entries of pass p + 1 are requested behind the data loads of pass p and arrive in the same round trip: one
-        // dependent round trip per pass (+ the first table read) instead of two (round 4: 8 -> 5 for the C2 network's four passes)
-        int2 e[12];
-    #pragma unroll
-        for (int u = 0; u < 12; ++u) {
-            const int i = t + NT * u;
-            e[u] = i < a.stage_n ? a.stage_tab[i] : make_int2(-1, -1);
-        }
-        for (int i0 = t; i0 < a.stage_n; i0 += 12 * NT) {
-            float4 v[12];
-    #pragma unroll
-            for (int u = 0; u < 12; ++u) {
-                v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (e[u].x >= 0) {
-                    const float* src = a.params + e[u].x;
-                    const int nv = (e[u].y >> 20) & 7;
-                    if ((e[u].y >> 24) & 1) {
-                        v[u] = *reinterpret_cast<const float4*>(src);
-                    } else {
-                        v[u].x = src[0];
-                        if (nv > 1) v[u].y = src[1];
-                        if (nv > 2) v[u].z = src[2];
-                        if (nv > 3) v[u].w = src[3];
-                    }
-                }
-            }
-            if (x_vec && !x_issued) {   // behind the first pass's data loads (loads return in order: issued earlier, the cold
-                x_issued = true;        // rows of X would hold up the table entries; here they ride along the data round trip)
-                const int f4 = F0 >> 2;
-    #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int i = t + NT * u, r = i >> x_sh, c = i - (r << x_sh);
-                    xv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (i < x_tot && r0 + r < a.R && c < f4) xv[u] = *reinterpret_cast<const float4*>(a.Xn + rows.template get<true>(r0 + r) * a.ld + 4 * c);
-                }
-            }
-            int2 en[12];
-    #pragma unroll
-            for (int u = 0; u < 12; ++u) {
-                const int i = i0 + 12 * NT + NT * u;
-                en[u] = i < a.stage_n ? a.stage_tab[i] : make_int2(-1, -1);
-            }
-    #pragma unroll
-            for (int u = 0; u < 12; ++u)
-                if (e[u].y >= 0) *reinterpret_cast<float4*>(sl + (e[u].y & 0xFFFFF)) = v[u];
-    #pragma unroll
-            for (int u = 0; u < 12; ++u) e[u] = en[u];
-        }
-    }
-    if (x_vec && !x_issued) {   // (a plan without staging units: not reachable, kept for the invariant xv is loaded)
+    auto issue_x = [&]() {
+        if (!x_vec || x_issued) return;
+        x_issued = true;
         const int f4 = F0 >> 2;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -170,7 +103,17 @@ __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
             xv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (i < x_tot && r0 + r < a.R && c < f4) xv[u] = *reinterpret_cast<const float4*>(a.Xn + rows.template get<true>(r0 + r) * a.ld + 4 * c);
         }
+    };
+    // ---- stage every weight image and bias (zero-padded, row stride pin + 4)
+    if (a.img != nullptr) {
+        // one contiguous LDS-DMA copy of the whole weight image (kept current by the optimiser: OptArgs::img); the input rows
+        // are requested right behind it
+        snet_stage_image<NT>(a.img, sl, 0, a.img_floats, t);
+    } else {
+        // through the plan's staging table, the input rows behind the first pass's data loads
+        snet_stage_table<NT, false>(a.stage_tab, 0, a.stage_n, a.params, sl, t, issue_x);
     }
+    issue_x();   // (behind the image copy; after the table: a plan without staging units, not reachable, kept for the invariant xv is loaded)
     asm volatile("" ::"s"(ka_touch));   // the touches have landed
     if (a.img != nullptr) vm_wait<0>();   // the image copies of this wave have landed (the barrier below covers the other waves)
     SNET_STAMP(1);
@@ -216,36 +159,24 @@ __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
         float* Hout = sl + a.lh[l + 1];
         const int psin = VAE && l == a.vae_l ? a.pz : a.ps[l], pso = a.ps[l + 1];
         const bool last = l == L - 1;
-        const float* ap = Hin + (rg * 16 + n) * psin + 4 * q;
-        const float* W = sl + y.lw + n * y.pws + 4 * q;
-        const float* H0row = sl + a.lh[0] + (rg * 16 + 4 * q) * a.ps[0];
-#define SNET_FWD(NK)                                                                                                        \
-        SnetFrags<NK> A;                                                                                                     \
-        A.load(ap);                                                                                                          \
-        for (int ct = cg; ct < y.nk_out; ct += CG) {                                                                         \
-            const sv4f acc = snet_fwd_tile<NK>(A, W + ct * 16 * y.pws);                                                      \
-            const int col = ct * 16 + n;                                                                                     \
-            const float bias = sl[y.lb + col];                                                                               \
-            sv4f h = snet_act4(y.act, acc + bias);                                                                           \
-            if (col >= y.out) h = sv4f{0.f, 0.f, 0.f, 0.f};                                                                  \
-            if (last) {   /* autoencoder loss on the spot: e = (y - xn) * range ; dY = scale * (y - xn) * range^2 * act'(y) */ \
-                const float rgv = col < y.out ? a.range[col] : 0.f;                                                          \
-                const sv4f dh = snet_actgrad4(y.act, h);                                                                     \
-                _Pragma("unroll") for (int v = 0; v < 4; ++v) {                                                              \
-                    float g = 0.f;                                                                                           \
-                    if (col < y.out && r0 + rg * 16 + 4 * q + v < a.R) {                                                     \
-                        const float x = H0row[v * a.ps[0] + col];                                                            \
-                        const float ev = (h[v] - x) * rgv;                                                                   \
-                        sse += (double)ev * (double)ev;                                                                      \
-                        g = a.scale * (h[v] - x) * rgv * rgv * dh[v];                                                        \
-                    }                                                                                                        \
-                    h[v] = g;   /* H_L now holds dZ_L */                                                                     \
-                }                                                                                                            \
-            }                                                                                                                \
-            _Pragma("unroll") for (int v = 0; v < 4; ++v) Hout[(rg * 16 + 4 * q + v) * pso + col] = h[v];                    \
-        }
-        SNET_NK_SWITCH(y.nk_in, SNET_FWD)
-#undef SNET_FWD
+        const float* H0row = sl + a.lh[0] + (k.rg * 16 + 4 * k.q) * a.ps[0];
+        snet_forward_layer<TR>(k, y, sl, Hin, psin, Hout, pso, [&](sv4f& h, int col) {
+            if (!last) return;
+            // autoencoder loss on the spot: e = (y - xn) * range ; dY = scale * (y - xn) * range^2 * act'(y)
+            const float rgv = col < y.out ? a.range[col] : 0.f;
+            const sv4f dh = snet_actgrad4(y.act, h);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                float g = 0.f;
+                if (col < y.out && r0 + k.rg * 16 + 4 * k.q + v < a.R) {
+                    const float x = H0row[v * a.ps[0] + col];
+                    const float ev = (h[v] - x) * rgv;
+                    sse += (double)ev * (double)ev;
+                    g = a.scale * (h[v] - x) * rgv * rgv * dh[v];
+                }
+                h[v] = g;   // H_L now holds dZ_L
+            }
+        });
         __syncthreads();
         SNET_STAMP(3 + l);
     }
@@ -287,60 +218,11 @@ __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
             const int psw = VAE && l == a.vae_l ? a.pz : psh;
             // input gradient first, kept in registers
             sv4f dg[kSnetMaxTiles];
-            if (l > 0) {
-                const float* ap = dZ + (rg * 16 + n) * psz + 4 * q;
-                const float* W = sl + y.lw + (4 * q) * y.pws + n;
-#define SNET_DGRAD(NK)                                                                                   \
-                SnetFrags<NK> A;                                                                         \
-                A.load(ap);                                                                              \
-                _Pragma("unroll") for (int j = 0; j < kSnetMaxTiles; ++j) {                              \
-                    const int it = cg + j * CG;                                                          \
-                    if (it < y.nk_in) dg[j] = snet_dgrad_tile<NK>(A, W + it * 16, y.pws);                \
-                }
-                SNET_NK_SWITCH(y.nk_out, SNET_DGRAD)
-#undef SNET_DGRAD
-            }
+            if (l > 0) snet_dgrad_layer<TR>(k, y, sl, dZ, psz, dg);
             SNET_STAMP(40 + l);
-            // weight gradient of the tile: the nk_out x nk_in tiles round-robin over the waves
-            {
-                const int nti = y.nk_in, ntot = y.nk_out * nti;
-                float* pw = a.part + y.pw_off + (int64_t)blockIdx.x * y.pw_stride;
-                const bool vec_ok = (y.in & 3) == 0 && ((y.pw_off + (int64_t)blockIdx.x * y.pw_stride) & 3) == 0;   // a.part is a hipMalloc base
-                int ot = 0, it = wave;
-                while (it >= nti) { it -= nti; ++ot; }
-#pragma unroll 2
-                for (int tile = wave; tile < ntot; tile += kSnetWaves) {
-                    // operands swapped (rows of the MFMA tile = input columns): a lane ends up with four CONSECUTIVE inputs
-                    // i of one output o = its 16 bytes of the partial's row -- one global_store_dwordx4 per tile and lane
-                    // instead of four 4-byte stores (the partial stores of the two wide layers were what these phases waited on)
-                    const sv4f acc = snet_wgrad_tile<TR>(Hw + q * psw + it * 16 + n, psw, dZ + q * psz + ot * 16 + n, psz);
-                    const int o = ot * 16 + n, i0 = it * 16 + 4 * q;
-                    if (o < y.out) {
-                        float* dst = pw + (int64_t)o * y.in + i0;
-                        if (vec_ok && i0 + 4 <= y.in) {
-                            handoff_store16(dst, acc);   // write-through: the 10 MB of partials are not left for the write-back at the launch's end (44.3 -> 42.8 us per step)
-                        } else {
-#pragma unroll
-                            for (int v = 0; v < 4; ++v)
-                                if (i0 + v < y.in) dst[v] = acc[v];
-                        }
-                    }
-                    it += kSnetWaves;
-                    while (it >= nti) { it -= nti; ++ot; }
-                }
-                SNET_STAMP(48 + l);
-                // bias gradient: column sums of dZ_l over the tile's rows, rows in index order
-                // (four threads per column, a quarter of the rows each, combined by two shuffles: a fixed order)
-                for (int o4 = t; o4 < 4 * y.pout; o4 += NT) {
-                    const int o = o4 >> 2, part = o4 & 3;
-                    float s = 0.f;
-#pragma unroll
-                    for (int r = 0; r < TR / 4; ++r) s += dZ[(part * (TR / 4) + r) * psz + o];
-                    s += __shfl_xor(s, 1, 64);
-                    s += __shfl_xor(s, 2, 64);
-                    if (part == 0 && o < y.out) a.part[y.pb_off + (int64_t)blockIdx.x * y.pb_stride + o] = s;
-                }
-            }
+            snet_wgrad_partials<TR>(k, y, a.part, Hw, psw, dZ, psz);
+            SNET_STAMP(48 + l);
+            snet_bgrad_partials<TR>(k, y, a.part, dZ, psz);
             SNET_STAMP(21 + 2 * l);
             if (l == 0) break;
             __syncthreads();   // every wave is done reading H_l
@@ -352,19 +234,21 @@ __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
                 const float* ep = a.eps + ((int64_t)bj * a.R + r0) * d;
 #pragma unroll
                 for (int j = 0; j < kSnetMaxTiles; ++j) {
-                    const int it = cg + j * CG;
+                    const int it = k.cg + j * SnetCoords<TR>::CG;
                     if (it < y.nk_in) {
-                        const int col = it * 16 + n;
-                        float* p = Hin + (rg * 16 + 4 * q) * psh + col;
+                        const int col = it * 16 + k.n;
+                        float* p = Hin + (k.rg * 16 + 4 * k.q) * psh + col;
 #pragma unroll
                         for (int v = 0; v < 4; ++v) {
-                            const int r = rg * 16 + 4 * q + v;
+                            const int r = k.rg * 16 + 4 * k.q + v;
                             if (col < d) {
                                 float gm = 0.f, gl = 0.f;
                                 if (r0 + r < a.R) {
                                     const float mu = p[v * psh], lv = p[v * psh + d], e = ep[r * d + col], dz = dg[j][v];
-                                    gm = dz + a.beta_b * mu;
-                                    gl = dz * e * 0.5f * expf(0.5f * lv) + a.beta_b * 0.5f * (expf(lv) - 1.f);
+                                    // the roundings spelt out (as for z above): left to the compiler, WHICH of gl's two products
+                                    // is fused into the sum changes with the code around it, and with it the last bit
+                                    gm = __fmaf_rn(a.beta_b, mu, dz);
+                                    gl = __fmaf_rn(a.beta_b * 0.5f, expf(lv) - 1.f, __fmul_rn(dz * e * 0.5f, expf(0.5f * lv)));
                                 }
                                 p[v * psh] = gm;
                                 p[v * psh + d] = gl;
@@ -377,20 +261,7 @@ __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
                 __syncthreads();
                 continue;
             }
-#pragma unroll
-            for (int j = 0; j < kSnetMaxTiles; ++j) {
-                const int it = cg + j * CG;
-                if (it < y.nk_in) {
-                    const int col = it * 16 + n;
-                    float* p = Hin + (rg * 16 + 4 * q) * psh + col;
-                    sv4f h;
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) h[v] = p[v * psh];
-                    const sv4f dh = snet_actgrad4(act_prev, h);
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) p[v * psh] = col < out_prev ? dg[j][v] * dh[v] : 0.f;
-                }
-            }
+            snet_dz_prev<TR>(k, y, act_prev, out_prev, Hin, psh, dg);
             __syncthreads();
         }
     }
@@ -470,14 +341,9 @@ struct SnetPlan {
 // Activation map of a TR-row tile behind the weight images (H_0 .. H_L, the reduction scratch); returns the LDS bytes, 0 when
 // the tile does not fit
 static size_t snet_ae_map(SnetArgs& a, int L, int fl, int TR) {
-    int f = fl;
-    for (int l = 0; l <= L; ++l) {
-        const int P = l == 0 ? a.l[0].pin : a.l[l - 1].pout;
-        if (l > 0 && l < L && a.l[l].pin != P) return 0;   // (always equal: both pad the same width)
-        a.ps[l] = P + 4;
-        a.lh[l] = f;
-        f += TR * (P + 4);
-    }
+    for (int l = 1; l < L; ++l)
+        if (a.l[l].pin != a.l[l - 1].pout) return 0;   // (always equal: both pad the same width)
+    int f = snet_act_map(a.l, L, TR, fl, a.lh, a.ps);
     if (a.vae_l >= 0) {   // the z tile: the decoder's input, apart from the heads' output it is sampled from
         a.pz = a.l[a.vae_l].pin + 4;
         a.lz = f;
@@ -507,80 +373,43 @@ static int snet_ae_pick_tr(const SnetPlan* pl, int64_t R) {
 // in LDS with at least 16-row tiles.
 static bool snet_build(dcv_mlp* m) {
     if ((m->desc.model != DCV_MODEL_AE && m->desc.model != DCV_MODEL_VAE) || m->any_drop || snet_disabled()) return false;
-    SnetPlan* pl = new (std::nothrow) SnetPlan();
+    SnetPlan* pl = new (std::nothrow) SnetPlan();   // value-initialised: no buffer yet
     if (!pl) return false;
+    m->snet = pl;   // from here on a half-built plan is released by snet_free
     SnetArgs& a = pl->base;
     a.L = m->L;
     a.vae_l = m->vae_d > 0 ? m->desc.latent_layer : -1;
     a.vae_d = m->vae_d;
-    a.lz = a.pz = 0;
-    pl->kl_part = nullptr;
-    if (m->vae_d > 0 && hipMalloc(reinterpret_cast<void**>(&pl->kl_part), (size_t)kEvalWorkgroupsPerLaunch * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        delete pl;
+    auto fail = [&] {
+        snet_free(m);
         return false;
-    }
-    int fl = 0;
-    int64_t per_wg = 0;
+    };
+    int64_t kl_n = 0, stamps_n = 0;
+    if (m->vae_d > 0 && !snet_grow(&pl->kl_part, &kl_n, kEvalWorkgroupsPerLaunch)) return fail();
     std::vector<int2> tab;
-    if (!snet_layout(m, a.l, tab, nullptr, fl, per_wg)) {
-        if (pl->kl_part) (void)hipFree(pl->kl_part);
-        delete pl;
-        return false;
-    }
-    pl->per_wg = per_wg;
+    if (!snet_layout(m, a.l, tab, nullptr, pl->fl, pl->per_wg)) return fail();
     (void)snet_image_build(m);   // on failure the kernels keep the table-driven staging
-    pl->stage_tab = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&pl->stage_tab), tab.size() * sizeof(int2)) != hipSuccess ||
-        hipMemcpy(pl->stage_tab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        if (pl->stage_tab) (void)hipFree(pl->stage_tab);
-        if (pl->kl_part) (void)hipFree(pl->kl_part);
-        delete pl;
-        return false;
-    }
+    if (!snet_upload_table(tab, &pl->stage_tab)) return fail();
     a.stage_tab = pl->stage_tab;
     a.stage_n = (int)tab.size();
-    pl->fl = fl;
-    pl->tr_max = 0;
     for (int TR : {32, 16}) {
         SnetArgs tmp = a;
-        if (snet_ae_map(tmp, m->L, fl, TR) != 0) {
+        if (snet_ae_map(tmp, m->L, pl->fl, TR) != 0) {
             pl->tr_max = TR;
             break;
         }
     }
-    if (pl->tr_max != 0) {
-        pl->part = nullptr;
-        pl->part_floats = 0;
-        pl->stamps = nullptr;
-        pl->ev_sse = nullptr;
-        pl->ev_sse_n = 0;
-        pl->ev_ticket = nullptr;
-        pl->ev_ticket_n = 0;
-        pl->last_tr = 0;
-        // batched validation passes: partials and tickets for the bounds of dcv_mlp_eval_steps (33 KB); without them the
-        // passes go batch by batch
-        if (hipMalloc(reinterpret_cast<void**>(&pl->ev_sse), (size_t)kEvalWorkgroupsPerLaunch * sizeof(double)) == hipSuccess &&
-            hipMalloc(reinterpret_cast<void**>(&pl->ev_ticket), (size_t)(kEvalBatchesPerLaunch + 1) * sizeof(unsigned)) == hipSuccess &&
-            hipMemset(pl->ev_ticket, 0, (size_t)(kEvalBatchesPerLaunch + 1) * sizeof(unsigned)) == hipSuccess) {
-            pl->ev_sse_n = kEvalWorkgroupsPerLaunch;
-            pl->ev_ticket_n = kEvalBatchesPerLaunch + 1;
-        } else {
-            (void)hipGetLastError();
-        }
-        {
-            const char* e = getenv("DCV_SNET_STAMPS");
-            if (e && e[0] == '1' && hipMalloc(reinterpret_cast<void**>(&pl->stamps), 64 * sizeof(unsigned long long)) == hipSuccess)
-                (void)hipMemset(pl->stamps, 0, 64 * sizeof(unsigned long long));
-        }
-        m->snet = pl;
-        return true;
+    if (pl->tr_max == 0) return fail();
+    // batched validation passes: partials and tickets for the bounds of dcv_mlp_eval_steps (33 KB); without them the
+    // passes go batch by batch
+    if (!snet_grow(&pl->ev_sse, &pl->ev_sse_n, kEvalWorkgroupsPerLaunch) || !snet_grow(&pl->ev_ticket, &pl->ev_ticket_n, (int64_t)kEvalBatchesPerLaunch + 1) ||
+        hipMemset(pl->ev_ticket, 0, (size_t)pl->ev_ticket_n * sizeof(unsigned)) != hipSuccess) {
+        (void)hipGetLastError();
+        pl->ev_sse_n = pl->ev_ticket_n = 0;   // (the buffers go with the plan)
     }
-    (void)hipFree(pl->stage_tab);
-    if (pl->kl_part) (void)hipFree(pl->kl_part);
-    delete pl;
-    return false;
+    const char* e = getenv("DCV_SNET_STAMPS");
+    if (e && e[0] == '1' && snet_grow(&pl->stamps, &stamps_n, 64)) (void)hipMemset(pl->stamps, 0, 64 * sizeof(unsigned long long));
+    return true;
 }
 
 // ---- the global weight image: every weight / bias at its LDS-image offset, zero padding included, kept current by the
@@ -662,13 +491,7 @@ int snet_ae_last_tile_rows(const dcv_mlp* m) {
 // Rows per workgroup the fused autoencoder kernel takes for batches of R rows (R = 0: its largest tile); the plan is built on
 // first use; 0: the fused form does not apply.
 int snet_ae_tile_rows(dcv_mlp* m, int64_t R) {
-    if (m->snet == nullptr) {
-        if (m->snet_tried || !snet_build(m)) {
-            m->snet_tried = true;
-            return 0;
-        }
-        m->snet_tried = true;
-    }
+    if (!snet_plan_ready(m->snet, m->snet_tried, [&] { return snet_build(m); })) return 0;
     const SnetPlan* pl = static_cast<SnetPlan*>(m->snet);
     return R > 0 ? snet_ae_pick_tr(pl, R) : pl->tr_max;
 }
@@ -691,33 +514,11 @@ int snet_ae_step(dcv_mlp* m, const float* Xn_d, int64_t ld, const RowMap& rm, in
     if (nb > 1 && (nwg > pl->ev_sse_n || nb + 1 > pl->ev_ticket_n)) return 1;   // (sized by snet_build for the bounds of dcv_mlp_eval_steps)
     if (m->vae_d > 0 && (pl->kl_part == nullptr || nwg > kEvalWorkgroupsPerLaunch || m->eps_cur == nullptr)) return 1;
     const int64_t part_need = nwg * pl->per_wg + 8 * (int64_t)m->L;   // + the alignment padding of the items
-    if (train && pl->part_floats < part_need) {
-        if (pl->part) (void)hipFree(pl->part);
-        pl->part = nullptr;
-        pl->part_floats = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&pl->part), (size_t)part_need * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            return 1;
-        }
-        pl->part_floats = part_need;
-    }
+    if (train && !snet_grow(&pl->part, &pl->part_floats, part_need)) return 1;
     SnetArgs a = pl->base;
     const size_t lds_bytes = snet_ae_map(a, m->L, pl->fl, TR);
     if (lds_bytes == 0) return 1;
-    int64_t off = 0;
-    for (int l = 0; l < m->L; ++l) {
-        SnetLayer& y = a.l[l];
-        y.pw_off = off; off += nwg * (int64_t)y.pw_stride;   // 16-byte aligned items (vector stores here, vector loads in the reduction)
-        y.pb_off = off; off += nwg * (int64_t)y.pb_stride;
-        if (ra) {
-            ra->slab[l] = pl->part + y.pw_off;
-            ra->bpart[l] = pl->part + y.pb_off;
-            ra->splits[l] = (int)nwg;
-            ra->bblocks[l] = (int)nwg;
-            ra->wstride[l] = y.pw_stride;
-            ra->bstride[l] = y.pb_stride;
-        }
-    }
+    snet_partials_layout(a.l, m->L, nwg, pl->part, ra);
     a.params = m->params;
     a.img = m->snet_img;
     a.img_floats = m->snet_img_floats;
@@ -745,25 +546,9 @@ int snet_ae_step(dcv_mlp* m, const float* Xn_d, int64_t ld, const RowMap& rm, in
     a.kl_part = pl->kl_part;
     a.stamps = pl->stamps;
     pl->last_tr = TR;
+    static int attr_state[4] = {0, 0, 0, 0};   // per kernel instantiation (snet_launch)
     auto launch = [&](auto kern) -> int {
-        static int attr_state[4] = {0, 0, 0, 0};   // 0 unknown, 1 set, -1 refused by the runtime (the fused form is then off)
-        const int slot = (TR == 32 ? 0 : 1) + (a.vae_l >= 0 ? 2 : 0);
-        if (attr_state[slot] == 0) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) (void)hipGetLastError();
-            attr_state[slot] = e == hipSuccess ? 1 : -1;
-        }
-        if (attr_state[slot] < 0) return 1;
-        if (g_launch_ev.start != nullptr) {   // a profiled launch: events stamped with the kernel's own begin / end (common.h)
-            const LaunchEvents ev = g_launch_ev;
-            g_launch_ev = LaunchEvents{};
-            g_launch_taken = ev.start;
-            hipExtLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(kSnetThreads), (uint32_t)lds_bytes, s, ev.start, ev.stop, 0u, a);
-        } else {
-            hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(kSnetThreads), lds_bytes, s, a);
-        }
-        DCV_CHECK_LAUNCH();
-        return DCV_OK;
+        return snet_launch(kern, attr_state[(TR == 32 ? 0 : 1) + (a.vae_l >= 0 ? 2 : 0)], 160 * 1024, lds_bytes, a, nwg, s);
     };
     if (a.vae_l >= 0) {
         const int rc = TR == 32 ? launch(snet_ae_kernel<32, true>) : launch(snet_ae_kernel<16, true>);

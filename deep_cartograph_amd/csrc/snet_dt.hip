@@ -57,27 +57,27 @@ struct SnetDtArgs {
     float* part;                  // backward: gradient partials
 };
 
-template <int NARGS>
-__device__ __forceinline__ unsigned touch_kernargs() {
-    unsigned x = 0;
-    const __attribute__((address_space(4))) unsigned* kp = (const __attribute__((address_space(4))) unsigned*)__builtin_amdgcn_kernarg_segment_ptr();
-#pragma unroll
-    for (int off = 0; off < NARGS; off += 64) x ^= kp[off / 4];
-    return x;
-}
-
 union TicaWaveLdsAny {
     TicaWaveLds<1> h1;
     TicaWaveLds<2> h2;
     TicaWaveLds<3> h3;
     TicaWaveLds<4> h4;
 };
+// the wave-parallel d x d loss head (tica_head.h) for the run-time d of the plan
+__device__ __forceinline__ void snet_dt_head(int D, TicaWaveLdsAny& w, const double* stats, const FusedHead& f, double* gradp, double* log,
+                                             int* log_count, int log_cap, int lane) {
+    switch (D) {
+        case 1: tica_grad_wave<1>(w.h1, stats, f.Bg, f.reg, gradp, log, log_count, log_cap, f.log_width, lane); break;
+        case 2: tica_grad_wave<2>(w.h2, stats, f.Bg, f.reg, gradp, log, log_count, log_cap, f.log_width, lane); break;
+        case 3: tica_grad_wave<3>(w.h3, stats, f.Bg, f.reg, gradp, log, log_count, log_cap, f.log_width, lane); break;
+        default: tica_grad_wave<4>(w.h4, stats, f.Bg, f.reg, gradp, log, log_count, log_cap, f.log_width, lane); break;
+    }
+}
 // TR rows per workgroup = TR / 2 pairs (16 for small batches, 32, 64 or 128: larger tiles mean fewer statistics / gradient partials for the
 // ticketed sums and the reduction launch behind; the work of a tile is latency, not arithmetic, at these widths)
 template <int TR>
 __global__ __launch_bounds__(kSnetThreads) void snet_dt_fwd_kernel(SnetDtArgs a) {
     constexpr int NT = kSnetThreads, HP = TR / 2;
-    constexpr int RG = TR / 16, CG = kSnetWaves / RG;
     constexpr int XU = TR / 8;   // 16-byte units of the input tile per thread (TR * pin / 4 <= XU * NT: pin <= 256 * 32 / TR ... checked by the plan)
     const int D = a.d, W = 2 * D + 2 * D * D;
     extern __shared__ __attribute__((aligned(16))) float sl[];
@@ -85,11 +85,10 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_fwd_kernel(SnetDtArgs a)
     __shared__ double s_stat[40];
     __shared__ unsigned s_flag;
     __shared__ int s_slot;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int rg = wave % RG, cg = wave / RG;
-    const int q = lane >> 4, n = lane & 15;
+    const SnetCoords<TR> k;
+    const int t = k.t, lane = k.lane, wave = k.wave;
     const int L = a.L;
-    const unsigned ka_touch = touch_kernargs<(int)sizeof(SnetDtArgs)>();
+    const unsigned ka_touch = snet_touch_kernargs<(int)sizeof(SnetDtArgs)>();
     // ---- input tile: local row r is pair p0 + r % HP, half r / HP
     // workgroup -> (batch of the launch, tile of the batch); batch j of a batched evaluation = the pairs [j * B, (j + 1) * B)
     const int bj = a.nb > 1 ? (int)blockIdx.x / a.wgpb : 0;
@@ -127,57 +126,18 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_fwd_kernel(SnetDtArgs a)
         if (i < x_tot) *reinterpret_cast<float4*>(H0 + r * ps0 + 4 * c) = v;
     };
     auto issue_x = [&]() {
+        if (!x_vec || x_issued) return;
+        x_issued = true;
 #pragma unroll
         for (int u = 0; u < XA; ++u) xv[u] = load_x(u);
     };
-    // ---- stage every weight image and bias (snet.hip: one flat table, twelve loads in flight, two dependent round trips)
+    // ---- stage every weight image and bias
     if (a.img != nullptr) {   // one contiguous LDS-DMA copy of the weight image (kept current by the optimiser), the input rows behind it
         snet_stage_image<NT>(a.img, sl, 0, a.img_floats, t);
-    } else {
-        // the table entries of pass p + 1 are requested behind the data loads of pass p and arrive in the same round trip: one
-        // dependent round trip per pass (+ the first table read) instead of two (round 4: 8 -> 5 for the C2 network's four passes)
-        int2 e[12];
-    #pragma unroll
-        for (int u = 0; u < 12; ++u) {
-            const int i = t + NT * u;
-            e[u] = i < a.stage_n ? a.stage_tab[i] : make_int2(-1, -1);
-        }
-        for (int i0 = t; i0 < a.stage_n; i0 += 12 * NT) {
-            float4 v[12];
-    #pragma unroll
-            for (int u = 0; u < 12; ++u) {
-                v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (e[u].x >= 0) {
-                    const float* src = a.params + e[u].x;
-                    const int nv = (e[u].y >> 20) & 7;
-                    if ((e[u].y >> 24) & 1) {
-                        v[u] = *reinterpret_cast<const float4*>(src);
-                    } else {
-                        v[u].x = src[0];
-                        if (nv > 1) v[u].y = src[1];
-                        if (nv > 2) v[u].z = src[2];
-                        if (nv > 3) v[u].w = src[3];
-                    }
-                }
-            }
-            if (x_vec && !x_issued) {   // the rows of X ride along the data round trip
-                x_issued = true;
-                issue_x();
-            }
-            int2 en[12];
-    #pragma unroll
-            for (int u = 0; u < 12; ++u) {
-                const int i = i0 + 12 * NT + NT * u;
-                en[u] = i < a.stage_n ? a.stage_tab[i] : make_int2(-1, -1);
-            }
-    #pragma unroll
-            for (int u = 0; u < 12; ++u)
-                if (e[u].y >= 0) *reinterpret_cast<float4*>(sl + (e[u].y & 0xFFFFF)) = v[u];
-    #pragma unroll
-            for (int u = 0; u < 12; ++u) e[u] = en[u];
-        }
+    } else {   // through the plan's staging table, the rows of X riding along the first pass's data round trip
+        snet_stage_table<NT, false>(a.stage_tab, 0, a.stage_n, a.params, sl, t, issue_x);
     }
-    if (x_vec && !x_issued) issue_x();
+    issue_x();
     if (a.img != nullptr) vm_wait<0>();   // this wave's image copies have landed (the barrier below covers the other waves)
     asm volatile("" ::"s"(ka_touch));
     if (x_vec) {
@@ -208,21 +168,7 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_fwd_kernel(SnetDtArgs a)
         const float* Hin = sl + a.lh[l];
         float* Hout = sl + a.lh[l + 1];
         const int psin = a.ps[l], pso = a.ps[l + 1];
-        const float* ap = Hin + (rg * 16 + n) * psin + 4 * q;
-        const float* Wl = sl + y.lw + n * y.pws + 4 * q;
-#define SNET_FWD(NK)                                                                                          \
-        SnetFrags<NK> A;                                                                                       \
-        A.load(ap);                                                                                            \
-        for (int ct = cg; ct < y.nk_out; ct += CG) {                                                           \
-            const sv4f acc = snet_fwd_tile<NK>(A, Wl + ct * 16 * y.pws);                                       \
-            const int col = ct * 16 + n;                                                                       \
-            const float bias = sl[y.lb + col];                                                                 \
-            sv4f h = snet_act4(y.act, acc + bias);                                                             \
-            if (col >= y.out) h = sv4f{0.f, 0.f, 0.f, 0.f};                                                    \
-            _Pragma("unroll") for (int v = 0; v < 4; ++v) Hout[(rg * 16 + 4 * q + v) * pso + col] = h[v];      \
-        }
-        SNET_NK_SWITCH(y.nk_in, SNET_FWD)
-#undef SNET_FWD
+        snet_forward_layer<TR>(k, y, sl, Hin, psin, Hout, pso, [](sv4f&, int) {});
         __syncthreads();
     }
     // ---- statistics partial of the tile's pairs: [sum f_t | sum f_lag | sum f_t f_t^T | sum f_t f_lag^T], float64, pair order
@@ -304,12 +250,7 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_fwd_kernel(SnetDtArgs a)
                     lc = &s_slot;
                     cap = f.log_cap - bj;
                 }
-                switch (D) {
-                    case 1: tica_grad_wave<1>(s_head.h1, s_stat, f.Bg, f.reg, f.gradp, logp, lc, cap, f.log_width, lane); break;
-                    case 2: tica_grad_wave<2>(s_head.h2, s_stat, f.Bg, f.reg, f.gradp, logp, lc, cap, f.log_width, lane); break;
-                    case 3: tica_grad_wave<3>(s_head.h3, s_stat, f.Bg, f.reg, f.gradp, logp, lc, cap, f.log_width, lane); break;
-                    default: tica_grad_wave<4>(s_head.h4, s_stat, f.Bg, f.reg, f.gradp, logp, lc, cap, f.log_width, lane); break;
-                }
+                snet_dt_head(D, s_head, s_stat, f, f.gradp, logp, lc, cap, lane);
                 if (a.nb > 1 && lane == 0) {
                     const unsigned prev = __hip_atomic_fetch_add(a.ticket + a.nb, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if (prev == (unsigned)a.nb - 1u) {
@@ -325,17 +266,15 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_fwd_kernel(SnetDtArgs a)
 template <int TR>
 __global__ __launch_bounds__(kSnetThreads) void snet_dt_bwd_kernel(SnetDtArgs a) {
     constexpr int NT = kSnetThreads, HP = TR / 2;
-    constexpr int RG = TR / 16, CG = kSnetWaves / RG;
     const int D = a.d, NG = 2 * D + 2 * D * D;   // mu | Gu | Gv | c
     extern __shared__ __attribute__((aligned(16))) float sl[];
     __shared__ double s_g[40];
     __shared__ double s_stat[40];
     __shared__ TicaWaveLdsAny s_head;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int rg = wave % RG, cg = wave / RG;
-    const int q = lane >> 4, n = lane & 15;
+    const SnetCoords<TR> k;
+    const int t = k.t, lane = k.lane, wave = k.wave;
     const int L = a.L;
-    const unsigned ka_touch = touch_kernargs<(int)sizeof(SnetDtArgs)>();
+    const unsigned ka_touch = snet_touch_kernargs<(int)sizeof(SnetDtArgs)>();
     const int64_t p0 = (int64_t)blockIdx.x * HP;
     // ---- stage the weight images of layers >= 1 (the input gradients read them; no bias, no layer 0) and the blob.
     //      Order of issue: table entries, the first eight blob units, the weight data (needs the entries: loads return in
@@ -346,6 +285,8 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_bwd_kernel(SnetDtArgs a)
     float4 bv[8];
     bool blob_issued = false;
     auto issue_blob = [&]() {
+        if (blob_issued) return;
+        blob_issued = true;
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int i = t + NT * u;
@@ -365,61 +306,15 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_bwd_kernel(SnetDtArgs a)
             const FusedHead& f = a.fused;
             double* logp = blockIdx.x == 0 ? f.log : nullptr;
             int* lc = blockIdx.x == 0 ? f.log_count : nullptr;
-            switch (D) {
-                case 1: tica_grad_wave<1>(s_head.h1, s_stat, f.Bg, f.reg, s_g, logp, lc, f.log_cap, f.log_width, lane); break;
-                case 2: tica_grad_wave<2>(s_head.h2, s_stat, f.Bg, f.reg, s_g, logp, lc, f.log_cap, f.log_width, lane); break;
-                case 3: tica_grad_wave<3>(s_head.h3, s_stat, f.Bg, f.reg, s_g, logp, lc, f.log_cap, f.log_width, lane); break;
-                default: tica_grad_wave<4>(s_head.h4, s_stat, f.Bg, f.reg, s_g, logp, lc, f.log_cap, f.log_width, lane); break;
-            }
+            snet_dt_head(D, s_head, s_stat, f, s_g, logp, lc, f.log_cap, lane);
         }
     };
     if (a.img != nullptr) {   // layers >= 1 of the weight image by LDS-DMA, the blob's first units behind it
         snet_stage_image<NT>(a.img, sl, a.img_bwd0, a.img_floats, t);
-    } else {
-        // the table entries of pass p + 1 are requested behind the data loads of pass p and arrive in the same round trip: one
-        // dependent round trip per pass (+ the first table read) instead of two (round 4: 8 -> 5 for the C2 network's four passes)
-        int2 e[12];
-    #pragma unroll
-        for (int u = 0; u < 12; ++u) {
-            const int i = a.stage_bwd0 + t + NT * u;
-            e[u] = i < a.stage_n ? a.stage_tab[i] : make_int2(-1, -1);
-        }
-        for (int i0 = a.stage_bwd0 + t; i0 < a.stage_n; i0 += 12 * NT) {
-            float4 v[12];
-            if (!blob_issued) {
-                blob_issued = true;
-                issue_blob();
-            }
-    #pragma unroll
-            for (int u = 0; u < 12; ++u) {
-                v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (e[u].x >= 0) {
-                    const float* src = a.params + e[u].x;
-                    const int nv = (e[u].y >> 20) & 7;
-                    if ((e[u].y >> 24) & 1) {
-                        v[u] = *reinterpret_cast<const float4*>(src);
-                    } else {
-                        v[u].x = src[0];
-                        if (nv > 1) v[u].y = src[1];
-                        if (nv > 2) v[u].z = src[2];
-                        if (nv > 3) v[u].w = src[3];
-                    }
-                }
-            }
-            int2 en[12];
-    #pragma unroll
-            for (int u = 0; u < 12; ++u) {
-                const int i = i0 + 12 * NT + NT * u;
-                en[u] = i < a.stage_n ? a.stage_tab[i] : make_int2(-1, -1);
-            }
-    #pragma unroll
-            for (int u = 0; u < 12; ++u)
-                if (e[u].y >= 0) *reinterpret_cast<float4*>(sl + (e[u].y & 0xFFFFF)) = v[u];
-    #pragma unroll
-            for (int u = 0; u < 12; ++u) e[u] = en[u];
-        }
+    } else {   // through the plan's staging table from layer 1 on, the blob's first units ahead of the first pass's data loads
+        snet_stage_table<NT, true>(a.stage_tab, a.stage_bwd0, a.stage_n, a.params, sl, t, issue_blob);
     }
-    if (!blob_issued) issue_blob();
+    issue_blob();
     // After the staging loop on both paths: the head is wave-wide (its lanes share data through LDS) and must run with the
     // whole wave.  Inside the table loop only the lanes with an entry left take the last pass, so a staging table of
     // 449..511 entries in the backward ran it twice under partial exec masks, each time with part of the statistics.
@@ -502,69 +397,13 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_bwd_kernel(SnetDtArgs a)
         float* Hin = sl + a.lh[l];
         const int psz = a.ps[l + 1], psh = a.ps[l];
         sv4f dg[kSnetMaxTiles];
-        if (l > 0) {
-            const float* ap = dZ + (rg * 16 + n) * psz + 4 * q;
-            const float* Wl = sl + y.lw + (4 * q) * y.pws + n;
-#define SNET_DGRAD(NK)                                                                                   \
-            SnetFrags<NK> A;                                                                             \
-            A.load(ap);                                                                                  \
-            _Pragma("unroll") for (int j = 0; j < kSnetMaxTiles; ++j) {                                  \
-                const int it = cg + j * CG;                                                              \
-                if (it < y.nk_in) dg[j] = snet_dgrad_tile<NK>(A, Wl + it * 16, y.pws);                   \
-            }
-            SNET_NK_SWITCH(y.nk_out, SNET_DGRAD)
-#undef SNET_DGRAD
-        }
-        {
-            const int nti = y.nk_in, ntot = y.nk_out * nti;
-            float* pw = a.part + y.pw_off + (int64_t)blockIdx.x * y.pw_stride;
-            const bool vec_ok = (y.in & 3) == 0 && ((y.pw_off + (int64_t)blockIdx.x * y.pw_stride) & 3) == 0;
-            int ot = 0, it = wave;
-            while (it >= nti) { it -= nti; ++ot; }
-#pragma unroll 2
-            for (int tile = wave; tile < ntot; tile += kSnetWaves) {
-                const sv4f acc = snet_wgrad_tile<TR>(Hin + q * psh + it * 16 + n, psh, dZ + q * psz + ot * 16 + n, psz);
-                const int o = ot * 16 + n, i0 = it * 16 + 4 * q;
-                if (o < y.out) {
-                    float* dst = pw + (int64_t)o * y.in + i0;
-                    if (vec_ok && i0 + 4 <= y.in) {
-                        handoff_store16(dst, acc);
-                    } else {
-#pragma unroll
-                        for (int v = 0; v < 4; ++v)
-                            if (i0 + v < y.in) dst[v] = acc[v];
-                    }
-                }
-                it += kSnetWaves;
-                while (it >= nti) { it -= nti; ++ot; }
-            }
-            for (int o4 = t; o4 < 4 * y.pout; o4 += NT) {
-                const int o = o4 >> 2, part = o4 & 3;
-                float s = 0.f;
-#pragma unroll
-                for (int r = 0; r < TR / 4; ++r) s += dZ[(part * (TR / 4) + r) * psz + o];
-                s += __shfl_xor(s, 1, 64);
-                s += __shfl_xor(s, 2, 64);
-                if (part == 0 && o < y.out) a.part[y.pb_off + (int64_t)blockIdx.x * y.pb_stride + o] = s;
-            }
-        }
+        if (l > 0) snet_dgrad_layer<TR>(k, y, sl, dZ, psz, dg);   // input gradient first, kept in registers
+        snet_wgrad_partials<TR>(k, y, a.part, Hin, psh, dZ, psz);
+        snet_bgrad_partials<TR>(k, y, a.part, dZ, psz);
         if (l == 0) break;
         __syncthreads();   // every wave is done reading H_l
         const int act_prev = a.l[l - 1].act, out_prev = a.l[l - 1].out;
-#pragma unroll
-        for (int j = 0; j < kSnetMaxTiles; ++j) {
-            const int it = cg + j * CG;
-            if (it < y.nk_in) {
-                const int col = it * 16 + n;
-                float* p = Hin + (rg * 16 + 4 * q) * psh + col;
-                sv4f h;
-#pragma unroll
-                for (int v = 0; v < 4; ++v) h[v] = p[v * psh];
-                const sv4f dh = snet_actgrad4(act_prev, h);
-#pragma unroll
-                for (int v = 0; v < 4; ++v) p[v * psh] = col < out_prev ? dg[j][v] * dh[v] : 0.f;
-            }
-        }
+        snet_dz_prev<TR>(k, y, act_prev, out_prev, Hin, psh, dg);
         __syncthreads();
     }
 }
@@ -589,13 +428,7 @@ constexpr size_t kSnetDtLdsMax = 160 * 1024 - 8 * 1024;   // static LDS of the k
 
 // activation map of a TR-row tile behind the weight images; returns the LDS floats needed
 static int snet_dt_map(SnetDtArgs& a, int fl, int TR) {
-    int f = fl;
-    for (int l = 0; l <= a.L; ++l) {
-        const int P = l == 0 ? a.l[0].pin : a.l[l - 1].pout;
-        a.ps[l] = P + 4;
-        a.lh[l] = f;
-        f += TR * (P + 4);
-    }
+    const int f = snet_act_map(a.l, a.L, TR, fl, a.lh, a.ps);
     a.act_len = f - a.lh[0];
     return f < 2048 ? 2048 : f;   // the last arriver sums the statistics partials in the first 4 KB
 }
@@ -635,53 +468,33 @@ static int snet_dt_pick_tr(const SnetDtPlan* pl, int64_t B) {
     return best;
 }
 
-template <class T>
-static bool grow(T** p, int64_t* have, int64_t need) {
-    if (*have >= need) return true;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    if (hipMalloc(reinterpret_cast<void**>(p), (size_t)need * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    *have = need;
-    return true;
-}
-
 static bool snet_dt_build(dcv_mlp* m) {
     if (m->desc.model != DCV_MODEL_DEEPTICA || m->any_drop || m->any_bn || m->d_out > 4 || m->d_out < 1 || snet_disabled()) return false;
-    SnetDtPlan* pl = new (std::nothrow) SnetDtPlan();
+    SnetDtPlan* pl = new (std::nothrow) SnetDtPlan();   // value-initialised: no buffer yet
     if (!pl) return false;
-    *pl = SnetDtPlan{};
+    m->snet_dt = pl;   // from here on a half-built plan is released by snet_dt_free
+    auto fail = [&] {
+        snet_dt_free(m);
+        return false;
+    };
     SnetDtArgs& a = pl->base;
     a.L = m->L;
     a.d = m->d_out;
-    int fl = 0;
-    int64_t per_wg = 0;
     std::vector<int2> tab;
     int tab_begin[DCV_MAX_LAYERS];
-    if (!snet_layout(m, a.l, tab, tab_begin, fl, per_wg)) { delete pl; return false; }
-    pl->per_wg = per_wg;
+    if (!snet_layout(m, a.l, tab, tab_begin, pl->fl, pl->per_wg)) return fail();
     (void)snet_image_build(m);   // on failure the kernels keep the table-driven staging
-    pl->fl = fl;
     {
         SnetDtArgs tmp = a;
-        if ((size_t)snet_dt_map(tmp, fl, 32) * sizeof(float) > kSnetDtLdsMax) { delete pl; return false; }
+        if ((size_t)snet_dt_map(tmp, pl->fl, 32) * sizeof(float) > kSnetDtLdsMax) return fail();
     }
-    if (hipMalloc(reinterpret_cast<void**>(&pl->stage_tab), tab.size() * sizeof(int2)) != hipSuccess ||
-        hipMemcpy(pl->stage_tab, tab.data(), tab.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        if (pl->stage_tab) (void)hipFree(pl->stage_tab);
-        delete pl;
-        return false;
-    }
+    if (!snet_upload_table(tab, &pl->stage_tab)) return fail();
     a.stage_tab = pl->stage_tab;
     a.stage_n = (int)tab.size();
     a.stage_bwd0 = m->L > 1 ? tab_begin[1] : (int)tab.size();
     // batched validation passes: statistics partials and tickets for the bounds of dcv_mlp_eval_steps, allocated now so that no
     // allocation lands in a timed pass (without them the passes go batch by batch)
-    if (grow(&pl->spart, &pl->spart_n, kEvalWorkgroupsPerLaunch * (int64_t)m->stats_len) && grow(&pl->ev_ticket, &pl->ev_ticket_n, (int64_t)kEvalBatchesPerLaunch + 1)) {
+    if (snet_grow(&pl->spart, &pl->spart_n, kEvalWorkgroupsPerLaunch * (int64_t)m->stats_len) && snet_grow(&pl->ev_ticket, &pl->ev_ticket_n, (int64_t)kEvalBatchesPerLaunch + 1)) {
         if (hipMemset(pl->ev_ticket, 0, (size_t)pl->ev_ticket_n * sizeof(unsigned)) != hipSuccess) {
             (void)hipGetLastError();
             (void)hipFree(pl->ev_ticket);
@@ -689,7 +502,6 @@ static bool snet_dt_build(dcv_mlp* m) {
             pl->ev_ticket_n = 0;
         }
     }
-    m->snet_dt = pl;
     return true;
 }
 
@@ -710,25 +522,10 @@ int snet_dt_last_tile_rows(const dcv_mlp* m) {
     return pl ? pl->last_tr : 0;
 }
 
+static int g_dt_attr_state[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // per kernel instantiation (snet_launch): forward TR 32 / 64 / 128 / 16, then the backward's
 template <class K>
 static int snet_dt_launch(K kern, int slot, size_t lds_bytes, const SnetDtArgs& a, int64_t nwg, hipStream_t s) {
-    static int attr_state[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // per kernel instantiation: 0 unknown, 1 set, -1 refused by the runtime
-    if (attr_state[slot] == 0) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSnetDtLdsMax);
-        if (e != hipSuccess) (void)hipGetLastError();
-        attr_state[slot] = e == hipSuccess ? 1 : -1;
-    }
-    if (attr_state[slot] < 0) return 1;
-    if (g_launch_ev.start != nullptr) {   // a profiled launch: events stamped with the kernel's own begin / end (common.h)
-        const LaunchEvents ev = g_launch_ev;
-        g_launch_ev = LaunchEvents{};
-        g_launch_taken = ev.start;
-        hipExtLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(kSnetThreads), (uint32_t)lds_bytes, s, ev.start, ev.stop, 0u, a);
-    } else {
-        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(kSnetThreads), lds_bytes, s, a);
-    }
-    DCV_CHECK_LAUNCH();
-    return DCV_OK;
+    return snet_launch(kern, g_dt_attr_state[slot], kSnetDtLdsMax, lds_bytes, a, nwg, s);
 }
 
 // Fused forward of one Deep-TICA batch (+ batch statistics, + the loss head when head != 0: 1 = training, the head's
@@ -738,13 +535,7 @@ static int snet_dt_launch(K kern, int slot, size_t lds_bytes, const SnetDtArgs& 
 int snet_dt_forward(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t* idx_d, int64_t row0, int32_t batch, int head, bool keep_blob,
                     hipStream_t s, int nb) {
     static const int64_t kMaxBytes = 64ll << 20;
-    if (m->snet_dt == nullptr) {
-        if (m->snet_dt_tried || !snet_dt_build(m)) {
-            m->snet_dt_tried = true;
-            return 1;
-        }
-        m->snet_dt_tried = true;
-    }
+    if (!snet_plan_ready(m->snet_dt, m->snet_dt_tried, [&] { return snet_dt_build(m); })) return 1;
     SnetDtPlan* pl = static_cast<SnetDtPlan*>(m->snet_dt);
     const int TR = snet_dt_pick_tr(pl, batch);
     if (TR == 0) return 1;
@@ -755,9 +546,9 @@ int snet_dt_forward(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t* id
     if (wgpb > 512 || wgpb * pl->per_wg * (int64_t)sizeof(float) > kMaxBytes || wgpb * a.act_len * (int64_t)sizeof(float) > kMaxBytes) return 1;
     if (nb < 1 || (nb > 1 && (head != 2 || keep_blob))) return 1;
     const int64_t nwg = wgpb * nb;
-    if (!grow(&pl->spart, &pl->spart_n, nwg * W)) return 1;
+    if (!snet_grow(&pl->spart, &pl->spart_n, nwg * W)) return 1;
     if (nb > 1 && nb + 1 > pl->ev_ticket_n) return 1;   // (sized by snet_dt_build for the bounds of dcv_mlp_eval_steps)
-    if (keep_blob && !grow(&pl->blob, &pl->blob_floats, nwg * (int64_t)a.act_len)) return 1;
+    if (keep_blob && !snet_grow(&pl->blob, &pl->blob_floats, nwg * (int64_t)a.act_len)) return 1;
     a.params = m->params;
     a.img = m->snet_img;
     a.img_floats = m->snet_img_floats;
@@ -804,24 +595,13 @@ int snet_dt_backward(dcv_mlp* m, int32_t batch, int64_t global_batch, bool head,
         return DCV_ESTATE;
     }
     const int64_t part_need = nwg * pl->per_wg + 8 * (int64_t)m->L;
-    if (!grow(&pl->part, &pl->part_floats, part_need)) {
+    if (!snet_grow(&pl->part, &pl->part_floats, part_need)) {
         set_error("snet_dt_backward: out of device memory (%lld floats of gradient partials)", (long long)part_need);
         return DCV_ENOMEM;
     }
     SnetDtArgs a = pl->base;
     const size_t lds_bytes = (size_t)snet_dt_map(a, pl->fl, TR) * sizeof(float);
-    int64_t off = 0;
-    for (int l = 0; l < m->L; ++l) {
-        SnetLayer& y = a.l[l];
-        y.pw_off = off; off += nwg * (int64_t)y.pw_stride;
-        y.pb_off = off; off += nwg * (int64_t)y.pb_stride;
-        ra->slab[l] = pl->part + y.pw_off;
-        ra->bpart[l] = pl->part + y.pb_off;
-        ra->splits[l] = (int)nwg;
-        ra->bblocks[l] = (int)nwg;
-        ra->wstride[l] = y.pw_stride;
-        ra->bstride[l] = y.pb_stride;
-    }
+    snet_partials_layout(a.l, m->L, nwg, pl->part, ra);
     a.params = m->params;
     a.img = m->snet_img;
     a.img_floats = m->snet_img_floats;
