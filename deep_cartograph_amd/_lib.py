@@ -148,6 +148,10 @@ SIGNATURES = {
     "dcv_linkage_workspace": (_SZ, [_I64, _I32]),
     "dcv_linkage_pdist": (C.c_int, [_P, _I64, _I32, _P, _SZ, _P]),
     "dcv_linkage": (C.c_int, [_P, _I64, _I32, _I32, _P, C.POINTER(_I64), _P, _SZ, _P]),
+    "dcv_core_distances_workspace": (_SZ, [_I64, _I32, _I32]),
+    "dcv_core_distances": (C.c_int, [_P, _I64, _I32, _I32, _P, _P, _SZ, _P]),
+    "dcv_mr_mst_workspace": (_SZ, [_I64, _I32]),
+    "dcv_mr_mst": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "dcv_gemm_f32": (C.c_int, [_I32, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
 }
 

@@ -379,6 +379,71 @@ def linkage(P: torch.Tensor, method: str = "complete", return_searches: bool = F
     return (Z, int(searches.value)) if return_searches else Z
 
 
+CORE_MAX_K = 64   # min_samples dcv_core_distances holds per query
+
+
+def _check_points(P: torch.Tensor, what: str):
+    _require_gpu(P)
+    _check_matrix(P, torch.float64)
+    n, d = P.shape
+    if not (2 <= n < 2 ** 31) or not (1 <= d <= 16):
+        raise DcvError(f"{what} failed (code -1): {n} points in {d} dimensions, supported n >= 2, 1 <= d <= 16")
+    # a NaN never compares below anything: no neighbour, no candidate.  Refused here; the kernels keep their own guard
+    if not bool(torch.isfinite(P).all()):
+        raise DcvError(f"{what} failed (code -1): the points hold NaN or infinite values")
+
+
+def core_distances_workspace_bytes(n: int, d: int, k: int) -> int:
+    return int(_lib.load().dcv_core_distances_workspace(n, d, k))
+
+
+def core_distances(P: torch.Tensor, k: int) -> torch.Tensor:
+    """NearestNeighbors(n_neighbors=k).kneighbors(P)[0][:, -1] on the GPU: for every point the k-th smallest Euclidean
+    distance to all points, itself included -- HDBSCAN's core distances with min_samples = k, equal to scikit-learn's
+    (dcv_core_distances).  P is n x d float64 on the device, finite, n >= 2, d <= 16, 1 <= k <= min(n, CORE_MAX_K).
+    Returns a float64 device tensor of n entries."""
+    _check_points(P, "core_distances")
+    P = P.contiguous()
+    n, d = P.shape
+    k = int(k)
+    if not (1 <= k <= min(n, CORE_MAX_K)):
+        raise DcvError(f"core_distances failed (code -1): k = {k}, supported 1..min(n, {CORE_MAX_K})")
+    lib = _lib.load()
+    core = torch.empty(n, dtype=torch.float64, device=P.device)
+    nbytes = lib.dcv_core_distances_workspace(n, d, k)
+    ws = _ws(nbytes, P.device)
+    check(lib.dcv_core_distances(_ptr(P), n, d, k, _ptr(core), _ptr(ws), nbytes, _stream()), "dcv_core_distances")
+    return core
+
+
+def mr_mst_workspace_bytes(n: int, d: int) -> int:
+    return int(_lib.load().dcv_mr_mst_workspace(n, d))
+
+
+def mr_mst(P: torch.Tensor, core: torch.Tensor) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """sklearn's mst_from_data_matrix(P, core, Euclidean, alpha=1) on the GPU: the minimum spanning tree of the mutual
+    reachability graph by Prim's algorithm from node 0.  Returns NumPy arrays (src int64, dst int64, w float64) of
+    n - 1 edges in Prim order, equal to scikit-learn's (dcv_mr_mst).  `core`: n float64 on the device, finite."""
+    _check_points(P, "mr_mst")
+    _require_gpu(core)
+    P = P.contiguous()
+    n, d = P.shape
+    if core.dtype != torch.float64 or core.dim() != 1 or core.shape[0] != n:
+        raise DcvError(f"mr_mst failed (code -1): expected {n} float64 core distances, got shape {tuple(core.shape)} dtype {core.dtype}")
+    core = core.contiguous()
+    if not bool(torch.isfinite(core).all()):
+        raise DcvError("mr_mst failed (code -1): the core distances hold NaN or infinite values")
+    lib = _lib.load()
+    src = np.empty(n - 1, dtype=np.int64)
+    dst = np.empty(n - 1, dtype=np.int64)
+    w = np.empty(n - 1, dtype=np.float64)
+    nbytes = lib.dcv_mr_mst_workspace(n, d)
+    ws = _ws(nbytes, P.device)
+    check(lib.dcv_mr_mst(_ptr(P), n, d, _ptr(core), src.ctypes.data, dst.ctypes.data, w.ctypes.data, _ptr(ws), nbytes, _stream()),
+          "dcv_mr_mst")
+    return src, dst, w
+
+
 # ------------------------------------------------------------------------------- MLP engine
 class RcclComm:
     """RCCL communicator owned by the library (dcv_comm_*): the collectives of a data-parallel step are then issued by

@@ -12,8 +12,16 @@ nearest-neighbour chain of scipy.cluster.hierarchy.linkage over a device-residen
 matrix (hip.linkage, csrc/linkage.hip) gives scipy's dendrogram bit for bit, ties included;
 the cut (scikit-learn's _hc_cut) and the centroids are host work over n - 1 merges.
 optimize_clustering builds the tree once for all k and scores every cut with the GPU score
-kernels.  `single` linkage and HDBSCAN keep delegating to scikit-learn, and so does a point
-set whose n x n matrix does not fit the free device memory."""
+kernels.  `single` linkage keeps delegating to scikit-learn, and so does a point set whose
+n x n matrix does not fit the free device memory.
+
+HDBSCAN runs on the GPU where its cost is: the core distances (hip.core_distances, an all-pairs
+pass) and Prim's algorithm over the implicit mutual-reachability graph (hip.mr_mst, one launch
+per step, O(n) state -- no n x n matrix), both equal to scikit-learn's bit for bit
+(csrc/hdbscan.hip).  What scikit-learn does with the minimum spanning tree -- the sort, the
+single-linkage tree, its condensation, the cluster selection, labels, probabilities and
+centroids -- is restated on the host (hdbscan.py).  More than 16 dimensions, min_samples above
+64, non-finite points or parameters scikit-learn would refuse delegate to scikit-learn."""
 from __future__ import annotations
 
 import heapq
@@ -25,6 +33,7 @@ import numpy as np
 import pandas as pd
 import torch
 
+from . import hdbscan as _hdbscan
 from . import hip
 from .parallel import Comm, global_topk, reduce_nearest
 
@@ -247,6 +256,66 @@ def _linkage_on_gpu(features: np.ndarray, linkage: str) -> bool:
     return True
 
 
+def _hdbscan_on_gpu(features: np.ndarray, min_cluster_size, max_cluster_size, min_samples, cluster_selection_epsilon,
+                    cluster_selection_method) -> bool:
+    """Whether HDBSCAN of these points runs on the GPU; one log line naming the reason when it does not."""
+    def no(why):
+        logger.info(f"HDBSCAN is delegated to scikit-learn: {why}")
+        return False
+
+    def integer(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+    if features.ndim != 2:
+        return no(f"the points are not a 2-D array (shape {features.shape})")
+    n, d = features.shape
+    # what scikit-learn's own parameter validation refuses is left to it: it raises its own error
+    if not (integer(min_cluster_size) and min_cluster_size >= 2 and integer(min_samples) and min_samples >= 1
+            and (max_cluster_size is None or (integer(max_cluster_size) and max_cluster_size >= 1))
+            and isinstance(cluster_selection_epsilon, (int, float, np.integer, np.floating)) and not isinstance(cluster_selection_epsilon, bool)
+            and cluster_selection_epsilon >= 0 and cluster_selection_method in ("eom", "leaf")):
+        return no("a parameter is outside the range handled on the GPU")
+    if n < 2 or not (1 <= d <= 16):
+        return no(f"{n} points in {d} dimensions (GPU: n >= 2, d <= 16)")
+    if min_samples > hip.CORE_MAX_K:
+        return no(f"min_samples = {min_samples} (GPU: at most {hip.CORE_MAX_K})")
+    if not np.isfinite(features).all():
+        return no("the points hold NaN or infinite values")
+    _device()
+    need = hip.mr_mst_workspace_bytes(n, d) + hip.core_distances_workspace_bytes(n, d, int(min_samples)) + 8 * n * (d + 1)
+    free, _ = torch.cuda.mem_get_info()
+    if need > LINKAGE_HEADROOM * free:
+        return no(f"{n} points need {need / 2**20:.0f} MiB of device memory, {free / 2**20:.0f} MiB are free")
+    return True
+
+
+def hdbscan_clustering(features: np.ndarray, min_cluster_size: Optional[int] = 5, max_cluster_size: Optional[int] = None,
+                       min_samples: Optional[int] = None, cluster_selection_epsilon: Optional[float] = None,
+                       cluster_selection_method: str = "eom") -> Tuple[np.ndarray, np.ndarray]:
+    """HDBSCAN(min_cluster_size, min_samples, cluster_selection_epsilon, max_cluster_size, cluster_selection_method,
+    store_centers="centroid", allow_single_cluster=False).fit(features) -> (labels_, centroids_), the reference's
+    hdbscan_clustering (statistics.py:199-283).  Core distances and the mutual-reachability minimum spanning tree on
+    the GPU, the rest on the host (hdbscan.py); scikit-learn's labels bit for bit.  min_samples=None is min_cluster_size,
+    as in scikit-learn."""
+    features = np.asarray(features)
+    if features.ndim == 2 and isinstance(min_cluster_size, (int, np.integer)) and isinstance(min_samples, (int, np.integer, type(None))):
+        min_samples = _hdbscan.check_parameters(features.shape[0], min_cluster_size, min_samples)   # scikit-learn's ValueErrors
+    if not _hdbscan_on_gpu(features, min_cluster_size, max_cluster_size, min_samples, cluster_selection_epsilon, cluster_selection_method):
+        from sklearn.cluster import HDBSCAN
+
+        hdb = HDBSCAN(min_cluster_size=min_cluster_size, min_samples=min_samples, store_centers="centroid",
+                      cluster_selection_epsilon=cluster_selection_epsilon, max_cluster_size=max_cluster_size,
+                      cluster_selection_method=cluster_selection_method, allow_single_cluster=False)
+        hdb.fit(features)
+        return hdb.labels_, hdb.centroids_
+    X = np.ascontiguousarray(features, dtype=np.float64)
+    P = torch.from_numpy(X).to(_device())
+    src, dst, w = hip.mr_mst(P, hip.core_distances(P, int(min_samples)))
+    labels, _, centroids = _hdbscan.finish(X, src, dst, w, int(min_cluster_size), cluster_selection_method,
+                                           float(cluster_selection_epsilon), None if max_cluster_size is None else int(max_cluster_size))
+    return labels, centroids
+
+
 def cluster_data(features: np.ndarray, settings: Dict, initial_centroids: np.ndarray = None, pts: Optional[_DevicePoints] = None,
                  tree: Optional[Tuple[np.ndarray, np.ndarray]] = None) -> Tuple[np.ndarray, np.ndarray]:
     """Cluster with the algorithm named in `settings` (defaults filled in place, as the reference
@@ -277,13 +346,8 @@ def cluster_data(features: np.ndarray, settings: Dict, initial_centroids: np.nda
         cents = np.stack([features[labels == i].mean(axis=0) for i in range(len(np.unique(labels)))])
         return labels, cents
     if algo == "hdbscan":
-        from sklearn.cluster import HDBSCAN
-
-        hdb = HDBSCAN(min_cluster_size=settings["min_cluster_size"], min_samples=settings["min_samples"], store_centers="centroid",
-                      cluster_selection_epsilon=settings["cluster_selection_epsilon"], max_cluster_size=settings["max_cluster_size"],
-                      cluster_selection_method=settings["cluster_selection_method"], allow_single_cluster=False)
-        hdb.fit(features)
-        return hdb.labels_, hdb.centroids_
+        return hdbscan_clustering(features, settings["min_cluster_size"], settings["max_cluster_size"], settings["min_samples"],
+                                  settings["cluster_selection_epsilon"], settings["cluster_selection_method"])
     raise Exception(f"clustering algorithm {algo} not implemented")
 
 
@@ -355,7 +419,8 @@ def optimize_clustering(features: np.ndarray, settings: Dict):
     """k in search_interval (inclusive): cluster, Calinski-Harabasz / Davies-Bouldin / silhouette,
     min-max normalise each list, best (CH - DB + Sil) / 3 (reference :17-110).  k-means and the GPU linkages are scored
     with clustering_scores on points uploaded once; the hierarchical tree is built once and cut for every k.  Only what
-    is delegated to scikit-learn (single linkage, a matrix that does not fit) is scored there too."""
+    is delegated to scikit-learn (single linkage, a matrix that does not fit) is scored there too.  HDBSCAN is one
+    cluster_data call (hdbscan_clustering: GPU core distances and spanning tree)."""
     if settings["algorithm"] in ("kmeans", "hierarchical"):
         from sklearn.metrics import calinski_harabasz_score, davies_bouldin_score, silhouette_score
 

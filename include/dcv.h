@@ -526,6 +526,34 @@ int dcv_linkage_pdist(const double* P_d, int64_t n, int32_t d, void* ws_d, size_
 int dcv_linkage(const double* P_d, int64_t n, int32_t d, int32_t method, double* Z_h, int64_t* searches_h,
                 void* ws_d, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- HDBSCAN
+ * Replaces the two stages of sklearn.cluster.HDBSCAN (Euclidean, alpha = 1, the kd_tree branch _hdbscan_prims) that
+ * touch the points, as statistics.hdbscan_clustering calls them; the condensation of the tree is host work.
+ * P is n x d float64 row-major on the device, 2 <= n < 2^31, 1 <= d <= 16, finite.  All distances are
+ * sqrt(sum_c (x_c - y_c)^2) with the squares added in coordinate order, no fused multiply-adds and a correctly
+ * rounded sqrt, so that both results EQUAL scikit-learn's bit for bit.
+ *
+ * dcv_core_distances: core_d[i] = the k-th smallest distance from point i to all n points, itself included
+ * (NearestNeighbors(n_neighbors = k).kneighbors(P)[0][:, -1]); k = min_samples, 1 <= k <= min(n, 64); k = 1 gives 0.
+ * A larger k is DCV_EINVAL before anything is launched.  The workspace is 256 bytes (a status word).
+ *
+ * dcv_mr_mst: Prim's algorithm from node 0 over mrd(i, j) = max(core[i], core[j], dist(i, j)) with the update and
+ * tie rules of sklearn's mst_from_data_matrix (a strictly smaller value replaces a point's running minimum; the
+ * new node is the lowest index among the minimal candidates).  src_h / dst_h (int64) and w_h (float64) are HOST
+ * arrays of n - 1 entries and receive the edges in Prim order.  One launch per step, n - 1 steps, enqueued in
+ * blocks.  The workspace is O(n): 32 n bytes (running minimum, source, in-tree flag, the edges) and about 8 KB of
+ * state -- no n x n matrix.
+ *
+ * Both calls synchronise the stream.  DCV_EINVAL: bad arguments -- before anything is launched -- or points
+ * that left a query without k finite distances / a step without a candidate (non-finite input); DCV_ENOMEM:
+ * workspace too small, nothing launched.  The *_workspace functions return 0 for arguments out of range. */
+size_t dcv_core_distances_workspace(int64_t n, int32_t d, int32_t k);
+int dcv_core_distances(const double* P_d, int64_t n, int32_t d, int32_t k, double* core_d, void* ws_d,
+                       size_t ws_bytes, void* stream);
+size_t dcv_mr_mst_workspace(int64_t n, int32_t d);
+int dcv_mr_mst(const double* P_d, int64_t n, int32_t d, const double* core_d, int64_t* src_h, int64_t* dst_h,
+               double* w_h, void* ws_d, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- building block
  * C[M,N] = op(A).op(B) on the FP32 MFMA engine that the covariance and MLP kernels are built
  * from (v_mfma_f32_32x32x2_f32, exact f32 products, f32 accumulation).  mode 0 (NT):
