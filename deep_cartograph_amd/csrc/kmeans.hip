@@ -1,11 +1,19 @@
 // k-means on the projected CVs (float64, d <= 16, k <= 64): one HBM-bound pass per Lloyd
 // iteration computing labels, per-cluster sums / counts, inertia and the number of changed
-// labels; centroid-nearest-sample search; 1-NN label transfer.
+// labels; k-means++ seeding passes; centroid-nearest-sample search; 1-NN label transfer.
 //
 // Determinism: every wave owns a private LDS accumulator, waves are combined in wave order,
 // blocks in block order, and each thread walks its points in increasing index order.
+//
+// Layout.  The shared device pieces come first, ONE copy each: block_range (a block's points), load_point (runtime d and
+// <D>), block_sum (the 256-value LDS tree), take_min / wave_min (the (distance, row) minimum), glds_stream (LDS-DMA) and the
+// two point streams reg_stream (registers: two alternating batches, the D == 4 pair path) and ring_stream (per-wave LDS-DMA
+// ring), which both call a per-point f(x, i, old).  The kernels pass what differs between them as template parameters and
+// callables.  In the C-ABI at the end a runtime d / k becomes an instantiation through for_value, and every entry reads
+// "choose kernel, blocks and LDS; launch; final".
 #include "gemm_kernels.h"   // butterfly_sum
 #include <stdlib.h>
+#include <type_traits>
 
 namespace dcv {
 
@@ -40,7 +48,56 @@ __device__ __forceinline__ void load_point(const double* __restrict__ P, int64_t
             if (c < d) x[c] = p[c];
     }
 }
+template <int D>
+__device__ __forceinline__ void load_point(const double* __restrict__ P, int64_t i, double (&x)[D]) {
+    const double* p = P + i * D;
+    if constexpr (D % 2 == 0) {
+#pragma unroll
+        for (int c = 0; c < D; c += 2) {
+            const double2 v = *reinterpret_cast<const double2*>(p + c);
+            x[c] = v.x;
+            x[c + 1] = v.y;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < D; ++c) x[c] = p[c];
+    }
+}
 
+// the block's contiguous range of points [begin, end)
+struct Range {
+    int64_t begin, end;
+};
+__device__ __forceinline__ Range block_range(int64_t n) {
+    const int64_t per_block = (n + gridDim.x - 1) / gridDim.x;
+    const int64_t begin = (int64_t)blockIdx.x * per_block;
+    return {begin, begin + per_block < n ? begin + per_block : n};
+}
+
+// s_red[0] = the sum of the block's 256 values v by a fixed LDS tree (pairs 128 apart, then 64, ...), valid after the call
+__device__ __forceinline__ void block_sum(double v, double (&s_red)[kKmThreads], int t) {
+    s_red[t] = v;
+    __syncthreads();
+    for (int o = kKmThreads / 2; o > 0; o >>= 1) {
+        if (t < o) s_red[t] += s_red[t + o];
+        __syncthreads();
+    }
+}
+// lexicographic (distance, row) minimum: the smaller distance wins, ties go to the smaller row
+__device__ __forceinline__ void take_min(double& best, int64_t& besti, double v, int64_t i) {
+    if (v < best || (v == best && i < besti)) {
+        best = v;
+        besti = i;
+    }
+}
+__device__ __forceinline__ void wave_min(double& best, int64_t& besti) {   // lane 0 ends up with the wave's minimum
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double v2 = __shfl_down(best, off, 64);
+        const int64_t i2 = __shfl_down(besti, off, 64);
+        take_min(best, besti, v2, i2);
+    }
+}
 
 // ---- D = 4 float64 coordinates = 32 bytes per point.  A lane that reads its own point issues two 16-byte loads at a
 // 32-byte lane stride: every wave-instruction touches 2 KB of lines and uses half of them (measured 3.9 - 4.2 TB/s where the
@@ -89,38 +146,28 @@ __device__ __forceinline__ void pair_finish(const PairUnits& r, int lane, double
 // waves per SIMD", item 7).  vmcnt counts loads, LDS-DMA and stores together in issue order; the loop below issues nothing
 // but its own DMAs and (k-means) ONE label store per chunk, so the number of younger operations is known exactly.
 constexpr int kRingSlots = 4;   // (k-means: 110 VGPRs -> four blocks per CU fit beside 4 x 36 KB of rings: 16 waves x 3 slots x 2.25 KB = 108 KB in flight)
-__device__ __forceinline__ void glds4(const void* gsrc, unsigned lds_wave_addr) {   // 4 bytes per lane: LDS[m0 + 4 * lane]
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dword %1, off nt\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_wave_addr)
-        : "memory");
-}
-// 16 bytes per lane, non-temporal: the points are streamed once (MI355X_MICROARCH.md, nt-weights: issue -> landed 18 % sooner
-// for once-read streams).  DCV_KM_NT=0 at build time restores the default policy.
+// LDS-DMA of BYTES per lane: LDS[m0 + BYTES * lane] <- *gsrc.  M0 carries the wave-uniform LDS byte address; it is
+// compiler-reserved, so it is saved / restored inside the same statement (see glds16, gemm.h).  NT = non-temporal: the points
+// are streamed once (MI355X_MICROARCH.md, nt-weights: issue -> landed 18 % sooner for once-read streams).  DCV_KM_NT=0 at build
+// time restores the default policy for the 16-byte point units.
 #ifndef DCV_KM_NT
 #define DCV_KM_NT 1
 #endif
-__device__ __forceinline__ void glds16_stream(const float* gsrc, unsigned lds_wave_addr) {
-#if DCV_KM_NT
+constexpr bool kKmPointsNt = DCV_KM_NT != 0;
+template <int BYTES, bool NT>
+__device__ __forceinline__ void glds_stream(const void* gsrc, unsigned lds_wave_addr) {
+    static_assert(BYTES == 4 || BYTES == 16, "glds_stream: a dword or four per lane");
     unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off nt\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_wave_addr)
-        : "memory");
-#else
-    glds16(gsrc, lds_wave_addr);
-#endif
+#define DCV_KM_GLDS(LOAD)                                                                            \
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t" LOAD "\n\ts_mov_b32 m0, %0" \
+                 : "=&s"(keep)                                                                       \
+                 : "v"(gsrc), "s"(lds_wave_addr)                                                     \
+                 : "memory")
+    if constexpr (BYTES == 16 && NT) DCV_KM_GLDS("global_load_lds_dwordx4 %1, off nt");
+    else if constexpr (BYTES == 16) DCV_KM_GLDS("global_load_lds_dwordx4 %1, off");
+    else if constexpr (NT) DCV_KM_GLDS("global_load_lds_dword %1, off nt");
+    else DCV_KM_GLDS("global_load_lds_dword %1, off");
+#undef DCV_KM_GLDS
 }
 __device__ __forceinline__ void vm_wait_dyn(int n) {   // s_waitcnt vmcnt(min(n, 31)): fewer allowed in flight only waits longer
     n = __builtin_amdgcn_readfirstlane(n);   // wave-uniform by construction: a scalar branch, not an exec-masked tree
@@ -154,12 +201,12 @@ __device__ __forceinline__ void ring_stream(const double* __restrict__ P, const 
         for (int u = 0; u < UNITS; ++u) {
             int64_t off = cb * (int64_t)(D * 8) + u * 1024 + lane * 16;
             off = off < max_off ? off : max_off;   // units past the block's range re-read its last unit (never used)
-            glds16_stream(reinterpret_cast<const float*>(Pb + off), slot + u * 1024);
+            glds_stream<16, kKmPointsNt>(Pb + off, slot + u * 1024);
         }
         if constexpr (LABELS) {
             int64_t li = cb + lane;
             li = li < end ? li : end - 1;
-            glds4(labels + li, slot + UNITS * 1024);
+            glds_stream<4, true>(labels + li, slot + UNITS * 1024);
         }
     };
     for (int64_t kk = 0; kk < kRingSlots - 1 && kk < nw; ++kk) issue(kk);
@@ -188,6 +235,70 @@ __device__ __forceinline__ void ring_stream(const double* __restrict__ P, const 
 }
 template <int D, bool LABELS>
 constexpr size_t ring_lds_bytes() { return (size_t)4 * kRingSlots * ((D / 2) * 1024 + (LABELS ? 256 : 0)); }
+
+// The same stream through registers, for any D: f(x, i, old) as above for every valid point of [begin, end).  A batch = U
+// points per thread, requested together before any of them is used (with one point per thread in flight a wave keeps 2 KB
+// outstanding and a pass is bound by load latency: 1.4 TB/s, not by HBM).  TWO batches alternate: the loads of the next one
+// are issued before the current one is computed, so a wave has memory requests in flight while it computes (one batch at a
+// time left the k-means pass at the SUM of its load latency and its ~150 float64 instructions per point: 3.8 TB/s, round 3).
+// D == 4 reads contiguous 16-byte units and swaps halves between lane pairs (pair_issue / pair_finish): wave w takes the
+// 64-point chunks w, w + 4, ...; any other D reads the lane's own points, thread-strided.
+template <int D, int U, bool LABELS, class F>
+__device__ __forceinline__ void reg_stream(const double* P, const int32_t* labels, int64_t begin, int64_t end, int t, F&& f) {
+    const int lane = t & 63, wave = t >> 6;
+    struct Batch {
+        PairUnits pu[U];      // D == 4: contiguous 16-byte units
+        double xs[U][D];      // other D: the lane's own points
+        int32_t olds[U];      // LABELS: the points' previous labels
+    };
+    const int64_t nchunk = (end - begin + 63) / 64;
+    const int64_t step = D == 4 ? 4 * U : (int64_t)kKmThreads * U;                    // batch stride in chunks / points
+    const int64_t first = D == 4 ? wave : begin + t, last = D == 4 ? nchunk : end;   // batch positions of this wave / thread
+    auto issue = [&](Batch& b, int64_t pos) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if constexpr (D == 4) {
+                const int64_t cb = begin + (pos + 4 * u) * 64;
+                pair_issue(P, cb, end, lane, b.pu[u]);
+                if constexpr (LABELS) {
+                    const int64_t i = pair_point(cb, lane);
+                    b.olds[u] = labels[i < end ? i : end - 1];
+                }
+            } else {
+                const int64_t i = pos + (int64_t)u * kKmThreads;
+                const int64_t ic = i < end ? i : end - 1;   // unconditional loads from a clamped index (see pair_issue)
+                load_point<D>(P, ic, b.xs[u]);
+                if constexpr (LABELS) b.olds[u] = labels[ic];
+            }
+        }
+    };
+    auto process = [&](Batch& b, int64_t pos) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            int32_t old = 0;
+            if constexpr (LABELS) old = b.olds[u];
+            if constexpr (D == 4) {
+                const int64_t cb = begin + (pos + 4 * u) * 64;
+                double x[D];
+                pair_finish(b.pu[u], lane, x);   // every lane of the wave takes part in the swap: before the i < end test
+                const int64_t i = pair_point(cb, lane);
+                if (i < end) f(x, i, old);
+            } else {
+                const int64_t i = pos + (int64_t)u * kKmThreads;
+                if (i < end) f(b.xs[u], i, old);
+            }
+        }
+    };
+    Batch ba, bb;
+    int64_t pos = first;
+    if (pos < last) issue(ba, pos);
+    for (; pos < last; pos += 2 * step) {
+        if (pos + step < last) issue(bb, pos + step);
+        process(ba, pos);
+        if (pos + 2 * step < last) issue(ba, pos + 2 * step);
+        if (pos + step < last) process(bb, pos + step);
+    }
+}
 
 // acc layout per block: [sums k*d | counts k | inertia | changed]
 __global__ __launch_bounds__(kKmThreads) void kmeans_step_kernel(const double* __restrict__ P, int64_t n, int d,
@@ -221,10 +332,8 @@ __global__ __launch_bounds__(kKmThreads) void kmeans_step_kernel(const double* _
     double inertia = 0.0;
     double changed = 0.0;
     // contiguous block of points per workgroup, thread-strided inside
-    const int64_t per_block = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t begin = (int64_t)blockIdx.x * per_block;
-    const int64_t end = begin + per_block < n ? begin + per_block : n;
-    for (int64_t i = begin + t; i < end; i += kKmThreads) {
+    const Range r = block_range(n);
+    for (int64_t i = r.begin + t; i < r.end; i += kKmThreads) {
         double x[kKmMaxD];
         load_point(P, i, d, x);
         if (offset) {
@@ -304,12 +413,7 @@ __global__ __launch_bounds__(kKmThreads, (KMAX * (D + 1) > 48 ? 1 : 2)) void kme
     double acc[WR];
 #pragma unroll
     for (int i = 0; i < WR; ++i) acc[i] = 0.0;
-    const int64_t per_block = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t begin = (int64_t)blockIdx.x * per_block;
-    const int64_t end = begin + per_block < n ? begin + per_block : n;
-    // U points per thread are requested before any of them is used: with one point per thread in flight a wave keeps
-    // 2 KB outstanding and the pass is bound by load latency (1.4 TB/s), not by HBM
-    constexpr int U = 2;   // points per thread and batch; two batches alternate (below): four points in flight, two waves per SIMD
+    const Range r = block_range(n);
     // one point: label, inertia, changed count, sums (the arithmetic is the same whichever way the point was loaded)
     auto take_point = [&](const double (&xr)[D], int64_t i, int32_t old) {
         double x[D];
@@ -356,80 +460,13 @@ __global__ __launch_bounds__(kKmThreads, (KMAX * (D + 1) > 48 ? 1 : 2)) void kme
             }
         }
     };
-    // A batch = U points per thread, requested together.  TWO batches alternate: the loads of the next one are issued before the
-    // current one is computed, so a wave has memory requests in flight while it computes (one batch at a time left the pass at
-    // the SUM of its load latency and its ~150 float64 instructions per point: 3.8 TB/s, round 3).
-    struct Batch {
-        PairUnits pu[U];      // D == 4: contiguous 16-byte units, halves swapped between lane pairs (pair_issue / pair_finish)
-        double xs[U][D];      // other D: the lane's own points
-        int32_t olds[U];
-    };
-    const int64_t nchunk = (end - begin + 63) / 64;                                  // D == 4: 64-point chunks, wave w takes w, w + 4, ...
-    const int64_t step = D == 4 ? 4 * U : (int64_t)kKmThreads * U;                    // batch stride in chunks / points
-    const int64_t first = D == 4 ? wave : begin + t, last = D == 4 ? nchunk : end;   // batch positions of this wave / thread
-    auto issue = [&](Batch& b, int64_t pos) {
-        if constexpr (D == 4) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t cb = begin + (pos + 4 * u) * 64;
-                pair_issue(P, cb, end, lane, b.pu[u]);
-                const int64_t i = pair_point(cb, lane);
-                b.olds[u] = labels[i < end ? i : end - 1];
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t i = pos + (int64_t)u * kKmThreads;
-                const int64_t ic = i < end ? i : end - 1;   // unconditional loads from a clamped index (see pair_issue)
-                const double* p = P + ic * D;
-                if constexpr (D % 2 == 0) {
-#pragma unroll
-                    for (int c = 0; c < D; c += 2) {
-                        const double2 v = *reinterpret_cast<const double2*>(p + c);
-                        b.xs[u][c] = v.x;
-                        b.xs[u][c + 1] = v.y;
-                    }
-                } else {
-#pragma unroll
-                    for (int c = 0; c < D; ++c) b.xs[u][c] = p[c];
-                }
-                b.olds[u] = labels[ic];
-            }
-        }
-    };
-    auto process = [&](Batch& b, int64_t pos) {
-        if constexpr (D == 4) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t cb = begin + (pos + 4 * u) * 64;
-                double xr[D];
-                pair_finish(b.pu[u], lane, xr);   // every lane of the wave takes part in the swap
-                const int64_t i = pair_point(cb, lane);
-                if (i < end) take_point(xr, i, b.olds[u]);
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t i = pos + (int64_t)u * kKmThreads;
-                if (i < end) take_point(b.xs[u], i, b.olds[u]);
-            }
-        }
-    };
+    // U = 2 points per thread and batch (reg_stream): four points in flight, two waves per SIMD
     if constexpr (RING && (D == 2 || D == 4)) {
-        // the point stream through the wave's LDS-DMA ring (ring_stream above): launched when mindist == nullptr, so the only
-        // vector-memory store per chunk is the label store of take_point
+        // launched when mindist == nullptr, so the only vector-memory store per chunk is the label store of take_point
         extern __shared__ __attribute__((aligned(16))) char s_ring[];
-        ring_stream<D, true>(P, labels, begin, end, s_ring, wave, lane, 1, [&](const double (&xr)[D], int64_t i, int32_t old) { take_point(xr, i, old); });
+        ring_stream<D, true>(P, labels, r.begin, r.end, s_ring, wave, lane, 1, take_point);
     } else {
-        Batch ba, bb;
-        int64_t pos = first;
-        if (pos < last) issue(ba, pos);
-        for (; pos < last; pos += 2 * step) {
-            if (pos + step < last) issue(bb, pos + step);
-            process(ba, pos);
-            if (pos + 2 * step < last) issue(ba, pos + 2 * step);
-            if (pos + step < last) process(bb, pos + step);
-        }
+        reg_stream<D, 2, true>(P, labels, r.begin, r.end, t, take_point);
     }
     {
         int base = 0, dup = 0;
@@ -448,41 +485,6 @@ __global__ __launch_bounds__(kKmThreads, (KMAX * (D + 1) > 48 ? 1 : 2)) void kme
         my_part[i] = ((s_red[0][src] + s_red[1][src]) + s_red[2][src]) + s_red[3][src];
     }
 }
-typedef void (*km_reg_fn_t)(const double*, int64_t, const double*, const double*, int, int32_t*, double*, double*);
-template <int KM>
-static km_reg_fn_t km_reg_fn_d(int d, bool ring) {
-    if (ring && KM <= 8) {   // (9 .. 16 clusters: the register form; its accumulators leave one wave per SIMD anyway)
-        if (d == 2) return kmeans_step_reg_kernel<2, KM, true>;
-        if (d == 4) return kmeans_step_reg_kernel<4, KM, true>;
-    }
-    switch (d) {
-        case 1: return kmeans_step_reg_kernel<1, KM>;
-        case 2: return kmeans_step_reg_kernel<2, KM>;
-        case 3: return kmeans_step_reg_kernel<3, KM>;
-        case 4: return kmeans_step_reg_kernel<4, KM>;
-        default: return nullptr;
-    }
-}
-// k <= 8: an instantiation for the exact cluster count (the `j < k` tests of a padded count were 158 scalar branches in the
-// point loop of the D = 4, KMAX = 8 kernel: every unrolled centroid its own basic block); 9 .. 16 clusters share KMAX = 16
-static km_reg_fn_t km_reg_fn(int d, int k, bool ring) {
-    switch (k) {
-        case 1: return km_reg_fn_d<1>(d, ring);
-        case 2: return km_reg_fn_d<2>(d, ring);
-        case 3: return km_reg_fn_d<3>(d, ring);
-        case 4: return km_reg_fn_d<4>(d, ring);
-        case 5: return km_reg_fn_d<5>(d, ring);
-        case 6: return km_reg_fn_d<6>(d, ring);
-        case 7: return km_reg_fn_d<7>(d, ring);
-        case 8: return km_reg_fn_d<8>(d, ring);
-        default: return k <= 16 ? km_reg_fn_d<16>(d, false) : nullptr;
-    }
-}
-static bool km_ring_enabled() {
-    static const bool on = [] { const char* e = getenv("DCV_KM_RING"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 // acc[i] = sum over the blocks of part[b][i]: one workgroup per output, its threads take b = t, t + 256, ... (all loads
 // in flight at once; one thread walking 1024 partials with dependent loads cost 0.4 ms -- most of the pass) and a fixed
 // LDS tree adds them up.
@@ -491,12 +493,7 @@ __global__ __launch_bounds__(256) void kmeans_final_kernel(const double* __restr
     const int i = blockIdx.x, t = threadIdx.x;
     double s = 0.0;
     for (int b = t; b < nblocks; b += 256) s += part[(int64_t)b * width + i];
-    s_red[t] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) s_red[t] += s_red[t + o];
-        __syncthreads();
-    }
+    block_sum(s, s_red, t);
     if (t == 0) acc[i] = s_red[0];
 }
 
@@ -521,18 +518,9 @@ __device__ __forceinline__ double pp_dist(const double (&x)[D], const double* __
 }
 template <int D>
 __device__ __forceinline__ void pp_load(const double* __restrict__ P, int64_t i, const double* off, double (&x)[D]) {
-    const double* p = P + i * D;
-    if constexpr (D % 2 == 0) {
+    load_point<D>(P, i, x);
 #pragma unroll
-        for (int c = 0; c < D; c += 2) {
-            const double2 v = *reinterpret_cast<const double2*>(p + c);
-            x[c] = v.x - off[c];
-            x[c + 1] = v.y - off[c + 1];
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < D; ++c) x[c] = p[c] - off[c];
-    }
+    for (int c = 0; c < D; ++c) x[c] -= off[c];
 }
 // part[block][t] = sum over the block's points of min(closest_i, dist(x_i, cand_t))
 template <int D>
@@ -559,10 +547,8 @@ __global__ __launch_bounds__(kKmThreads) void kmeanspp_potentials_kernel(const d
     double acc[kPpMaxTrials];
 #pragma unroll
     for (int q = 0; q < kPpMaxTrials; ++q) acc[q] = 0.0;
-    const int64_t per_block = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t begin = (int64_t)blockIdx.x * per_block;
-    const int64_t end = begin + per_block < n ? begin + per_block : n;
-    for (int64_t i = begin + t; i < end; i += kKmThreads) {
+    const Range r = block_range(n);
+    for (int64_t i = r.begin + t; i < r.end; i += kKmThreads) {
         double x[D];
         pp_load<D>(P, i, off, x);
         const double cl = closest[i];
@@ -574,12 +560,7 @@ __global__ __launch_bounds__(kKmThreads) void kmeanspp_potentials_kernel(const d
             }
     }
     for (int q = 0; q < T; ++q) {
-        s_red[t] = acc[q];
-        __syncthreads();
-        for (int o = kKmThreads / 2; o > 0; o >>= 1) {
-            if (t < o) s_red[t] += s_red[t + o];
-            __syncthreads();
-        }
+        block_sum(acc[q], s_red, t);
         if (t == 0) part[(int64_t)blockIdx.x * T + q] = s_red[0];
         __syncthreads();
     }
@@ -601,10 +582,8 @@ __global__ __launch_bounds__(kKmThreads) void kmeanspp_update_kernel(const doubl
         cc = fma(c[q], c[q], cc);
     }
     double acc = 0.0;
-    const int64_t per_block = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t begin = (int64_t)blockIdx.x * per_block;
-    const int64_t end = begin + per_block < n ? begin + per_block : n;
-    for (int64_t i = begin + t; i < end; i += kKmThreads) {
+    const Range r = block_range(n);
+    for (int64_t i = r.begin + t; i < r.end; i += kKmThreads) {
         double x[D];
         pp_load<D>(P, i, off, x);
         double v = pp_dist<D>(x, c, cc);
@@ -615,12 +594,7 @@ __global__ __launch_bounds__(kKmThreads) void kmeanspp_update_kernel(const doubl
         closest[i] = v;
         acc += v;
     }
-    s_red[t] = acc;
-    __syncthreads();
-    for (int o = kKmThreads / 2; o > 0; o >>= 1) {
-        if (t < o) s_red[t] += s_red[t + o];
-        __syncthreads();
-    }
+    block_sum(acc, s_red, t);
     if (t == 0) part[blockIdx.x] = s_red[0];
 }
 
@@ -675,12 +649,10 @@ __global__ __launch_bounds__(kKmThreads) void nearest_rows_kernel(const double* 
     double c[kKmMaxD];
 #pragma unroll
     for (int q = 0; q < kKmMaxD; ++q) c[q] = q < d ? centers[j * d + q] : 0.0;
-    const int64_t per_block = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t begin = (int64_t)blockIdx.x * per_block;
-    const int64_t end = begin + per_block < n ? begin + per_block : n;
+    const Range r = block_range(n);
     double best = INFINITY;
     int64_t besti = INT64_MAX;
-    for (int64_t i = begin + t; i < end; i += kKmThreads) {
+    for (int64_t i = r.begin + t; i < r.end; i += kKmThreads) {
         double x[kKmMaxD];
         load_point(P, i, d, x);
         const double v = np_norm(x, c, d);
@@ -693,14 +665,7 @@ __global__ __launch_bounds__(kKmThreads) void nearest_rows_kernel(const double* 
     s_i[t] = besti;
     __syncthreads();
     for (int off = kKmThreads / 2; off > 0; off >>= 1) {
-        if (t < off) {
-            const double od = s_d[t + off];
-            const int64_t oi = s_i[t + off];
-            if (od < s_d[t] || (od == s_d[t] && oi < s_i[t])) {
-                s_d[t] = od;
-                s_i[t] = oi;
-            }
-        }
+        if (t < off) take_min(s_d[t], s_i[t], s_d[t + off], s_i[t + off]);
         __syncthreads();
     }
     if (t == 0) {
@@ -719,7 +684,7 @@ constexpr int kNearKC = 8;
 template <int D, bool RING = false, int KX = 0>
 __global__ __launch_bounds__(kKmThreads) void nearest_rows_multi_kernel(const double* __restrict__ P, int64_t n, const double* __restrict__ centers,
                                                                         int k, double* __restrict__ pdist, int64_t* __restrict__ prow) {
-    constexpr int KC = KX > 0 ? KX : kNearKC, U = 4;
+    constexpr int KC = KX > 0 ? KX : kNearKC;
     __shared__ double s_c[KC][D];
     __shared__ double s_d[4][KC];
     __shared__ int64_t s_i[4][KC];
@@ -739,11 +704,9 @@ __global__ __launch_bounds__(kKmThreads) void nearest_rows_multi_kernel(const do
         bthr[j] = INFINITY;
         besti[j] = INT64_MAX;
     }
-    const int64_t per_block = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t begin = (int64_t)blockIdx.x * per_block;
-    const int64_t end = begin + per_block < n ? begin + per_block : n;
+    const Range r = block_range(n);
     // one point against the chunk's centroids
-    auto take_point = [&](const double (&xr)[D], int64_t i) {
+    auto take_point = [&](const double (&xr)[D], int64_t i, int32_t) {
 #pragma unroll
         for (int j = 0; j < KC; ++j) {
             if (KX > 0 || j < kc) {
@@ -772,82 +735,18 @@ __global__ __launch_bounds__(kKmThreads) void nearest_rows_multi_kernel(const do
             }
         }
     };
-    // two alternating batches of U points per thread: the next one's loads are in flight while this one is compared (see
-    // kmeans_step_reg_kernel); D == 4 reads contiguous 16-byte units and swaps halves between lane pairs
-    struct Batch {
-        PairUnits pu[U];
-        double xs[U][D];
-    };
-    const int64_t nchunk = (end - begin + 63) / 64;
-    const int64_t step = D == 4 ? 4 * U : (int64_t)kKmThreads * U;
-    const int64_t first = D == 4 ? wave : begin + t, last = D == 4 ? nchunk : end;
-    auto issue = [&](Batch& b, int64_t pos) {
-        if constexpr (D == 4) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) pair_issue(P, begin + (pos + 4 * u) * 64, end, lane, b.pu[u]);
-        } else {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t i = pos + (int64_t)u * kKmThreads;
-                const double* p = P + (i < end ? i : end - 1) * D;
-                if constexpr (D % 2 == 0) {
-#pragma unroll
-                    for (int q = 0; q < D; q += 2) {
-                        const double2 v = *reinterpret_cast<const double2*>(p + q);
-                        b.xs[u][q] = v.x;
-                        b.xs[u][q + 1] = v.y;
-                    }
-                } else {
-#pragma unroll
-                    for (int q = 0; q < D; ++q) b.xs[u][q] = p[q];
-                }
-            }
-        }
-    };
-    auto process = [&](Batch& b, int64_t pos) {
-        if constexpr (D == 4) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                double xr[D];
-                pair_finish(b.pu[u], lane, xr);
-                const int64_t i = pair_point(begin + (pos + 4 * u) * 64, lane);
-                if (i < end) take_point(xr, i);
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t i = pos + (int64_t)u * kKmThreads;
-                if (i < end) take_point(b.xs[u], i);
-            }
-        }
-    };
-    if constexpr (RING && (D == 2 || D == 4)) {   // the point stream through the wave's LDS-DMA ring (ring_stream): no store in the loop
+    // U = 4 points per thread and batch (reg_stream); the ring issues no store in its loop
+    if constexpr (RING && (D == 2 || D == 4)) {
         extern __shared__ __attribute__((aligned(16))) char s_ring[];
-        ring_stream<D, false>(P, nullptr, begin, end, s_ring, wave, lane, 0, [&](const double (&xr)[D], int64_t i, int32_t) { take_point(xr, i); });
+        ring_stream<D, false>(P, nullptr, r.begin, r.end, s_ring, wave, lane, 0, take_point);
     } else {
-        Batch ba, bb;
-        int64_t pos = first;
-        if (pos < last) issue(ba, pos);
-        for (; pos < last; pos += 2 * step) {
-            if (pos + step < last) issue(bb, pos + step);
-            process(ba, pos);
-            if (pos + 2 * step < last) issue(ba, pos + 2 * step);
-            if (pos + step < last) process(bb, pos + step);
-        }
+        reg_stream<D, 4, false>(P, nullptr, r.begin, r.end, t, take_point);
     }
 #pragma unroll
     for (int j = 0; j < KC; ++j) {
         double b = __dsqrt_rn(best[j]);   // from here on the rounded distances, as numpy's argmin sees them
         int64_t bi = besti[j];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double v2 = __shfl_down(b, off, 64);
-            const int64_t i2 = __shfl_down(bi, off, 64);
-            if (v2 < b || (v2 == b && i2 < bi)) {
-                b = v2;
-                bi = i2;
-            }
-        }
+        wave_min(b, bi);
         if (lane == 0) {
             s_d[wave][j] = b;
             s_i[wave][j] = bi;
@@ -858,14 +757,7 @@ __global__ __launch_bounds__(kKmThreads) void nearest_rows_multi_kernel(const do
         double b = s_d[0][t];
         int64_t bi = s_i[0][t];
 #pragma unroll
-        for (int w = 1; w < 4; ++w) {
-            const double v2 = s_d[w][t];
-            const int64_t i2 = s_i[w][t];
-            if (v2 < b || (v2 == b && i2 < bi)) {
-                b = v2;
-                bi = i2;
-            }
-        }
+        for (int w = 1; w < 4; ++w) take_min(b, bi, s_d[w][t], s_i[w][t]);
         pdist[(int64_t)(j0 + t) * gridDim.x + blockIdx.x] = b;
         prow[(int64_t)(j0 + t) * gridDim.x + blockIdx.x] = bi;
     }
@@ -892,20 +784,9 @@ __global__ __launch_bounds__(64) void nearest_rows_final(const double* __restric
             i[u] = b < nblocks ? pr[b] : INT64_MAX;
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (v[u] < best || (v[u] == best && i[u] < besti)) {
-                best = v[u];
-                besti = i[u];
-            }
+        for (int u = 0; u < 4; ++u) take_min(best, besti, v[u], i[u]);
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        const double v2 = __shfl_down(best, off, 64);
-        const int64_t i2 = __shfl_down(besti, off, 64);
-        if (v2 < best || (v2 == best && i2 < besti)) {
-            best = v2;
-            besti = i2;
-        }
-    }
+    wave_min(best, besti);
     if (lane == 0) {
         dist[j] = best;
         rows[j] = besti == INT64_MAX ? -1 : besti + row_offset;
@@ -948,6 +829,57 @@ __global__ __launch_bounds__(kKmThreads) void nearest_point_kernel(const double*
     if (i < n_sup) nn[i] = besti;
 }
 
+// ------------------------------------------------------------------ host: runtime value -> instantiation
+// f(std::integral_constant<int, v>) for a runtime v in 1 .. N, a value-initialised result (null kernel) for any other v
+template <int N, class F>
+static auto for_value(int v, F&& f) -> decltype(f(std::integral_constant<int, 1>{})) {
+    if constexpr (N == 0) return {};
+    else return v == N ? f(std::integral_constant<int, N>{}) : for_value<N - 1>(v, f);
+}
+template <class Fn>
+struct Pick {   // a kernel and the dynamic LDS it is launched with; fn == nullptr: no instantiation for the shape
+    Fn fn;
+    size_t lds;
+};
+static bool env_starts_with(const char* name, char c) {   // callers keep the answer in a static: every flag is read once
+    const char* e = getenv(name);
+    return e && e[0] == c;
+}
+static bool km_ring_enabled() {
+    static const bool on = !env_starts_with("DCV_KM_RING", '0');
+    return on;
+}
+
+// The register Lloyd kernel for d <= 4, k <= 16.  k <= 8: an instantiation for the exact cluster count (the `j < k` tests of a
+// padded count were 158 scalar branches in the point loop of the D = 4, KMAX = 8 kernel: every unrolled centroid its own basic
+// block); 9 .. 16 clusters share KMAX = 16 and keep the register stream (their accumulators leave one wave per SIMD anyway).
+typedef Pick<decltype(&kmeans_step_reg_kernel<1, 1>)> KmRegPick;
+static KmRegPick km_reg_pick(int d, int k, bool ring) {
+    auto by_d = [&](auto KM) {
+        return for_value<4>(d, [&](auto D) -> KmRegPick {
+            if constexpr (D() % 2 == 0)
+                if (ring && KM() <= 8) return {kmeans_step_reg_kernel<D(), KM(), true>, ring_lds_bytes<D(), true>()};
+            return {kmeans_step_reg_kernel<D(), KM()>, 0};
+        });
+    };
+    return k <= 8 ? for_value<8>(k, by_d) : k <= 16 ? by_d(std::integral_constant<int, 16>{}) : KmRegPick{};
+}
+// The one-pass nearest-rows kernel for d <= 4; through the ring at d = 4 one chunk of exactly k <= kNearKC centroids
+typedef Pick<decltype(&nearest_rows_multi_kernel<1>)> NearPick;
+static NearPick near_multi_pick(int d, int k, bool ring) {
+    return for_value<4>(d, [&](auto D) -> NearPick {
+        if constexpr (D() % 2 == 0) {
+            if (ring) {
+                NearPick p = {nearest_rows_multi_kernel<D(), true>, ring_lds_bytes<D(), false>()};
+                if constexpr (D() == 4)
+                    if (k <= kNearKC) p.fn = for_value<kNearKC>(k, [](auto K) { return &nearest_rows_multi_kernel<4, true, K()>; });
+                return p;
+            }
+        }
+        return {nearest_rows_multi_kernel<D()>, 0};
+    });
+}
+
 }  // namespace dcv
 
 using namespace dcv;
@@ -964,31 +896,26 @@ extern "C" int dcv_kmeans_step(const double* P_d, int64_t n, int32_t d, const do
     DCV_REQUIRE(d >= 1 && d <= kKmMaxD && k >= 1 && k <= kKmMaxK, "dcv_kmeans_step: d=%d (1..16) k=%d (1..64) unsupported", d, k);
     DCV_REQUIRE(ws_d && ws_bytes >= dcv_kmeans_workspace(n, d, k), "dcv_kmeans_step: workspace too small");
     hipStream_t s = as_stream(stream);
-    const int nb = km_blocks(n);
+    int nb = km_blocks(n);
     const int W = k * d + k;
-    const size_t lds = ((size_t)k * d + k + 4 * W + 2 * kKmThreads) * sizeof(double);
     double* part = static_cast<double*>(ws_d);
-    static const bool no_reg = [] { const char* e = getenv("DCV_KMEANS_ATOMIC"); return e && e[0] == '1'; }();   // diagnostic: general kernel
-    const bool ring = km_ring_enabled() && mindist_d == nullptr && (d == 2 || d == 4) && k <= 8;
-    const size_t ring_lds = ring ? (d == 4 ? ring_lds_bytes<4, true>() : ring_lds_bytes<2, true>()) : 0;
-    if (km_reg_fn_t reg = no_reg ? nullptr : km_reg_fn(d, k, ring)) {
+    static const bool no_reg = env_starts_with("DCV_KMEANS_ATOMIC", '1');   // diagnostic: general kernel
+    const KmRegPick reg = no_reg ? KmRegPick{} : km_reg_pick(d, k, km_ring_enabled() && mindist_d == nullptr);
+    if (reg.fn) {
         // One round of the chip: the register kernel holds ~150 VGPRs (3 blocks per CU), and 1024 equal blocks on 768
         // slots is two rounds with the second a third full (3.5 TB/s).  Blocks = CUs x resident blocks per CU.
-        int nbr = nb;
         int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(reg), kKmThreads, ring_lds) == hipSuccess && per_cu > 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(reg.fn), kKmThreads, reg.lds) == hipSuccess && per_cu > 0) {
             const int64_t one_round = (int64_t)num_cus() * per_cu;
-            if (nbr > one_round) nbr = (int)one_round;
+            if (nb > one_round) nb = (int)one_round;
         } else {
             (void)hipGetLastError();
         }
-        hipLaunchKernelGGL(reg, dim3(nbr), dim3(kKmThreads), ring_lds, s, P_d, n, offset_d, centers_d, (int)k, labels_d, mindist_d, part);
-        DCV_CHECK_LAUNCH();
-        hipLaunchKernelGGL(kmeans_final_kernel, dim3(W + 2), dim3(256), 0, s, part, nbr, W + 2, acc_d);
-        DCV_CHECK_LAUNCH();
-        return DCV_OK;
-    } else
+        hipLaunchKernelGGL(reg.fn, dim3(nb), dim3(kKmThreads), reg.lds, s, P_d, n, offset_d, centers_d, (int)k, labels_d, mindist_d, part);
+    } else {
+        const size_t lds = ((size_t)k * d + k + 4 * W + 2 * kKmThreads) * sizeof(double);
         hipLaunchKernelGGL(kmeans_step_kernel, dim3(nb), dim3(kKmThreads), lds, s, P_d, n, d, offset_d, centers_d, k, labels_d, mindist_d, part);
+    }
     DCV_CHECK_LAUNCH();
     hipLaunchKernelGGL(kmeans_final_kernel, dim3(W + 2), dim3(256), 0, s, part, nb, W + 2, acc_d);
     DCV_CHECK_LAUNCH();
@@ -1011,32 +938,12 @@ extern "C" int dcv_nearest_rows(const double* P_d, int64_t n, int32_t d, const d
     const int nb = km_blocks(n);
     double* pdist = static_cast<double*>(ws_d);
     int64_t* prow = reinterpret_cast<int64_t*>(pdist + (size_t)kKmMaxBlocks * k);
-    static const bool multi_off = [] { const char* e = getenv("DCV_NEAREST_PER_CENTROID"); return e && e[0] == '1'; }();
-    const dim3 gm(nb, (unsigned)cdiv(k, kNearKC));
-    if (d <= 4 && !multi_off) {   // one pass over the points per chunk of kNearKC centroids
-        const bool ring = km_ring_enabled();
-        const size_t rl2 = ring_lds_bytes<2, false>(), rl4 = ring_lds_bytes<4, false>();
-        switch (d) {
-            case 1: hipLaunchKernelGGL(nearest_rows_multi_kernel<1>, gm, dim3(kKmThreads), 0, s, P_d, n, centers_d, (int)k, pdist, prow); break;
-            case 2:
-                if (ring) hipLaunchKernelGGL((nearest_rows_multi_kernel<2, true>), gm, dim3(kKmThreads), rl2, s, P_d, n, centers_d, (int)k, pdist, prow);
-                else hipLaunchKernelGGL(nearest_rows_multi_kernel<2>, gm, dim3(kKmThreads), 0, s, P_d, n, centers_d, (int)k, pdist, prow);
-                break;
-            case 3: hipLaunchKernelGGL(nearest_rows_multi_kernel<3>, gm, dim3(kKmThreads), 0, s, P_d, n, centers_d, (int)k, pdist, prow); break;
-            default:
-                if (ring && k <= kNearKC) {   // one chunk of exactly k centroids
-                    switch (k) {
-#define DCV_NR4(K) case K: hipLaunchKernelGGL((nearest_rows_multi_kernel<4, true, K>), gm, dim3(kKmThreads), rl4, s, P_d, n, centers_d, (int)k, pdist, prow); break;
-                        DCV_NR4(1) DCV_NR4(2) DCV_NR4(3) DCV_NR4(4) DCV_NR4(5) DCV_NR4(6) DCV_NR4(7) DCV_NR4(8)
-#undef DCV_NR4
-                    }
-                } else if (ring) hipLaunchKernelGGL((nearest_rows_multi_kernel<4, true>), gm, dim3(kKmThreads), rl4, s, P_d, n, centers_d, (int)k, pdist, prow);
-                else hipLaunchKernelGGL(nearest_rows_multi_kernel<4>, gm, dim3(kKmThreads), 0, s, P_d, n, centers_d, (int)k, pdist, prow);
-                break;
-        }
-    } else {
+    static const bool multi_off = env_starts_with("DCV_NEAREST_PER_CENTROID", '1');
+    const NearPick multi = multi_off ? NearPick{} : near_multi_pick(d, k, km_ring_enabled());
+    if (multi.fn)   // one pass over the points per chunk of kNearKC centroids
+        hipLaunchKernelGGL(multi.fn, dim3(nb, (unsigned)cdiv(k, kNearKC)), dim3(kKmThreads), multi.lds, s, P_d, n, centers_d, (int)k, pdist, prow);
+    else
         hipLaunchKernelGGL(nearest_rows_kernel, dim3(nb, k), dim3(kKmThreads), 0, s, P_d, n, d, centers_d, pdist, prow);
-    }
     DCV_CHECK_LAUNCH();
     hipLaunchKernelGGL(nearest_rows_final, dim3((unsigned)k), dim3(64), 0, s, pdist, prow, nb, k, row_offset, dist_d, rows_d);
     DCV_CHECK_LAUNCH();
@@ -1055,27 +962,6 @@ extern "C" int dcv_nearest_point(const double* train_d, int64_t n_train, const d
 }
 
 // ------------------------------------------------------------------ k-means++ seeding (C-ABI)
-#define DCV_PP_DISPATCH(KERNEL, ...)                                                                   \
-    switch (d) {                                                                                      \
-        case 1: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break;                                    \
-        case 2: hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); break;                                    \
-        case 3: hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); break;                                    \
-        case 4: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break;                                    \
-        case 5: hipLaunchKernelGGL(KERNEL<5>, __VA_ARGS__); break;                                    \
-        case 6: hipLaunchKernelGGL(KERNEL<6>, __VA_ARGS__); break;                                    \
-        case 7: hipLaunchKernelGGL(KERNEL<7>, __VA_ARGS__); break;                                    \
-        case 8: hipLaunchKernelGGL(KERNEL<8>, __VA_ARGS__); break;                                    \
-        case 9: hipLaunchKernelGGL(KERNEL<9>, __VA_ARGS__); break;                                    \
-        case 10: hipLaunchKernelGGL(KERNEL<10>, __VA_ARGS__); break;                                  \
-        case 11: hipLaunchKernelGGL(KERNEL<11>, __VA_ARGS__); break;                                  \
-        case 12: hipLaunchKernelGGL(KERNEL<12>, __VA_ARGS__); break;                                  \
-        case 13: hipLaunchKernelGGL(KERNEL<13>, __VA_ARGS__); break;                                  \
-        case 14: hipLaunchKernelGGL(KERNEL<14>, __VA_ARGS__); break;                                  \
-        case 15: hipLaunchKernelGGL(KERNEL<15>, __VA_ARGS__); break;                                  \
-        case 16: hipLaunchKernelGGL(KERNEL<16>, __VA_ARGS__); break;                                  \
-        default: set_error("k-means++ passes: d=%d (1..16) unsupported", d); return DCV_EINVAL;       \
-    }
-
 extern "C" size_t dcv_kmeanspp_workspace(int64_t n, int32_t trials) {
     if (n <= 0 || trials <= 0) return 0;
     return (size_t)kKmMaxBlocks * (size_t)(trials > 1 ? trials : 1) * sizeof(double);
@@ -1089,7 +975,9 @@ extern "C" int dcv_kmeanspp_potentials(const double* P_d, int64_t n, int32_t d, 
     hipStream_t s = as_stream(stream);
     const int nb = km_blocks(n);
     double* part = static_cast<double*>(ws_d);
-    DCV_PP_DISPATCH(kmeanspp_potentials_kernel, dim3(nb), dim3(kKmThreads), 0, s, P_d, n, offset_d, cand_d, (int)trials, closest_d, part)
+    const auto kern = for_value<kKmMaxD>(d, [](auto D) { return &kmeanspp_potentials_kernel<D()>; });
+    DCV_REQUIRE(kern, "k-means++ passes: d=%d (1..16) unsupported", d);
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(kKmThreads), 0, s, P_d, n, offset_d, cand_d, (int)trials, closest_d, part);
     DCV_CHECK_LAUNCH();
     hipLaunchKernelGGL(kmeans_final_kernel, dim3((unsigned)trials), dim3(256), 0, s, part, nb, (int)trials, pot_d);
     DCV_CHECK_LAUNCH();
@@ -1103,7 +991,9 @@ extern "C" int dcv_kmeanspp_update(const double* P_d, int64_t n, int32_t d, cons
     hipStream_t s = as_stream(stream);
     const int nb = km_blocks(n);
     double* part = static_cast<double*>(ws_d);
-    DCV_PP_DISPATCH(kmeanspp_update_kernel, dim3(nb), dim3(kKmThreads), 0, s, P_d, n, offset_d, centre_d, (int)first, closest_d, part)
+    const auto kern = for_value<kKmMaxD>(d, [](auto D) { return &kmeanspp_update_kernel<D()>; });
+    DCV_REQUIRE(kern, "k-means++ passes: d=%d (1..16) unsupported", d);
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(kKmThreads), 0, s, P_d, n, offset_d, centre_d, (int)first, closest_d, part);
     DCV_CHECK_LAUNCH();
     hipLaunchKernelGGL(kmeans_final_kernel, dim3(1), dim3(256), 0, s, part, nb, 1, pot_d);
     DCV_CHECK_LAUNCH();

@@ -301,6 +301,185 @@ def test_nearest_rows_one_pass_narrow_d(d, k):
     np.testing.assert_array_equal(rows_o.cpu().numpy(), ref + 1_000_000)
 
 
+def _lloyd_case(d, k, n):
+    """Points, start centres and mean of a Lloyd-pass case whose argmin does not hang on the last bit: for every point the
+    two smallest |c|^2 - 2 x.c are more than 1e-9 apart and the argmin is the same whether the dot product is summed by BLAS,
+    sequentially, or sequentially with fused multiply-adds (where Python has math.fma) -- checked here, on the CPU."""
+    import math
+
+    rng = np.random.Generator(np.random.PCG64(2000 + 10 * d + k))
+    cent = rng.uniform(-1, 1, (k, d))
+    P = np.round(cent[rng.integers(0, k, n)] + 0.15 * rng.standard_normal((n, d)), 4)
+    C = P[rng.choice(n, k, replace=False)] + 1e-3
+    mean = P.mean(0)
+    Xc, Cc = P - mean, C - mean
+    cn = (Cc * Cc).sum(1)
+    pw = cn[None, :] - 2.0 * (Xc @ Cc.T)
+    ref_lab = pw.argmin(1)
+    two = np.sort(pw, axis=1)[:, :2]
+    assert (two[:, 1] - two[:, 0]).min() > 1e-9
+    dot = np.zeros((n, k))
+    for c in range(d):
+        dot = dot + Xc[:, c, None] * Cc[None, :, c]
+    np.testing.assert_array_equal((cn[None, :] - 2.0 * dot).argmin(1), ref_lab)
+    if hasattr(math, "fma"):
+        dotf = np.zeros((n, k))
+        for i in range(n):
+            for j in range(k):
+                s = 0.0
+                for c in range(d):
+                    s = math.fma(Xc[i, c], Cc[j, c], s)
+                dotf[i, j] = s
+        np.testing.assert_array_equal((cn[None, :] - 2.0 * dotf).argmin(1), ref_lab)
+    return P, C, mean, ref_lab
+
+
+@pytest.mark.parametrize("d,k,n", [(1, 2, 1_025), (3, 17, 777), (5, 3, 1_000), (8, 9, 300), (16, 64, 2_049)])
+def test_kmeans_step_general_kernel_and_odd_d(d, k, n):
+    """The Lloyd pass outside d = 2 / 4: the general kernel with per-wave LDS accumulators (k > 16 or d > 4, even and odd d:
+    the 16-byte and the scalar point load) and the register kernel at d = 1.  Labels bit-exact against the sklearn formula in
+    NumPy, counts exact, sums / inertia / per-point distances against NumPy, every label changed on the first call and none
+    on the second."""
+    from deep_cartograph_amd import hip
+
+    P, C, mean, ref_lab = _lloyd_case(d, k, n)
+    Xc, Cc = P - mean, C - mean
+    Pd = dev(P)
+    labels = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+    acc, md = hip.kmeans_step(Pd, dev(Cc), labels, offset=dev(mean), want_mindist=True)
+    acc = acc.cpu().numpy()
+    np.testing.assert_array_equal(labels.cpu().numpy(), ref_lab)
+    sums = np.zeros((k, d))
+    np.add.at(sums, ref_lab, Xc)
+    np.testing.assert_allclose(acc[:k * d].reshape(k, d), sums, rtol=1e-12, atol=1e-9)
+    np.testing.assert_array_equal(acc[k * d:k * d + k], np.bincount(ref_lab, minlength=k))
+    np.testing.assert_allclose(acc[k * d + k], ((Xc - Cc[ref_lab]) ** 2).sum(), rtol=1e-12)
+    np.testing.assert_allclose(md.cpu().numpy(), ((Xc - Cc[ref_lab]) ** 2).sum(1), rtol=1e-12, atol=1e-15)
+    assert acc[k * d + k + 1] == n
+    again, _ = hip.kmeans_step(Pd, dev(Cc), labels, offset=dev(mean), want_mindist=True)
+    assert again.cpu().numpy()[k * d + k + 1] == 0
+    np.testing.assert_array_equal(labels.cpu().numpy(), ref_lab)
+
+
+@pytest.mark.parametrize("d", [1, 2, 5, 8, 16])
+def test_kmeanspp_passes_even_and_odd_d(d):
+    """k-means++ seeding passes with an offset: closest = max(0, -2 x.c + |c|^2 + |x|^2) for the first centre, its running
+    minimum for a second one, the potential each update returns, and the potentials of three candidates.  The centres are
+    drawn independently of the points: at a centre that IS a point the three terms cancel to rounding noise of one ulp of
+    |x|^2 (1.8e-15 at d = 16, measured on the first run of this test), which depends on the order of summation and lies
+    outside atol = 1e-15; away from the points rtol covers that ulp."""
+    from deep_cartograph_amd import hip
+
+    n = 1_537
+    rng = np.random.Generator(np.random.PCG64(3000 + d))
+    P = np.round(rng.uniform(-1, 1, (n, d)), 4)
+    mean = P.mean(0)
+    X = P - mean
+
+    def dist(c):
+        return np.maximum(0.0, -2.0 * (X @ c) + (c * c).sum() + (X * X).sum(1))
+
+    c0, c1 = rng.uniform(-1, 1, d) - mean, rng.uniform(-1, 1, d) - mean
+    cand = rng.uniform(-1, 1, (3, d)) - mean
+    Pd, off = dev(P), dev(mean)
+    closest = torch.full((n,), -1.0, dtype=torch.float64, device="cuda")
+    pot = hip.kmeanspp_update(Pd, dev(c0), closest, True, offset=off)
+    ref = dist(c0)
+    np.testing.assert_allclose(closest.cpu().numpy(), ref, rtol=1e-12, atol=1e-15)
+    np.testing.assert_allclose(pot.cpu().numpy(), [ref.sum()], rtol=1e-12)
+    pots = hip.kmeanspp_potentials(Pd, dev(cand), closest, offset=off)
+    np.testing.assert_allclose(pots.cpu().numpy(), [np.minimum(ref, dist(c)).sum() for c in cand], rtol=1e-12)
+    pot = hip.kmeanspp_update(Pd, dev(c1), closest, False, offset=off)
+    ref = np.minimum(ref, dist(c1))
+    np.testing.assert_allclose(closest.cpu().numpy(), ref, rtol=1e-12, atol=1e-15)
+    np.testing.assert_allclose(pot.cpu().numpy(), [ref.sum()], rtol=1e-12)
+
+
+_REG_STREAM_NEAREST = [(4, 6, 70_001), (2, 3, 5_000), (4, 17, 63)]
+_REG_STREAM_LLOYD = (4, 6, 70_001)
+
+
+def _reg_stream_inputs():
+    """The point sets of the register-stream test, with duplicated rows (exact ties) and a centroid that IS a point, as
+    test_nearest_rows_one_pass_narrow_d builds them; the same in the parent and the child process."""
+    cases = []
+    for d, k, n in _REG_STREAM_NEAREST:
+        rng = np.random.Generator(np.random.PCG64(4000 + 10 * d + k))
+        P = np.round(rng.uniform(-1, 1, (n, d)), 4)
+        m = min(50, n // 4)
+        P[n // 2:n // 2 + m] = P[n // 8:n // 8 + m]
+        C = np.round(rng.uniform(-1, 1, (k, d)), 3)
+        C[0] = P[n // 2 + m // 5]
+        cases.append((P, C))
+    d, k, n = _REG_STREAM_LLOYD
+    rng = np.random.Generator(np.random.PCG64(4500))
+    cent = rng.uniform(-1, 1, (k, d))
+    P = np.round(cent[rng.integers(0, k, n)] + 0.15 * rng.standard_normal((n, d)), 4)
+    P[n // 2:n // 2 + 50] = P[n // 8:n // 8 + 50]
+    C = P[rng.choice(n, k, replace=False)] + 1e-3
+    return cases, (P, C)
+
+
+def _reg_stream_run():
+    """rows / distances of every nearest-rows case and labels / acc of the Lloyd case, through whichever stream the process's
+    DCV_KM_RING selects."""
+    from deep_cartograph_amd import hip
+
+    cases, (P, C) = _reg_stream_inputs()
+    out = {}
+    for q, (Pn, Cn) in enumerate(cases):
+        dist, rows = hip.nearest_rows(dev(Pn), dev(Cn))
+        out[f"dist{q}"], out[f"rows{q}"] = dist.cpu().numpy(), rows.cpu().numpy()
+    labels = torch.full((P.shape[0],), -1, dtype=torch.int32, device="cuda")
+    acc, _ = hip.kmeans_step(dev(P), dev(C), labels)
+    out["labels"], out["acc"] = labels.cpu().numpy(), acc.cpu().numpy()
+    return out
+
+
+_REG_STREAM_SCRIPT = """
+import importlib.util
+import sys
+sys.path.insert(0, sys.argv[1])
+import numpy as np
+spec = importlib.util.spec_from_file_location("kernels_gpu_cases", sys.argv[3])
+tk = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(tk)
+np.savez(sys.argv[2], **tk._reg_stream_run())
+"""
+
+
+def test_register_stream_matches_ring_and_numpy(tmp_path):
+    """DCV_KM_RING=0 in a fresh process selects the register stream (kmeans.hip: reg_stream) where this process takes the
+    LDS-DMA ring: nearest_rows (four points per thread and batch) at d = 4 (the lane-pair path; 17 centroids in three chunks
+    on fewer points than one 64-point chunk) and d = 2, and the Lloyd pass at d = 4 (two points, the labels travel along).
+    Rows and distances bit-equal to np.linalg.norm / argmin and to the ring's, labels equal to the ring's."""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    assert os.environ.get("DCV_KM_RING", "1") != "0"
+    ring = _reg_stream_run()
+    script = tmp_path / "reg_stream.py"
+    script.write_text(_REG_STREAM_SCRIPT)
+    env = dict(os.environ)
+    env["DCV_KM_RING"] = "0"
+    out = tmp_path / "reg.npz"
+    res = subprocess.run([sys.executable, str(script), root, str(out), os.path.abspath(__file__)], env=env, cwd=root, capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr[-2000:]
+    reg = np.load(out)
+    cases, _ = _reg_stream_inputs()
+    for q, (P, C) in enumerate(cases):
+        ref = oc.find_centroid_rows(P, C)
+        ref_dist = np.linalg.norm(P[ref] - C, axis=1)
+        for got in (reg, ring):
+            np.testing.assert_array_equal(got[f"rows{q}"], ref)
+            np.testing.assert_array_equal(got[f"dist{q}"], ref_dist)
+        assert reg[f"dist{q}"].tobytes() == ring[f"dist{q}"].tobytes()
+    np.testing.assert_array_equal(reg["labels"], ring["labels"])
+    assert reg["labels"].min() >= 0
+
+
 @pytest.mark.parametrize("d,bins,blocks", [(1, 150, 1), (2, 100, 1), (2, 64, 4), (1, 5000, 1)])
 def test_fes_binned_kde_matches_oracle(d, bins, blocks):
     """f4, FES half: dcv_linear_binning + statistics.compute_fes against the NumPy restatement of the same binned KDE
