@@ -157,10 +157,12 @@ __global__ __launch_bounds__(kScThreads) void silhouette_sum_kernel(const double
 // Every point spreads unit weight over the 2^d grid nodes around it, proportionally to proximity (KDEpy's linear binning).
 // Weights are accumulated as 64-bit fixed point (2^-36 resolution): integer atomics commute, so the grid is the same
 // whatever the order of the threads.  1-D grids that fit LDS are built per block first.
+// A point is inside when lo <= x <= hi on every axis, decided on x itself: (x - lo) * inv rounds, so a point one ulp
+// past hi can land on bins - 1 and a point at hi past it.  Non-finite coordinates fail the comparison and count as outside.
 constexpr double kBinScale = 68719476736.0;   // 2^36
 template <int D>
 __global__ __launch_bounds__(kScThreads) void linear_binning_kernel(const double* __restrict__ P, int64_t n, int64_t ldp, int c0, int c1,
-                                                                    double lo0, double inv0, double lo1, double inv1, int bins,
+                                                                    double lo0, double hi0, double inv0, double lo1, double hi1, double inv1, int bins,
                                                                     unsigned long long* __restrict__ grid, unsigned long long* __restrict__ outside) {
     extern __shared__ unsigned long long s_grid[];
     const bool local = D == 1 && bins <= 4096;
@@ -170,8 +172,10 @@ __global__ __launch_bounds__(kScThreads) void linear_binning_kernel(const double
     }
     unsigned long long miss = 0ull;
     for (int64_t i = (int64_t)blockIdx.x * kScThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kScThreads) {
-        const double t0 = (P[i * ldp + c0] - lo0) * inv0;   // position in grid-spacing units
-        if (!(t0 >= 0.0 && t0 <= (double)(bins - 1))) { ++miss; continue; }
+        const double x0 = P[i * ldp + c0];
+        if (!(x0 >= lo0 && x0 <= hi0)) { ++miss; continue; }
+        double t0 = (x0 - lo0) * inv0;   // position in grid-spacing units
+        if (t0 > (double)(bins - 1)) t0 = (double)(bins - 1);
         int i0 = (int)t0;
         if (i0 > bins - 2) i0 = bins - 2;
         const double f0 = t0 - (double)i0;
@@ -185,15 +189,24 @@ __global__ __launch_bounds__(kScThreads) void linear_binning_kernel(const double
                 atomicAdd(&grid[i0 + 1], w1);
             }
         } else {
-            const double t1 = (P[i * ldp + c1] - lo1) * inv1;
-            if (!(t1 >= 0.0 && t1 <= (double)(bins - 1))) { ++miss; continue; }
+            const double x1 = P[i * ldp + c1];
+            if (!(x1 >= lo1 && x1 <= hi1)) { ++miss; continue; }
+            double t1 = (x1 - lo1) * inv1;
+            if (t1 > (double)(bins - 1)) t1 = (double)(bins - 1);
             int j0 = (int)t1;
             if (j0 > bins - 2) j0 = bins - 2;
             const double f1 = t1 - (double)j0;
-            const unsigned long long w11 = (unsigned long long)(f0 * f1 * kBinScale + 0.5);
-            const unsigned long long w10 = (unsigned long long)(f0 * (1.0 - f1) * kBinScale + 0.5);
-            const unsigned long long w01 = (unsigned long long)((1.0 - f0) * f1 * kBinScale + 0.5);
-            const unsigned long long w00 = (unsigned long long)kBinScale - w11 - w10 - w01;
+            unsigned long long w11 = (unsigned long long)(f0 * f1 * kBinScale + 0.5);
+            unsigned long long w10 = (unsigned long long)(f0 * (1.0 - f1) * kBinScale + 0.5);
+            unsigned long long w01 = (unsigned long long)((1.0 - f0) * f1 * kBinScale + 0.5);
+            // the three can round up to 2^36 + 1 between them (f0 = 1 and f1 an odd multiple of 2^-37): the unit comes off
+            // the largest, so that w00 does not wrap and the four still add up to 2^36
+            unsigned long long w00 = 0ull;
+            const unsigned long long rest = w11 + w10 + w01;
+            if (rest <= (unsigned long long)kBinScale) w00 = (unsigned long long)kBinScale - rest;
+            else if (w11 >= w10 && w11 >= w01) w11 -= rest - (unsigned long long)kBinScale;
+            else if (w10 >= w01) w10 -= rest - (unsigned long long)kBinScale;
+            else w01 -= rest - (unsigned long long)kBinScale;
             unsigned long long* g = grid + (int64_t)i0 * bins + j0;   // grid[i][j]: first coordinate = row
             atomicAdd(g, w00);
             atomicAdd(g + 1, w01);
@@ -295,12 +308,12 @@ extern "C" int dcv_linear_binning(const double* P_d, int64_t n, int64_t ldp, int
     const double inv0 = (double)(bins - 1) / (hi_h[0] - lo_h[0]);
     if (d == 1) {
         const size_t lds = bins <= 4096 ? (size_t)bins * sizeof(unsigned long long) : 0;
-        hipLaunchKernelGGL(linear_binning_kernel<1>, dim3((unsigned)nb), dim3(kScThreads), lds, s, P_d, n, ldp, (int)cols_h[0], 0, lo_h[0], inv0, 0.0,
-                           0.0, (int)bins, fixed, fixed + cells);
+        hipLaunchKernelGGL(linear_binning_kernel<1>, dim3((unsigned)nb), dim3(kScThreads), lds, s, P_d, n, ldp, (int)cols_h[0], 0, lo_h[0], hi_h[0], inv0,
+                           0.0, 0.0, 0.0, (int)bins, fixed, fixed + cells);
     } else {
         const double inv1 = (double)(bins - 1) / (hi_h[1] - lo_h[1]);
         hipLaunchKernelGGL(linear_binning_kernel<2>, dim3((unsigned)nb), dim3(kScThreads), 0, s, P_d, n, ldp, (int)cols_h[0], (int)cols_h[1], lo_h[0],
-                           inv0, lo_h[1], inv1, (int)bins, fixed, fixed + cells);
+                           hi_h[0], inv0, lo_h[1], hi_h[1], inv1, (int)bins, fixed, fixed + cells);
     }
     DCV_CHECK_LAUNCH();
     hipLaunchKernelGGL(binning_to_double_kernel, dim3((unsigned)cdiv(cells, 256)), dim3(256), 0, s, fixed, cells, grid_d);

@@ -358,7 +358,10 @@ def clustering_scores(features: np.ndarray, labels: np.ndarray, comm: Optional[C
     block of frames.  CH and DB are two streaming passes (label sums -> means, then dispersions);
     the silhouette is the exact all-pairs form, O(n^2 d) float64: `silhouette_max_points` (opt-in, a
     behaviour change with respect to the reference) evaluates it on an evenly strided subset of the
-    query points against all points."""
+    query points against all points.
+    Noise (a label < 0, as HDBSCAN gives) is left out of all three scores: no cluster owns a noise point and the
+    silhouette is the mean over the scored points only.  That is sklearn.metrics on the filtered set
+    (features[labels >= 0], labels[labels >= 0]), not sklearn's reading of -1 as one more cluster."""
     comm = comm or Comm()
     dev = _device()
     P = P_dev if P_dev is not None else torch.from_numpy(np.ascontiguousarray(features, dtype=np.float64)).to(dev)
@@ -397,19 +400,20 @@ def clustering_scores(features: np.ndarray, labels: np.ndarray, comm: Optional[C
     lab_all = comm.all_gather_rows(lab)
     order = torch.argsort(lab_all, stable=True)
     P_sorted = P_all[order].contiguous()
-    start = torch.zeros(k + 1, dtype=torch.int64, device=dev)
-    start[1:] = torch.cumsum(torch.bincount(lab_all.clamp(min=0).to(torch.int64), minlength=k)[:k], dim=0)
+    # the noise rows sort first: cluster 0 starts behind them, and the sizes count the labels >= 0 only
+    scored = lab_all[lab_all >= 0].to(torch.int64)
+    start = torch.full((k + 1,), lab_all.numel() - scored.numel(), dtype=torch.int64, device=dev)
+    start[1:] += torch.cumsum(torch.bincount(scored, minlength=k)[:k], dim=0)
     Q, ql = P, lab
     if silhouette_max_points is not None and n > silhouette_max_points:
         stride = int(np.ceil(n / silhouette_max_points))
         Q, ql = P[::stride].contiguous(), lab[::stride].contiguous()
     tot = torch.zeros(1, dtype=torch.float64, device=dev)
-    nq = 0
     chunk = max(1, (1 << 26) // max(k, 1))           # bound the nq x k float64 scratch to 512 MiB
     for b in range(0, Q.shape[0], chunk):
         S = hip.cluster_dist_sums(Q[b:b + chunk], P_sorted, start)
         tot += hip.silhouette_sum(S, ql[b:b + chunk], start)
-        nq += min(chunk, Q.shape[0] - b)
+    nq = int((ql >= 0).sum().item())                 # the kernel skips the noise queries: the mean is over the scored ones
     tot = comm.sum_(tot)
     nq = comm.sum_scalar(float(nq), device=dev)
     return float(ch), float(db), float(tot.item() / nq)

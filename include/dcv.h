@@ -469,7 +469,9 @@ int dcv_kmeanspp_update(const double* P_d, int64_t n, int32_t d, const double* o
  * points against the points sorted by cluster (cluster c = rows [start[c], start[c+1]) of Psorted_d;
  * start_d holds k + 1 int64).  The exact all-pairs silhouette: O(nq * n * d) float64.
  * dcv_silhouette_sum: sum_d[0] = sum of the silhouette sample values of the nq queries (labels
- * qlabels_d), sklearn's definition incl. 0 for singleton clusters; divide by n for the score. */
+ * qlabels_d), sklearn's definition incl. 0 for singleton clusters; a query with a label outside [0, k)
+ * (noise) adds nothing, and start_d describes clusters 0 .. k-1 only (noise rows sorted first: start[0] =
+ * their number): divide by the number of queries with a label in [0, k) for the score. */
 size_t dcv_label_stats_workspace(int64_t n, int32_t d, int32_t k);
 int dcv_label_stats(const double* P_d, int64_t n, int32_t d, const int32_t* labels_d, const double* centers_d /* k*d or NULL */,
                     int32_t k, double* acc_d, void* ws_d, size_t ws_bytes, void* stream);
@@ -485,7 +487,7 @@ int dcv_silhouette_sum(const double* S_d, int64_t nq, int32_t k, const int32_t* 
  * FES = -kB T log(density + eps).  The streaming stage is the binning: each of the n points (row-major float64, row
  * stride ldp, the d <= 2 columns cols_h) spreads unit weight over the 2^d grid nodes around it.  grid_d receives the
  * bins^d node weights (sum = points inside the bounds; d = 2: grid[i][j], i along the first column); outside_h the
- * number of points outside [lo, hi] (ignored).  Deterministic (64-bit fixed-point accumulation).  The d-dimensional
+ * number of points outside [lo, hi] (ignored; lo and hi themselves are inside, a non-finite coordinate is outside).  Deterministic (64-bit fixed-point accumulation).  The d-dimensional
  * convolution on the small grid and the logarithm stay with the caller (statistics.compute_fes). */
 size_t dcv_linear_binning_workspace(int32_t d, int32_t bins);
 int dcv_linear_binning(const double* P_d, int64_t n, int64_t ldp, int32_t d, const int32_t* cols_h, const double* lo_h,

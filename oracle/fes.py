@@ -14,13 +14,15 @@ KB_KJ_MOL = 0.0083144621
 
 
 def linear_binning(X: np.ndarray, lo, hi, bins: int) -> np.ndarray:
-    """Unit weight of every point spread over its 2^d neighbouring nodes (d = 1, 2); points outside [lo, hi] are ignored."""
+    """Unit weight of every point spread over its 2^d neighbouring nodes (d = 1, 2); points outside [lo, hi] are ignored
+    (decided on the coordinates themselves: lo and hi are inside, one ulp past them and non-finite values are not)."""
     X = np.asarray(X, dtype=np.float64)
     n, d = X.shape
-    t = [(X[:, c] - lo[c]) * ((bins - 1) / (hi[c] - lo[c])) for c in range(d)]
+    with np.errstate(invalid="ignore"):
+        t = [np.minimum((X[:, c] - lo[c]) * ((bins - 1) / (hi[c] - lo[c])), bins - 1) for c in range(d)]
     ok = np.ones(n, dtype=bool)
     for c in range(d):
-        ok &= (t[c] >= 0) & (t[c] <= bins - 1)
+        ok &= (X[:, c] >= lo[c]) & (X[:, c] <= hi[c])
     idx, frac = [], []
     for c in range(d):
         i0 = np.minimum(t[c][ok].astype(np.int64), bins - 2)
