@@ -43,9 +43,17 @@ __device__ unsigned long long g_stamp[8 * 8192];
         if (threadIdx.x == 0 && blockIdx.x < 8192 && blockIdx.z == 0)                           \
             g_stamp[blockIdx.x * 8 + (slot)] = __builtin_amdgcn_s_memrealtime();               \
     } while (0)
+// raw hardware registers (the workgroup's placement) of the stamped workgroup
+#define DCV_STAMP_HW(slot)                                                                      \
+    do {                                                                                        \
+        if (threadIdx.x == 0 && blockIdx.x < 8192 && blockIdx.z == 0)                           \
+            g_stamp[blockIdx.x * 8 + (slot)] = (unsigned long long)__builtin_amdgcn_s_getreg(63492) | \
+                                               ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32); \
+    } while (0)
 #else
 #define DCV_STAMP_AT(slot) do {} while (0)
 #define DCV_STAMP_RT(slot) do {} while (0)
+#define DCV_STAMP_HW(slot) do {} while (0)
 #endif
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -111,11 +119,6 @@ struct Operand {
     RowMap rows;
     const float* shift;  // per-(non-contraction)-column value subtracted on load (KMAJOR only), or null
     int vec_ok;          // 16-byte loads legal (alignment part; extents are checked at launch)
-    // Pre-split operand (contraction-contiguous kinds only; see "plane operands" below): p points at the three bf16
-    // planes of the matrix, ld and pstride are in float units (2 bf16 each): plane q of (row r, contraction index k)
-    // is the bf16 at ((const __bf16*)(p + r * ld + q * pstride))[k].
-    int planes = 0;
-    int64_t pstride = 0;
 };
 
 struct GemmDims {
@@ -138,29 +141,13 @@ struct GemmDims {
 // one being multiplied); the register-staged loop always double-buffers in the first two.
 // SPLIT: FP32-accurate products on the BF16 matrix pipe (see split3 / mfma16 below) instead of the
 // FP32-input MFMA.
-// PL (SPLIT): bit 0 / bit 1 (NT products only) = the A / B operand arrives pre-split into its three bf16 planes
-// (Operand::planes), so its share of the in-register split -- the vector-ALU work that bounds the SPLIT flavour --
-// disappears from the main loop.  bit 2 / bit 3 = the A / B operand (contraction-contiguous kinds) is an ordinary fp32
-// matrix, staged through registers and split ONCE PER WORKGROUP when the stage is stored to LDS, as three plane images:
-// the in-register split after the fragment read is repeated by every wave that shares a fragment (two of the four waves
-// of a 2 x 2 layout), so this halves the vector-ALU work without the 1.5 x global traffic of pre-split operands --
-// what bounds the small-batch products (measured at 8192 x 256 x 512: in-register split 21.9 us, vector-ALU-bound;
-// pre-split planes 22.5 us, bound by the L2 -> LDS traffic; without loads 20.7 vs 14.3 us).
-template <int WAVES_M_, int WAVES_N_, int FM_, int FN_, int KB_, int NBUF_ = 2, bool SPLIT_ = false, int PL_ = 0>
+template <int WAVES_M_, int WAVES_N_, int FM_, int FN_, int KB_, int NBUF_ = 2, bool SPLIT_ = false>
 struct TileCfg {
     static constexpr int WAVES_M = WAVES_M_, WAVES_N = WAVES_N_, FM = FM_, FN = FN_, KB = KB_, NBUF = NBUF_;
     static constexpr bool SPLIT = SPLIT_;
-    static constexpr int PL = PL_;
-    static_assert(PL == 0 || SPLIT, "plane operands belong to the split flavour");
-    // bit 4 (with bits 2 / 3, NT products): the fp32 stage arrives by LDS-DMA in a raw ring behind the plane buffers and is
-    // split from THERE, once per workgroup (gemm_block: the LS loop).  Bit-identical, half the vector-ALU work, the global
-    // latency hidden as in the ring loop -- and SLOWER (25.7 vs 22.8 us at 8192 x 256 x 512): the plane stores, the second
-    // LDS round trip and the per-stage barrier behind the split cost more than the split they save.  Tool-only.
-    static constexpr bool LS = (PL_ & 16) != 0;
-    static constexpr int RAW_SZ = LS ? (WAVES_M_ * FM_ * 32 + WAVES_N_ * FN_ * 32) * KB_ : 0;   // floats of one raw stage
-    // LDS floats of one stage: an fp32 tile is [T][KB] floats, a plane tile three [T][KB/2] images
-    static constexpr int A_SZ = (PL & 5) ? 3 * (WAVES_M_ * FM_ * 32) * (KB_ / 2) : (WAVES_M_ * FM_ * 32) * KB_;
-    static constexpr int B_SZ = (PL & 10) ? 3 * (WAVES_N_ * FN_ * 32) * (KB_ / 2) : (WAVES_N_ * FN_ * 32) * KB_;
+    // LDS floats of one stage: an fp32 tile is [T][KB] floats
+    static constexpr int A_SZ = (WAVES_M_ * FM_ * 32) * KB_;
+    static constexpr int B_SZ = (WAVES_N_ * FN_ * 32) * KB_;
     static_assert(NBUF >= 2 && NBUF <= 8, "NBUF");
     static constexpr int TM = WAVES_M * FM * 32;
     static constexpr int TN = WAVES_N * FN * 32;
@@ -269,9 +256,6 @@ struct MMajorStage {
     bool all_rows;          // every row of the tile is in range (workgroup-uniform)
     bool affine;            // the tile's rows are row0 + m: no gather, not astride the x_t / x_lag seam
 
-    // CLAMP (kernels with plane operands: pure LDS-DMA, no register-staged loop): rows past the end read the last
-    // valid row instead of being zero-filled -- they only feed output rows the epilogue masks
-    template <bool CLAMP = false>
     __device__ __forceinline__ void init(const Operand& op, int64_t m0, int64_t m_end, int t) {
         const int row0 = t / CPR;
         kofs = ((t % CPR) ^ ((row0 / RPBR) % CPR)) * 4;
@@ -280,21 +264,23 @@ struct MMajorStage {
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int u = t + 256 * i;
-            int64_t m = m0 + u / CPR;
-            if constexpr (CLAMP) m = m < m_end ? m : m_end - 1;
+            const int64_t m = m0 + u / CPR;
             const bool ok = (UNITS % 256 == 0 || u < UNITS) && m < m_end;
             src[i] = ok ? op.p + op.rows.template get<GATHER>(m) * op.ld + kofs : nullptr;
             voff[i] = (unsigned)(((int64_t)(u / CPR) * op.ld + kofs) * 4);
         }
     }
-    // wave-uniform base of the affine form: first row of the tile, contraction offset k0
-    __device__ __forceinline__ const float* tile_base(const Operand& op, int64_t m0, int64_t k0) const {
-        return op.p + op.rows.template get<false>(m0) * op.ld + k0;
+    // The two stage kinds share their method signatures (gemm_block names neither); what one has no use for is ignored.
+    // rows are resolved once, in init()
+    __device__ __forceinline__ void resolve(const Operand&, int64_t, int64_t, int64_t, int) {}
+    // wave-uniform base of the affine form: first row of the tile (row0), contraction offset k0
+    __device__ __forceinline__ const float* base(const Operand& op, int64_t row0, int64_t k0, int64_t) const {
+        return op.p + op.rows.template get<false>(row0) * op.ld + k0;
     }
-    __device__ __forceinline__ void glds_affine(const float* base, unsigned lds0) const {
+    __device__ __forceinline__ void glds_affine(const float* src, unsigned lds0) const {
         // a tile shape with another unit count would silently issue NO copy here (a 256-row tile: 8 units per thread)
         static_assert(UNITS % 256 != 0 || PER == 1 || PER == 2 || PER == 4, "units per thread of the batched LDS-DMA form");
-        if constexpr (UNITS % 256 == 0 && (PER == 1 || PER == 2 || PER == 4)) glds16_batch<PER>(base, voff, lds0);
+        if constexpr (UNITS % 256 == 0 && (PER == 1 || PER == 2 || PER == 4)) glds16_batch<PER>(src, voff, lds0);
     }
     __device__ __forceinline__ bool dense(int64_t k0, int64_t k_end) const { return VEC && all_rows && k0 + KB <= k_end; }
     __device__ __forceinline__ void glds(int64_t k0, float* lds, int t) const {
@@ -330,38 +316,6 @@ struct MMajorStage {
         for (int i = 0; i < PER; ++i)
             if (UNITS % 256 == 0 || t + 256 * i < UNITS) *reinterpret_cast<float4*>(lds + (t + 256 * i) * 4) = r[i];
     }
-    // The staged fp32 values split into their three bf16 pieces on the way to LDS (TileCfg::PL bits 2 / 3): plane q of the
-    // tile is an MMAJOR image [T][KB / 2] floats (= [T][KB] bf16) at lds + q * T * KB / 2, its 16-byte chunks (8
-    // consecutive k) swizzled exactly as the pre-split operands' images are, so read_frags8 reads either alike.  A
-    // thread's 4 floats are one half of such a chunk: 8 bytes per plane.
-    __device__ __forceinline__ void store_planes(float* lds, int t) const {
-        constexpr int KF = KB / 2, CPRP = KF / 4, RPBRP = 64 / KF;
-        const int c4 = kofs >> 2;   // this thread's logical 4-float chunk of its rows (the same in every unit)
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int u = t + 256 * i;
-            if (UNITS % 256 == 0 || u < UNITS) {
-                const int row = u / CPR;
-                const int off = row * KF + (((c4 >> 1) ^ ((row / RPBRP) % CPRP)) << 2) + (c4 & 1) * 2;
-                const unsigned a = __float_as_uint(r[i].x), b = __float_as_uint(r[i].y), c = __float_as_uint(r[i].z), d = __float_as_uint(r[i].w);
-                uint2 p1, p2, p3;
-                p1.x = __builtin_amdgcn_perm(b, a, 0x07060302);
-                p1.y = __builtin_amdgcn_perm(d, c, 0x07060302);
-                const float ra = r[i].x - __uint_as_float(a & 0xFFFF0000u), rb = r[i].y - __uint_as_float(b & 0xFFFF0000u);
-                const float rc = r[i].z - __uint_as_float(c & 0xFFFF0000u), rd = r[i].w - __uint_as_float(d & 0xFFFF0000u);
-                const unsigned a2 = __float_as_uint(ra), b2 = __float_as_uint(rb), c2 = __float_as_uint(rc), d2 = __float_as_uint(rd);
-                p2.x = __builtin_amdgcn_perm(b2, a2, 0x07060302);
-                p2.y = __builtin_amdgcn_perm(d2, c2, 0x07060302);
-                const float sa = ra - __uint_as_float(a2 & 0xFFFF0000u), sb = rb - __uint_as_float(b2 & 0xFFFF0000u);
-                const float sc = rc - __uint_as_float(c2 & 0xFFFF0000u), sd = rd - __uint_as_float(d2 & 0xFFFF0000u);
-                p3.x = __builtin_amdgcn_perm(__float_as_uint(sb), __float_as_uint(sa), 0x07060302);
-                p3.y = __builtin_amdgcn_perm(__float_as_uint(sd), __float_as_uint(sc), 0x07060302);
-                *reinterpret_cast<uint2*>(lds + off) = p1;
-                *reinterpret_cast<uint2*>(lds + T * KF + off) = p2;
-                *reinterpret_cast<uint2*>(lds + 2 * T * KF + off) = p3;
-            }
-        }
-    }
 };
 
 // KMAJOR tile [KB][T]: unit u -> krow = u / (T/4), c4 = u % (T/4).  A thread's columns are the
@@ -375,7 +329,7 @@ struct KMajorStage {
     static_assert(256 % C4 == 0, "column group must be unit independent");
     float4 r[PER];
     float4 sh;          // shift of this thread's 4 columns
-    const float* base;  // op.p + first column of this thread
+    const float* colp;  // op.p + first column of this thread
     int64_t ld;
     int64_t rowv[PER];  // matrix row of unit i in the NEXT load (or -1)
     unsigned okmask;    // units of the LAST register load that were in range
@@ -389,7 +343,7 @@ struct KMajorStage {
         const int64_t col = c0 + (t % C4) * 4;
         const int64_t left = c_end - col;
         ncol = left >= 4 ? 4 : (left > 0 ? (int)left : 0);
-        base = op.p + col;
+        colp = op.p + col;
         ld = op.ld;
         has_shift = op.shift != nullptr;
         sh = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -408,17 +362,14 @@ struct KMajorStage {
         }
         okmask = 0;
     }
-    // affine form: the KB rows of the stage at k0 must be consecutive matrix rows
-    __device__ __forceinline__ static bool stage_affine(const Operand& op, int64_t k0) {
-        return op.rows.half <= 0 || k0 >= op.rows.half || k0 + KB <= op.rows.half;
+    // wave-uniform base of the affine form: first row of the stage (k0, shifted by row_off), first column of the tile (row0)
+    __device__ __forceinline__ const float* base(const Operand& op, int64_t row0, int64_t k0, int64_t row_off) const {
+        return op.p + (op.rows.template get<false>(k0) + row_off) * op.ld + row0;
     }
-    __device__ __forceinline__ static const float* stage_base(const Operand& op, int64_t k0, int64_t row_off, int64_t c0) {
-        return op.p + (op.rows.template get<false>(k0) + row_off) * op.ld + c0;
-    }
-    __device__ __forceinline__ void glds_affine(const float* base, unsigned lds0) const {
+    __device__ __forceinline__ void glds_affine(const float* src, unsigned lds0) const {
         // a tile shape with another unit count would silently issue NO copy here (a 256-row tile: 8 units per thread)
         static_assert(UNITS % 256 != 0 || PER == 1 || PER == 2 || PER == 4, "units per thread of the batched LDS-DMA form");
-        if constexpr (UNITS % 256 == 0 && (PER == 1 || PER == 2 || PER == 4)) glds16_batch<PER>(base, voff, lds0);
+        if constexpr (UNITS % 256 == 0 && (PER == 1 || PER == 2 || PER == 4)) glds16_batch<PER>(src, voff, lds0);
     }
     __device__ __forceinline__ void resolve(const Operand& op, int64_t k0, int64_t k_end, int64_t row_off, int t) {
 #pragma unroll
@@ -431,14 +382,14 @@ struct KMajorStage {
     }
     __device__ __forceinline__ bool dense(int64_t k0, int64_t k_end) const { return all_cols && k0 + KB <= k_end; }
     // both loaders fetch the stage resolved by the previous resolve() call
-    __device__ __forceinline__ void glds(float* lds, int t) const {
+    __device__ __forceinline__ void glds(int64_t, float* lds, int t) const {
 #pragma unroll
-        for (int i = 0; i < PER; ++i) glds16(base + rowv[i] * ld, lds_addr_uniform(lds + ((t & ~63) + 256 * i) * 4));
+        for (int i = 0; i < PER; ++i) glds16(colp + rowv[i] * ld, lds_addr_uniform(lds + ((t & ~63) + 256 * i) * 4));
     }
     __device__ __forceinline__ void load(int64_t k0, int64_t k_end) {
         if (dense(k0, k_end)) {  // uniform: unconditional 16-byte loads
 #pragma unroll
-            for (int i = 0; i < PER; ++i) r[i] = *reinterpret_cast<const float4*>(base + rowv[i] * ld);
+            for (int i = 0; i < PER; ++i) r[i] = *reinterpret_cast<const float4*>(colp + rowv[i] * ld);
             okmask = ~0u;
             return;
         }
@@ -447,7 +398,7 @@ struct KMajorStage {
         for (int i = 0; i < PER; ++i) {
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (rowv[i] >= 0) {
-                const float* s = base + rowv[i] * ld;
+                const float* s = colp + rowv[i] * ld;
                 m |= 1u << i;
                 if constexpr (VEC) {
                     v = *reinterpret_cast<const float4*>(s);
@@ -556,47 +507,51 @@ __device__ __forceinline__ void vm_wait_younger(int64_t younger) {
     }
 }
 
+// ---- staged-epilogue geometry (used by the side-operand prefetch of the ring loop and by the epilogue of gemm_block)
+// The accumulator tile is transposed through the stage buffers; when they are smaller than the tile (KB = 16) it goes
+// through in EPASS row blocks, each written by the waves that own those rows.
+template <class Cfg, int NB>
+struct EpiGeom {
+    static constexpr int TM = Cfg::TM, TN = Cfg::TN;
+    static constexpr int LDSF = Cfg::NBUF * (Cfg::A_SZ + NB * Cfg::B_SZ);   // floats of LDS the kernel owns
+    static constexpr int EPASS = (TM * TN + LDSF - 1) / LDSF;
+    static constexpr int RP = TM / (EPASS > 0 ? EPASS : 1);   // rows per pass
+    static constexpr bool kStaged = (NB == 1) && (EPASS <= 2) && (TM % EPASS == 0) && (RP % (Cfg::FM * 32) == 0) && (RP * TN <= LDSF);
+    static constexpr int C4 = TN / 4;                         // 16-byte segments per row
+    static constexpr int RPP = 256 / (C4 > 256 ? 256 : C4);   // rows per pass of the store loop
+    static constexpr int NQ = RP / RPP;                       // row segments per thread and epilogue pass
+    // Side operand of the epilogue (the stored activations whose derivative scales a dgrad tile): for a
+    // full tile its EPASS * NQ row segments are requested before the first stage is awaited, so they
+    // stream in under the main loop instead of in a burst at the end while the matrix pipe idles
+    // (short-K products are otherwise HBM-bound for the length of their epilogue and idle before it).
+    template <class Epi>
+    static constexpr bool kSidePre = kStaged && Epi::kSide && (EPASS * NQ <= 16) && !Cfg::SPLIT;   // SPLIT: the planes need the registers
+    template <class Epi>
+    static constexpr int NSIDE = kSidePre<Epi> ? EPASS * NQ : 1;
+};
+
 // ------------------------------------------------------------------ the kernel body
+// One workgroup's tile from start to finish, in five parts: (1) set-up, (2) ring loop, (3) register-staged remainder,
+// (4) tail hand-off, (5) epilogue.  It stays ONE function on purpose: hipcc's output for every kernel depends on when
+// each piece is inlined, and moving any part of the body into a function of its own changes registers and schedules in
+// every kernel ("Shape of gemm_block").
 // NB: number of B operands sharing A (2 for the lagged covariance: B and B shifted by `lag2`).
 template <int MODE, class Cfg, int NB, bool VEC, bool GATHER, class Epi>
 __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, int64_t lag2, const GemmDims& d,
                                            int tile_m, int tile_n, int64_t k_begin, int64_t k_end, float* lds,
                                            Epi& epi, int tail_chunk = -1) {
+    // ---------------------------------------------------------------- (1) set-up: stage objects, fragments, products
     constexpr int TM = Cfg::TM, TN = Cfg::TN, KB = Cfg::KB, FM = Cfg::FM, FN = Cfg::FN;
     constexpr int A_SZ = Cfg::A_SZ, B_SZ = Cfg::B_SZ;
     constexpr int STAGE = A_SZ + NB * B_SZ;
     constexpr bool A_MM = (MODE == kNT || MODE == kNN);
     constexpr bool B_MM = (MODE == kNT);
-    // ---- plane operands (Cfg::PL): the operand was split into its three bf16 planes ahead of time (a matrix that is
-    // constant over many products: the training set, the weights between optimiser steps).  A plane tile is three
-    // MMAJOR images of [T][KB/2] floats (= [T][KB] bf16) with the same chunk swizzle, filled by LDS-DMA only; a lane's
-    // 16-byte fragment read IS the bf16x8 operand of v_mfma_f32_32x32x16_bf16, bit-identical to what split3 would
-    // have produced from the fp32 value.  Such kernels have no register-staged loop: the launch guarantees K % KB == 0
-    // and 16-byte loads, and ragged row tiles read clamped rows (MMajorStage::init<true>).
-    constexpr int PL = Cfg::PL;
-    constexpr bool PRE = (PL & 3) != 0;                      // an operand arrives pre-split (pure LDS-DMA kernel)
-    constexpr bool PSA = (PL & 4) != 0, PSB = (PL & 8) != 0;  // fp32 operand split when its stage is stored to LDS (register-staged kernel)
-    constexpr bool PA = (PL & 5) != 0, PB = (PL & 10) != 0;   // the operand's LDS image is three plane images
-    constexpr bool LS = Cfg::LS;                               // ... split from a DMA-filled raw fp32 ring in LDS (below)
-    static_assert(!LS || (MODE == kNT && PSA && PSB && VEC && !GATHER && NB == 1), "split-from-LDS: NT products, both operands, 16-byte rows");
-    static_assert(!PRE || (MODE == kNT && NB == 1 && VEC && Cfg::SPLIT), "plane operands: NT products of the split flavour");
-    static_assert(!(PSA || PSB) || (!PRE && NB == 1 && Cfg::SPLIT), "split-at-store: split flavour, one B operand, no pre-split operand beside it");
-    static_assert(!PSA || MODE == kNT || MODE == kNN, "split-at-store of A needs a contraction-contiguous A");
-    static_assert(!PSB || MODE == kNT, "split-at-store of B needs a contraction-contiguous B");
-    constexpr int KF = KB / 2;           // floats per row of a plane image
-    constexpr int KA = (PL & 1) ? KF : KB, KBB = (PL & 2) ? KF : KB;   // row length of the stage objects' GLOBAL side
-    constexpr int NPA = (PL & 1) ? 3 : 1, NPB = (PL & 2) ? 3 : 1;
     const int t = threadIdx.x;
     const int lane = t & 63;
     const int wave = t >> 6;
     const int wm = (wave / Cfg::WAVES_N) * FM * 32;
     const int wn = (wave % Cfg::WAVES_N) * FN * 32;
     const int64_t m0 = (int64_t)tile_m * TM, n0 = (int64_t)tile_n * TN;
-#ifdef DCV_ABL_SAMETILE   // diagnostic (wrong results): every workgroup streams the first few row tiles of A -- all cache hits
-    const int64_t m0_ld = (int64_t)(tile_m % DCV_ABL_SAMETILE) * TM;
-#else
-    const int64_t m0_ld = m0;
-#endif
 
     f32x16 acc[NB][FM][FN];
 #pragma unroll
@@ -608,90 +563,51 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[b][i][j][e] = 0.f;
 
-    MMajorStage<TM, KA, VEC, GATHER> am;
-    KMajorStage<TM, KB, VEC, GATHER> ak;
-    MMajorStage<TN, KBB, VEC, GATHER> bm;
-    KMajorStage<TN, KB, VEC, GATHER> bk[NB];
-    if constexpr (A_MM) am.template init<PRE || LS>(A, m0, d.M, t);
-    else ak.init(A, m0, d.M, t);
-    if constexpr (B_MM) bm.template init<PRE || LS>(B, n0, d.N, t);
+    // The operand stage objects: A's, and B's with one copy per B operand when KMAJOR (copy 1 reads rows shifted by lag2).
+    // The two stage kinds share their method signatures, so nothing below asks which kind it holds.
+    using AStage = std::conditional_t<A_MM, MMajorStage<TM, KB, VEC, GATHER>, KMajorStage<TM, KB, VEC, GATHER>>;
+    using BStage = std::conditional_t<B_MM, MMajorStage<TN, KB, VEC, GATHER>, KMajorStage<TN, KB, VEC, GATHER>>;
+    constexpr int NBS = B_MM ? 1 : NB;
+    AStage sa;
+    BStage sb[NBS];
+    sa.init(A, m0, d.M, t);
+    // (the loop only where there can be two copies: a one-trip loop over the single MMAJOR object, or naming the KMAJOR
+    // copies one by one, is the same program and leaves hipcc with other registers and schedules in those kernels)
+    if constexpr (B_MM) sb[0].init(B, n0, d.N, t);
     else {
 #pragma unroll
-        for (int b = 0; b < NB; ++b) bk[b].init(B, n0, d.N, t);
+        for (int b = 0; b < NBS; ++b) sb[b].init(B, n0, d.N, t);
     }
 
     auto resolve_stage = [&](int64_t k0) {
-        if constexpr (!A_MM) ak.resolve(A, k0, k_end, 0, t);
-        if constexpr (!B_MM) {
-            bk[0].resolve(B, k0, k_end, 0, t);
-            if constexpr (NB == 2) bk[1].resolve(B, k0, k_end, lag2, t);
-        }
+        sa.resolve(A, k0, k_end, 0, t);
+        sb[0].resolve(B, k0, k_end, 0, t);
+        if constexpr (NBS == 2) sb[1].resolve(B, k0, k_end, lag2, t);
     };
     auto stage_dense = [&](int64_t k0) -> bool {  // workgroup-uniform
-#ifdef DCV_NO_GLDS
-        return false;
-#endif
-        bool ok;
-        if constexpr (A_MM) ok = am.dense(k0, k_end);
-        else ok = ak.dense(k0, k_end);
-        if constexpr (B_MM) ok = ok && bm.dense(k0, k_end);
-        else {
-            ok = ok && bk[0].dense(k0, k_end);
-            if constexpr (NB == 2) ok = ok && bk[1].dense(k0, k_end);
-        }
+        bool ok = sa.dense(k0, k_end) && sb[0].dense(k0, k_end);
+        if constexpr (NBS == 2) ok = ok && sb[1].dense(k0, k_end);
         return ok;
     };
     // pure-DMA issue of the stage at k0 into ring buffer `buf`
     const unsigned ldsw = lds_addr_uniform(lds + (t & ~63) * 4);   // this wave's unit-0 slot of buffer 0
-    // plane kernels: an operand whose tile is in range and affine takes the batched form, any other (gathered rows,
-    // the x_t / x_lag seam, a ragged last row tile) per-thread pointers to clamped rows; workgroup-uniform choice
-    const bool pl_a_aff = am.affine && am.all_rows, pl_b_aff = bm.affine && bm.all_rows;
     auto glds_stage = [&](int64_t k0, int buf, int part = 3) {   // part: 1 = A operand, 2 = B operand(s)
-        if constexpr (PRE) {
-            const unsigned l0 = ldsw + (unsigned)(buf * STAGE) * 4u;
-            float* b = lds + buf * STAGE;
-            if (part & 1) {
-                const int64_t ka = (PL & 1) ? k0 / 2 : k0;   // float offset inside a row
-#pragma unroll
-                for (int q = 0; q < NPA; ++q) {
-                    if (pl_a_aff) am.glds_affine(am.tile_base(A, m0_ld, ka) + q * A.pstride, l0 + (unsigned)(q * TM * KF) * 4u);
-                    else am.glds(ka + q * A.pstride, b + q * TM * KF, t);
-                }
-            }
-            if (part & 2) {
-                const int64_t kb = (PL & 2) ? k0 / 2 : k0;
-#pragma unroll
-                for (int q = 0; q < NPB; ++q) {
-                    if (pl_b_aff) bm.glds_affine(bm.tile_base(B, n0, kb) + q * B.pstride, l0 + (unsigned)(A_SZ + q * TN * KF) * 4u);
-                    else bm.glds(kb + q * B.pstride, b + A_SZ + q * TN * KF, t);
-                }
-            }
-        } else if constexpr (GATHER) {   // per-thread 64-bit source pointers
+        if constexpr (GATHER) {   // per-thread 64-bit source pointers
             float* b = lds + buf * STAGE;
             if (part & 1) {
                 resolve_stage(k0);
-                if constexpr (A_MM) am.glds(k0, b, t);
-                else ak.glds(b, t);
+                sa.glds(k0, b, t);
             }
             if (part & 2) {
-                if constexpr (B_MM) bm.glds(k0, b + A_SZ, t);
-                else {
-                    bk[0].glds(b + A_SZ, t);
-                    if constexpr (NB == 2) bk[1].glds(b + A_SZ + B_SZ, t);
-                }
+                sb[0].glds(k0, b + A_SZ, t);
+                if constexpr (NBS == 2) sb[1].glds(k0, b + A_SZ + B_SZ, t);
             }
         } else {                  // affine tiles: uniform base + constant unit offsets, no vector ALU
             const unsigned l0 = ldsw + (unsigned)(buf * STAGE) * 4u;
-            if (part & 1) {
-                if constexpr (A_MM) am.glds_affine(am.tile_base(A, m0_ld, k0), l0);
-                else ak.glds_affine(ak.stage_base(A, k0, 0, m0), l0);
-            }
+            if (part & 1) sa.glds_affine(sa.base(A, m0, k0, 0), l0);
             if (part & 2) {
-                if constexpr (B_MM) bm.glds_affine(bm.tile_base(B, n0, k0), l0 + A_SZ * 4u);
-                else {
-                    bk[0].glds_affine(bk[0].stage_base(B, k0, 0, n0), l0 + A_SZ * 4u);
-                    if constexpr (NB == 2) bk[1].glds_affine(bk[1].stage_base(B, k0, lag2, n0), l0 + (A_SZ + B_SZ) * 4u);
-                }
+                sb[0].glds_affine(sb[0].base(B, n0, k0, 0), l0 + A_SZ * 4u);
+                if constexpr (NBS == 2) sb[1].glds_affine(sb[1].base(B, n0, k0, lag2), l0 + (A_SZ + B_SZ) * 4u);
             }
         }
     };
@@ -702,35 +618,17 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
             const int64_t h = op.rows.half;
             return h <= 0 || k_begin >= h || k_end <= h || ((h - k_begin) % KB == 0);
         };
-        bool ok;
-        if constexpr (A_MM) ok = am.affine;
-        else ok = ak.affine && seam_ok(A);
-        if constexpr (B_MM) ok = ok && bm.affine;
-        else ok = ok && bk[0].affine && seam_ok(B);
-        return ok;
+        return sa.affine && (A_MM || seam_ok(A)) && sb[0].affine && (B_MM || seam_ok(B));
     };
     auto load_stage = [&](int64_t k0) {
-        if constexpr (A_MM) am.load(k0, k_end);
-        else ak.load(k0, k_end);
-        if constexpr (B_MM) bm.load(k0, k_end);
-        else {
-            bk[0].load(k0, k_end);
-            if constexpr (NB == 2) bk[1].load(k0, k_end);
-        }
+        sa.load(k0, k_end);
+        sb[0].load(k0, k_end);
+        if constexpr (NBS == 2) sb[1].load(k0, k_end);
     };
     auto store_stage = [&](float* buf) {
-        if constexpr (A_MM) {
-            if constexpr (PSA) am.store_planes(buf, t);
-            else am.store(buf, t);
-        } else ak.store(buf, t);
-        if constexpr (B_MM) {
-            if constexpr (PSB) bm.store_planes(buf + A_SZ, t);
-            else bm.store(buf + A_SZ, t);
-        }
-        else {
-            bk[0].store(buf + A_SZ, t);
-            if constexpr (NB == 2) bk[1].store(buf + A_SZ + B_SZ, t);
-        }
+        sa.store(buf, t);
+        sb[0].store(buf + A_SZ, t);
+        if constexpr (NBS == 2) sb[1].store(buf + A_SZ + B_SZ, t);
     };
     // fragments of one k-group (4 MFMA steps): registers av[i][s], bv[b][j][s]
     struct Frags {
@@ -829,18 +727,12 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
     struct Frags8 {
         float a[FM][8];
         float b[NB][FN][8];
-        u32x4 ap[3][FM];       // plane operands: the fragment is the bf16x8 itself
-        u32x4 bp[3][FN];
     };
     auto read_frags8 = [&](Frags8& f, const float* la, const float* lb, int s) {
         const int h = lane >> 5;
 #pragma unroll
         for (int i = 0; i < FM; ++i) {
-            if constexpr (PA) {
-#pragma unroll
-                for (int q = 0; q < 3; ++q)
-                    f.ap[q][i] = __builtin_bit_cast(u32x4, frag_mmajor_chunk<KF>(la + q * TM * KF, wm + i * 32, 2 * s + h, lane));
-            } else if constexpr (A_MM) {
+            if constexpr (A_MM) {
                 const v4f u = frag_mmajor_chunk<KB>(la, wm + i * 32, 4 * s + 2 * h, lane);
                 const v4f v = frag_mmajor_chunk<KB>(la, wm + i * 32, 4 * s + 2 * h + 1, lane);
                 f.a[i][0] = u.x; f.a[i][1] = u.y; f.a[i][2] = u.z; f.a[i][3] = u.w;
@@ -854,11 +746,7 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
         for (int b = 0; b < NB; ++b)
 #pragma unroll
             for (int j = 0; j < FN; ++j) {
-                if constexpr (PB) {
-#pragma unroll
-                    for (int q = 0; q < 3; ++q)
-                        f.bp[q][j] = __builtin_bit_cast(u32x4, frag_mmajor_chunk<KF>(lb + q * TN * KF, wn + j * 32, 2 * s + h, lane));
-                } else if constexpr (B_MM) {
+                if constexpr (B_MM) {
                     const v4f u = frag_mmajor_chunk<KB>(lb, wn + j * 32, 4 * s + 2 * h, lane);
                     const v4f v = frag_mmajor_chunk<KB>(lb, wn + j * 32, 4 * s + 2 * h + 1, lane);
                     f.b[b][j][0] = u.x; f.b[b][j][1] = u.y; f.b[b][j][2] = u.z; f.b[b][j][3] = u.w;
@@ -874,44 +762,11 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
     };
     auto split_frags = [&](const Frags8& f, Planes& p) {
 #pragma unroll
-        for (int i = 0; i < FM; ++i) {
-#ifdef DCV_ABL_NOSPLIT_A   // diagnostic: what a pre-split A operand would save (wrong results)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                p.a1[i][e] = __builtin_amdgcn_perm(__float_as_uint(f.a[i][2 * e + 1]), __float_as_uint(f.a[i][2 * e]), 0x07060302);
-                p.a2[i][e] = p.a1[i][e];
-                p.a3[i][e] = p.a1[i][e];
-            }
-#else
-            if constexpr (PA) {
-                p.a1[i] = f.ap[0][i]; p.a2[i] = f.ap[1][i]; p.a3[i] = f.ap[2][i];
-            } else {
-                split3(f.a[i], p.a1[i], p.a2[i], p.a3[i]);
-            }
-#endif
-        }
+        for (int i = 0; i < FM; ++i) split3(f.a[i], p.a1[i], p.a2[i], p.a3[i]);
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
-            for (int j = 0; j < FN; ++j) {
-                if constexpr (PB) {
-                    p.b1[b][j] = f.bp[0][j]; p.b2[b][j] = f.bp[1][j]; p.b3[b][j] = f.bp[2][j];
-                } else {
-                    split3(f.b[b][j], p.b1[b][j], p.b2[b][j], p.b3[b][j]);
-                }
-            }
-    };
-    // Makes the planes opaque at this point of the program: their split must have been computed by here (the compiler
-    // otherwise sinks it to the first use, on the far side of a stage barrier).
-    [[maybe_unused]] auto pin_planes = [&](Planes& p) {
-#pragma unroll
-        for (int i = 0; i < FM; ++i) {
-            asm volatile("" : "+v"(p.a1[i]), "+v"(p.a2[i]), "+v"(p.a3[i]));
-        }
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int j = 0; j < FN; ++j) asm volatile("" : "+v"(p.b1[b][j]), "+v"(p.b2[b][j]), "+v"(p.b3[b][j]));
+            for (int j = 0; j < FN; ++j) split3(f.b[b][j], p.b1[b][j], p.b2[b][j], p.b3[b][j]);
     };
     // six products per accumulator tile, small cross terms first; `between(k)` runs after the k-th product type
     // (k = 0..5) -- the stage boundary hangs its scalar DMA issue there, under MFMAs already in flight
@@ -957,22 +812,12 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
     };
     auto mfma_group = [&](const Frags& f) {
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int b = 0; b < NB; ++b)
-#pragma unroll
-                for (int i = 0; i < FM; ++i)
-#pragma unroll
-                    for (int j = 0; j < FN; ++j)
-                        acc[b][i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[i][s], f.b[b][j][s], acc[b][i][j], 0, 0, 0);
+        for (int s = 0; s < 4; ++s) mfma_step(f, s);
     };
 
     const int64_t nst = (k_end - k_begin + KB - 1) / KB;
     DCV_STAMP_AT(0);
-#ifdef DCV_STAMP
-    if (threadIdx.x == 0 && blockIdx.x < 8192 && blockIdx.z == 0)
-        g_stamp[blockIdx.x * 8 + 7] = (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32);
-#endif
+    DCV_STAMP_HW(7);
     constexpr int G = KB / 8;
     auto compute_stage = [&](const float* cur) {
         const float* la = cur;
@@ -986,7 +831,6 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
             }
             return;
         }
-#ifndef DCV_NO_FRAG_DBUF
         // fragments double buffered in registers: group g+1 is read while group g feeds the MFMAs
         Frags f0, f1;
         read_frags(f0, la, lb, 0);
@@ -1001,94 +845,19 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
                 mfma_group(f1);
             }
         }
-#else
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            Frags f0;
-            read_frags(f0, la, lb, g);
-            add_asum(f0);
-            mfma_group(f0);
-        }
-#endif
     };
-    // ---- staged-epilogue geometry (used by the side-operand prefetch below and by the epilogue)
-    constexpr int LDSF = Cfg::NBUF * STAGE;   // floats of LDS the kernel owns
-    constexpr int EPASS = (TM * TN + LDSF - 1) / LDSF;
-    constexpr int RP = TM / (EPASS > 0 ? EPASS : 1);   // rows per pass
-    constexpr bool kStaged = (NB == 1) && (EPASS <= 2) && (TM % EPASS == 0) && (RP % (FM * 32) == 0) && (RP * TN <= LDSF);
-    constexpr int EC4 = TN / 4;                 // 16-byte segments per row
-    constexpr int ERPP = 256 / (EC4 > 256 ? 256 : EC4);   // rows per pass of the store loop
-    constexpr int ENQ = RP / ERPP;              // row segments per thread and epilogue pass
-    // Side operand of the epilogue (the stored activations whose derivative scales a dgrad tile): for a
-    // full tile its EPASS * ENQ row segments are requested before the first stage is awaited, so they
-    // stream in under the main loop instead of in a burst at the end while the matrix pipe idles
-    // (short-K products are otherwise HBM-bound for the length of their epilogue and idle before it).
-    constexpr bool kSidePre = kStaged && Epi::kSide && (EPASS * ENQ <= 16) && !Cfg::SPLIT;   // SPLIT: the planes need the registers
-    float4 side_pre[kSidePre ? EPASS * ENQ : 1];
+    using Eg = EpiGeom<Cfg, NB>;   // staged-epilogue geometry: the side-operand prefetch below and the epilogue
+    constexpr int EPASS = Eg::EPASS, RP = Eg::RP, C4 = Eg::C4, RPP = Eg::RPP, NQ = Eg::NQ;
+    constexpr bool kStaged = Eg::kStaged, kSidePre = Eg::template kSidePre<Epi>;
+    float4 side_pre[Eg::template NSIDE<Epi>];
     bool side_ready = false;
+    // ---------------------------------------------------------------- (2) ring loop
     // Two main loops in sequence.  The full stages of a workgroup whose tile is fully in range (the
     // common case) run the pure LDS-DMA loop: no staging registers are live in it, so the compiler has
     // no reason to wait on the vector-memory counter inside the MFMA phase.  Whatever remains -- the
     // ragged last stage of such a workgroup, or every stage of an edge tile / scalar-load / covariance
     // shift workgroup -- runs the register-staged loop behind it.
-    if constexpr (LS) {
-        // ---- split-from-LDS loop (TileCfg::PL bit 4).  The fp32 stage of BOTH operands arrives by LDS-DMA in a raw ring of
-        // two buffers behind the plane buffers (no VGPR round trip, the latency of the global loads stays hidden as in the
-        // ring loop); one pass per stage reads it back (4 ds_read_b128 per thread), splits it ONCE per workgroup and stores
-        // the three plane images the MFMA side reads -- the in-register split repeats that work in every wave that shares
-        // a fragment (two of the four waves of a 2 x 2 layout).  Per stage and wave: raw reads of stage st + 1, DMA issue
-        // of stage st + 2, the products of stage st from its planes, the split + plane stores of stage st + 1, one barrier.
-        // The launch guarantees K % KB == 0 and 16-byte rows; ragged row tiles read clamped rows (MMajorStage::init<true>).
-        constexpr int PERA = MMajorStage<TM, KA, VEC, GATHER>::PER, PERB = MMajorStage<TN, KBB, VEC, GATHER>::PER;
-        constexpr int RAW = Cfg::RAW_SZ;
-        float* const raw0 = lds + Cfg::NBUF * STAGE;
-        const int64_t nst_ls = (k_end - k_begin) / KB;
-        auto dma_raw = [&](int64_t k0, int rb) {
-            float* rbuf = raw0 + rb * RAW;
-            const unsigned l0 = ldsw + (unsigned)(Cfg::NBUF * STAGE + rb * RAW) * 4u;
-            if (pl_a_aff) am.glds_affine(am.tile_base(A, m0_ld, k0), l0);
-            else am.glds(k0, rbuf, t);
-            if (pl_b_aff) bm.glds_affine(bm.tile_base(B, n0, k0), l0 + (unsigned)(TM * KB) * 4u);
-            else bm.glds(k0, rbuf + TM * KB, t);
-        };
-        auto raw_to_regs = [&](int rb) {
-            const float* rbuf = raw0 + rb * RAW;
-#pragma unroll
-            for (int i = 0; i < PERA; ++i) am.r[i] = *reinterpret_cast<const float4*>(rbuf + (t + 256 * i) * 4);
-#pragma unroll
-            for (int i = 0; i < PERB; ++i) bm.r[i] = *reinterpret_cast<const float4*>(rbuf + TM * KB + (t + 256 * i) * 4);
-        };
-        auto split_to_planes = [&](float* pbuf) {
-            am.store_planes(pbuf, t);
-            bm.store_planes(pbuf + A_SZ, t);
-        };
-        if (nst_ls > 0) {
-            dma_raw(k_begin, 0);
-            if (nst_ls > 1) {
-                dma_raw(k_begin + KB, 1);
-                vm_wait<PERA + PERB>();   // stage 0 landed (stage 1 may still be in flight)
-            } else {
-                vm_wait<0>();
-            }
-            __syncthreads();
-            raw_to_regs(0);
-            split_to_planes(lds);
-            vm_wait<0>();                 // stage 1 landed
-            __syncthreads();              // planes of stage 0 published; raw buffer 0 read by everyone
-            for (int64_t st = 0; st < nst_ls; ++st) {
-                const int cur = (int)(st & 1);
-                if (st + 1 < nst_ls) raw_to_regs(cur ^ 1);
-                __builtin_amdgcn_sched_barrier(0);
-                if (st + 2 < nst_ls) dma_raw(k_begin + (st + 2) * KB, cur);   // raw buffer `cur` was read one barrier ago
-                __builtin_amdgcn_sched_barrier(0);
-                if (m0 + wm < d.M) compute_stage(lds + cur * STAGE);
-                if (st + 1 < nst_ls) split_to_planes(lds + (cur ^ 1) * STAGE);   // that plane buffer was multiplied one barrier ago
-                vm_wait<0>();
-                __syncthreads();
-            }
-        }
-    }
-    const bool dense_ok = !LS && (PRE || (!(PSA || PSB) && nst > 0 && stage_dense(k_begin) && affine_all()));   // split-at-store: every stage through registers
+    const bool dense_ok = nst > 0 && stage_dense(k_begin) && affine_all();
     const int64_t nfull = dense_ok ? (k_end - k_begin) / KB : 0;
     if (nfull > 0) {
         const int64_t nst = nfull;   // stages of the ring loop
@@ -1100,8 +869,7 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
         // the barrier skew, the DMA issue and the LDS latency, so the matrix pipe does not drain at
         // stage boundaries even with one wave per SIMD.
         constexpr int NBUF = Cfg::NBUF;
-        constexpr int GL = (A_MM ? NPA * MMajorStage<TM, KA, VEC, GATHER>::PER : KMajorStage<TM, KB, VEC, GATHER>::PER) +
-                           NB * (B_MM ? NPB * MMajorStage<TN, KBB, VEC, GATHER>::PER : KMajorStage<TN, KB, VEC, GATHER>::PER);  // DMA instructions per thread and stage
+        constexpr int GL = AStage::PER + NB * BStage::PER;  // DMA instructions per thread and stage
         static_assert((NBUF - 2) * GL <= 63, "vmcnt range");
         static_assert(Cfg::SPLIT || G % 2 == 0, "fragment double buffer parity");
 #pragma unroll
@@ -1109,15 +877,15 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
             if (s < nst) glds_stage(k_begin + s * KB, s);
         // boundary "-1 -> 0": stage 0 landed and published; every buffer is still free
         if constexpr (kSidePre) {
-            static_assert((NBUF - 2) * GL + EPASS * ENQ <= 63, "vmcnt range");
+            static_assert((NBUF - 2) * GL + EPASS * NQ <= 63, "vmcnt range");
             side_ready = epi.vec && (m0 + TM <= d.M) && (n0 + TN <= d.N);
             if constexpr (Epi::kMaskIn) side_ready = side_ready && epi.mask == nullptr;
             if (side_ready) {
-                const int ec4 = t % EC4, er0 = t / EC4;
+                const int ec4 = t % C4, er0 = t / C4;
 #pragma unroll
-                for (int q = 0; q < EPASS * ENQ; ++q)
-                    side_pre[q] = *reinterpret_cast<const float4*>(epi.side_ptr(m0 + er0 + q * ERPP, n0 + ec4 * 4));
-                vm_wait_younger<NBUF - 2, GL, EPASS * ENQ>(nst - 1);   // the side loads are younger than the stage DMAs
+                for (int q = 0; q < EPASS * NQ; ++q)
+                    side_pre[q] = *reinterpret_cast<const float4*>(epi.side_ptr(m0 + er0 + q * RPP, n0 + ec4 * 4));
+                vm_wait_younger<NBUF - 2, GL, EPASS * NQ>(nst - 1);   // the side loads are younger than the stage DMAs
             } else {
                 vm_wait_younger<NBUF - 2, GL>(nst - 1);
             }
@@ -1125,66 +893,19 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
             vm_wait_younger<NBUF - 2, GL>(nst - 1);
         }
         __syncthreads();
-#ifndef DCV_ABL_NOLOAD
         if (NBUF - 1 < nst) glds_stage(k_begin + (NBUF - 1) * KB, NBUF - 1);
-#endif
         DCV_STAMP_AT(1);
         DCV_STAMP_RT(5);
         if constexpr (Cfg::SPLIT) {
             // same ring, 16-deep steps: the last step of a stage is multiplied after the boundary work
             constexpr int S = KB / 16;
             Frags8 f0, f1;
-#ifdef DCV_PIPE_SPLIT
-            Planes pl0, pl1;
-#endif
             read_frags8(f0, lds, lds + A_SZ, 0);
-#ifdef DCV_PIPE_SPLIT
-            if constexpr (S == 2) split_frags(f0, pl0);
-#endif
             int cur_buf = 0;
             for (int64_t st = 0; st < nst; ++st) {
                 const float* la = lds + cur_buf * STAGE;
                 const float* lb = la + A_SZ;
                 const int nxt_buf = cur_buf + 1 == NBUF ? 0 : cur_buf + 1;
-#ifdef DCV_PIPE_SPLIT
-                if constexpr (S == 2) {
-                    // Software pipeline over the 16-deep steps: the six bf16 products of step s run from planes that were
-                    // split while step s - 1 was being multiplied, and the operands of step s + 1 are split under them --
-                    // one wave keeps the matrix pipe and the vector ALU busy together instead of in turns (with a single
-                    // workgroup per CU, the small-batch case, nobody else fills the gaps).  sched_group_barrier asks for
-                    // one MFMA followed by VPM vector-ALU instructions, over and over.
-                    constexpr int NMF = 6 * NB * FM * FN;                      // MFMAs of a step
-                    constexpr int NVA = 44 * (FM + NB * FN);                   // vector-ALU instructions of its split
-                    constexpr int VPM = (NVA + NMF - 1) / NMF;
-                    read_frags8(f1, la, lb, 1);
-                    mfma_planes(pl0, [](int) {});
-                    split_frags(f1, pl1);
-                    pin_planes(pl1);
-#pragma unroll
-                    for (int q = 0; q < NMF; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x002, VPM, 0);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    vm_wait_younger<NBUF - 2, GL>(nst - 2 - st);
-                    __syncthreads();
-                    read_frags8(f0, lds + nxt_buf * STAGE, lds + nxt_buf * STAGE + A_SZ, 0);
-                    const bool more = st + NBUF < nst;
-                    const int64_t k_next = k_begin + (st + NBUF) * KB;
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (more) glds_stage(k_next, cur_buf, 3);
-                    __builtin_amdgcn_sched_barrier(0);
-                    mfma_planes(pl1, [](int) {});
-                    split_frags(f0, pl0);
-                    pin_planes(pl0);
-#pragma unroll
-                    for (int q = 0; q < NMF; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x002, VPM, 0);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                } else
-#endif
                 if constexpr (S == 2) {
                     read_frags8(f1, la, lb, 1);
                     mfma16(f0);
@@ -1193,29 +914,21 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
                     Planes pl;
                     split_frags(f1, pl);
                     vm_wait_younger<NBUF - 2, GL>(nst - 2 - st);
-#ifndef DCV_ABL_NOBARRIER
                     __syncthreads();
-#endif
                     read_frags8(f0, lds + nxt_buf * STAGE, lds + nxt_buf * STAGE + A_SZ, 0);
                     const bool more = st + NBUF < nst;
                     const int64_t k_next = k_begin + (st + NBUF) * KB;
                     mfma_planes(pl, [&](int k) {
-#ifndef DCV_ABL_NOLOAD
                         if (k == 0 || k == 2) {
                             __builtin_amdgcn_sched_barrier(0);
                             if (more) glds_stage(k_next, cur_buf, k == 0 ? 1 : 2);
                             __builtin_amdgcn_sched_barrier(0);
                         }
-#endif
                     });
                 } else {
                     vm_wait_younger<NBUF - 2, GL>(nst - 2 - st);
-#ifndef DCV_ABL_NOBARRIER
                     __syncthreads();
-#endif
-#ifndef DCV_ABL_NOLOAD
                     if (st + NBUF < nst) glds_stage(k_begin + (st + NBUF) * KB, cur_buf);
-#endif
                     read_frags8(f1, lds + nxt_buf * STAGE, lds + nxt_buf * STAGE + A_SZ, 0);
                     mfma16(f0);
                     f0 = f1;
@@ -1253,24 +966,18 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
                     // synchronises and reads fragments of a stale buffer for nothing, which is cheaper
                     // than the accumulator copies hipcc generates when MFMAs sit on divergent paths.
                     vm_wait_younger<NBUF - 2, GL>(nst - 2 - st);
-#ifndef DCV_ABL_NOBARRIER
                     __syncthreads();
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                     pin_frags(f1);
                     if (dma_sub) sub_frags(f1);
                     add_asum(f1);
                     mfma_step(f1, 0);
                     __builtin_amdgcn_sched_barrier(0);
-#ifndef DCV_ABL_NOLOAD
                     if (st + NBUF < nst) glds_stage(k_begin + (st + NBUF) * KB, cur_buf, 1);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                     mfma_step(f1, 1);
                     __builtin_amdgcn_sched_barrier(0);
-#ifndef DCV_ABL_NOLOAD
                     if (st + NBUF < nst) glds_stage(k_begin + (st + NBUF) * KB, cur_buf, 2);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                     mfma_step(f1, 2);
                     __builtin_amdgcn_sched_barrier(0);
@@ -1288,8 +995,9 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
         DCV_STAMP_AT(1);
         DCV_STAMP_RT(5);
     }
+    // ---------------------------------------------------------------- (3) register-staged remainder
     const int64_t k_rem = k_begin + nfull * KB;
-    const int64_t nrem = (PRE || LS) ? 0 : (k_end - k_rem + KB - 1) / KB;
+    const int64_t nrem = (k_end - k_rem + KB - 1) / KB;
     if (nrem > 0) {
         resolve_stage(k_rem);
         load_stage(k_rem);
@@ -1311,6 +1019,7 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
             __syncthreads();
         }
     }
+    // ---------------------------------------------------------------- (4) tail hand-off
     if constexpr (MODE != kTN && NB == 1) {
         if (tail_chunk >= 0) {   // workgroup-uniform: one contraction chunk of the ragged last row tile (GemmDims::tail_split)
             constexpr int NACC = FM * FN * 16;
@@ -1347,22 +1056,8 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
             }
         }
     }
-#ifdef DCV_ABL_NOEPI
-    {   // keep every accumulator live (no dead-code elimination of the MFMAs), then skip the epilogue
-        float sink = 0.f;
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int j = 0; j < FN; ++j)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) sink += acc[b][i][j][e];
-        if (sink != 12345.678f) return;
-    }
-#endif
 
-    // ---------------------------------------------------------------- epilogue
+    // ---------------------------------------------------------------- (5) epilogue
     // The accumulator layout (column on the lane, rows across registers) would give 4-byte stores
     // at a row stride; instead the tile is transposed through LDS (the stage buffers are free now)
     // and leaves as 16-byte row segments: 4x fewer, fully coalesced store instructions, and the
@@ -1378,9 +1073,6 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
     static_assert(!Epi::kHead || kStaged, "the fused narrow layer needs the staged epilogue");
     if constexpr (kStaged) {
         float* tile = lds;  // [RP][TN]
-        constexpr int C4 = TN / 4;           // 16-byte segments per row
-        constexpr int RPP = 256 / C4;        // rows per pass of the store loop
-        constexpr int NQ = RP / RPP;         // row segments per thread and epilogue pass
         const int c4 = t % C4, r0 = t / C4;
         const int64_t col = n0 + c4 * 4;
         const int64_t left = d.N - col;
@@ -1528,7 +1220,7 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
 
 template <class Cfg, int NB>
 constexpr size_t gemm_lds_bytes() {
-    return ((size_t)Cfg::NBUF * (Cfg::A_SZ + NB * Cfg::B_SZ) + 2 * (size_t)Cfg::RAW_SZ) * sizeof(float);
+    return (size_t)Cfg::NBUF * (Cfg::A_SZ + NB * Cfg::B_SZ) * sizeof(float);
 }
 
 }  // namespace dcv

@@ -621,65 +621,30 @@ static CfgPick pick_cfg(int64_t M, int64_t N, int64_t K, int64_t k_chunk) {
     }
     return kPickBig;
 }
-// Split-from-LDS configurations (TileCfg::PL bit 4): NT products with 16-byte rows, no gathered rows and K a multiple of the
-// stage depth; returns 1 when the product does not qualify (the caller takes the in-register split).
-template <class Cfg, class Epi>
-static int launch_gemm_ls(const Operand& A, const Operand& B, int64_t M, int64_t N, int64_t K, const Epi& epi, hipStream_t s,
-                          int* tiles_m_out, const TailWs* tw) {
-    if (K % Cfg::KB != 0 || A.shift || B.shift) return 1;
-    GemmPlan pl;
-    int rc = prepare_gemm<kNT, Cfg, 1, Epi>(A, B, M, N, K, 0, epi, tiles_m_out, tw, &pl);
-    if (rc) return rc;
-    if (!pl.vec || pl.gather) return 1;
-    return launch_gemm_vec<kNT, Cfg, 1, true, false, Epi>(A, B, 0, pl.d, pl.splits, epi, s);
+// The tile family of a pick: the one place where the two are tied together (single and grouped launches)
+template <bool S, bool HEAD, class F>
+static int with_cfg(CfgPick pick, F&& f) {
+    switch (pick) {
+        case kPickNarrowN: return f(CfgNarrowNT<S>{});
+        case kPickNarrowM: return f(CfgNarrowMT<S>{});
+        case kPickHalfM: return f(CfgHalfMT<S>{});
+        case kPickQuarter:
+            if constexpr (!HEAD) return f(CfgQuarterT<S>{});
+            else return f(CfgHalfMT<S>{});
+        default: return f(CfgBigT<S>{});
+    }
 }
 
 template <int MODE, bool S, class Epi>
 static int launch_gemm_mode(const Operand& A, const Operand& B, int64_t M, int64_t N, int64_t K, int64_t k_chunk,
                             const Epi& epi, hipStream_t s, int* tiles_m_out, const TailWs* tw = nullptr) {
-#ifdef DCV_BIGCFG
-    using Big = CfgBig;
-#else
-    using Big = CfgBigT<S>;
-#endif
     const CfgPick pick = pick_cfg<MODE, Epi::kHead>(M, N, K, k_chunk);
-#ifdef DCV_PS_EXPERIMENT   // tools/planes_bench only: measured SLOWER than the LDS-DMA ring + in-register split
-    if constexpr (S && MODE != kTN) {
-        // Small grids of the split flavour (the row-parallel products of a small batch: one or two workgroups per CU) are
-        // bound by the vector ALU's operand splitting: stage through registers and split once per workgroup on the way to
-        // LDS (TileCfg::PL bits 2 / 3) -- both operands of an NT product, the A operand of an NN product.  Bit-identical
-        // results, half the splitting work -- and 25.2 vs 22.4 us at 8192 x 256 x 512, 12.0 vs 10.5 us at 8202 x 128 x 256:
-        // the register-staged loop exposes the load latency the DMA ring hides.
-        constexpr int PS = MODE == kNT ? 12 : 4;
-        static const bool ps_on = [] { const char* e = getenv("DCV_SPLIT_AT_STORE"); return !(e && e[0] == '0'); }();
-        if (ps_on && K % 32 == 0) {
-            if (pick == kPickHalfM || (pick == kPickQuarter && Epi::kHead))
-                return launch_gemm_cfg<MODE, TileCfg<2, 2, 1, 2, 32, 2, true, PS>, 1, Epi>(A, B, 0, M, N, K, k_chunk, epi, s, tiles_m_out, tw);
-            if (pick == kPickNarrowM) return launch_gemm_cfg<MODE, TileCfg<1, 4, 1, 1, 32, 2, true, PS>, 1, Epi>(A, B, 0, M, N, K, k_chunk, epi, s, tiles_m_out, tw);
-            if constexpr (!Epi::kHead) {
-                if (pick == kPickQuarter) return launch_gemm_cfg<MODE, TileCfg<2, 2, 1, 1, 32, 2, true, PS>, 1, Epi>(A, B, 0, M, N, K, k_chunk, epi, s, tiles_m_out, tw);
-            }
-        }
-    }
+#ifdef DCV_BIGCFG   // diagnostic override of the big tile (tools/gemm_bench)
+    if (pick == kPickBig) return launch_gemm_cfg<MODE, CfgBig, 1, Epi>(A, B, 0, M, N, K, k_chunk, epi, s, tiles_m_out, tw);
 #endif
-#ifdef DCV_PS_EXPERIMENT   // tools/planes_bench only (-DDCV_PS_EXPERIMENT, DCV_LS=1): bit-identical and measured SLOWER (25.7 vs 22.8 us at 8192 x 256 x 512)
-    if constexpr (S && MODE == kNT && !Epi::kHead) {
-        static const bool ls_on = [] { const char* e = getenv("DCV_LS"); return e && e[0] == '1'; }();
-        if (ls_on && pick == kPickQuarter) {
-            const int rc = launch_gemm_ls<TileCfg<2, 2, 1, 1, 32, 2, true, 28>, Epi>(A, B, M, N, K, epi, s, tiles_m_out, tw);
-            if (rc != 1) return rc;
-        }
-    }
-#endif
-    switch (pick) {
-        case kPickNarrowN: return launch_gemm_cfg<MODE, CfgNarrowNT<S>, 1, Epi>(A, B, 0, M, N, K, k_chunk, epi, s, tiles_m_out, tw);
-        case kPickNarrowM: return launch_gemm_cfg<MODE, CfgNarrowMT<S>, 1, Epi>(A, B, 0, M, N, K, k_chunk, epi, s, tiles_m_out, tw);
-        case kPickHalfM: return launch_gemm_cfg<MODE, CfgHalfMT<S>, 1, Epi>(A, B, 0, M, N, K, k_chunk, epi, s, tiles_m_out, tw);
-        case kPickQuarter:
-            if constexpr (!Epi::kHead) return launch_gemm_cfg<MODE, CfgQuarterT<S>, 1, Epi>(A, B, 0, M, N, K, k_chunk, epi, s, tiles_m_out, tw);
-            else return launch_gemm_cfg<MODE, CfgHalfMT<S>, 1, Epi>(A, B, 0, M, N, K, k_chunk, epi, s, tiles_m_out, tw);
-        default: return launch_gemm_cfg<MODE, Big, 1, Epi>(A, B, 0, M, N, K, k_chunk, epi, s, tiles_m_out, tw);
-    }
+    return with_cfg<S, Epi::kHead>(pick, [&](auto c) {
+        return launch_gemm_cfg<MODE, decltype(c), 1, Epi>(A, B, 0, M, N, K, k_chunk, epi, s, tiles_m_out, tw);
+    });
 }
 
 template <int MODE, class Epi>
@@ -694,18 +659,6 @@ static int launch_gemm(const Operand& A, const Operand& B, int64_t M, int64_t N,
 }
 
 // ---- grouped NT products (gemm_group_kernel)
-template <bool S, bool HEAD, class F>
-static int with_cfg(CfgPick pick, F&& f) {   // the tile family launch_gemm_mode takes for `pick`
-    switch (pick) {
-        case kPickNarrowN: return f(CfgNarrowNT<S>{});
-        case kPickNarrowM: return f(CfgNarrowMT<S>{});
-        case kPickHalfM: return f(CfgHalfMT<S>{});
-        case kPickQuarter:
-            if constexpr (!HEAD) return f(CfgQuarterT<S>{});
-            else return f(CfgHalfMT<S>{});
-        default: return f(CfgBigT<S>{});
-    }
-}
 // (diagnostic) DCV_EVAL_GROUP_TILES=0: every member keeps the tile family of the single-batch launch
 inline bool group_retile_enabled() {
     static const bool on = [] { const char* e = getenv("DCV_EVAL_GROUP_TILES"); return !(e && e[0] == '0'); }();
@@ -805,120 +758,6 @@ int gemm_nn_store(const Operand& A, const Operand& B, int64_t M, int64_t N, int6
 int launch_wgrad_dgrad(const Operand& A1, const Operand& B1, int64_t M1, int64_t N1, int64_t K1, int64_t k_chunk1, const EpiSlab& e1,
                        const Operand& A2, const Operand& B2, int64_t M2, int64_t N2, int64_t K2, const EpiActGrad& e2, int* tiles_m_out2,
                        const TailWs* tw, hipStream_t s);
-
-// ------------------------------------------------------------------ plane operands (TileCfg::PL)
-// Plane form of an fp32 matrix [rows][cols]: row r is [plane 1 | plane 2 | plane 3], each Kp = round_up(cols, 32) bf16
-// (zero padded), the pieces of split3 -- x = p1 + p2 + p3 exactly, truncation split.  In float units the row pitch is
-// 3 * Kp / 2 and the plane stride Kp / 2.  The engine keeps the training matrix and the weights in this form next to
-// the fp32 originals: the split is then paid once per matrix instead of once per use inside the product's main loop.
-__host__ __device__ inline int64_t planes_kp(int64_t cols) { return (cols + 31) / 32 * 32; }
-__host__ __device__ inline int64_t planes_ld(int64_t cols) { return 3 * planes_kp(cols) / 2; }        // floats
-__host__ __device__ inline int64_t planes_pstride(int64_t cols) { return planes_kp(cols) / 2; }       // floats
-inline size_t planes_bytes(int64_t rows, int64_t cols) { return (size_t)rows * (size_t)planes_ld(cols) * sizeof(float); }
-// TRANS: dst row = src column (the planes of the transpose; small matrices only -- the loads are strided)
-template <bool TRANS>
-__global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ src, int64_t ld, int64_t rows, int64_t cols,
-                                                           float* __restrict__ dst, int64_t rows_out) {
-    const int64_t orows = TRANS ? cols : rows, ocols = TRANS ? rows : cols;   // extents of the matrix being written
-    const int64_t kp8 = planes_kp(ocols) / 8, ldp = planes_ld(ocols), ps = planes_pstride(ocols);
-    const int64_t total = rows_out * kp8;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t r = i / kp8, g = i - r * kp8;
-        float x[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int64_t k = 8 * g + e;
-            x[e] = (r < orows && k < ocols) ? (TRANS ? src[k * ld + r] : src[r * ld + k]) : 0.f;
-        }
-        u32x4 p1, p2, p3;
-        split3(x, p1, p2, p3);
-        float* o = dst + r * ldp + g * 4;
-        *reinterpret_cast<u32x4*>(o) = p1;
-        *reinterpret_cast<u32x4*>(o + ps) = p2;
-        *reinterpret_cast<u32x4*>(o + 2 * ps) = p3;
-    }
-}
-// rows_out >= (TRANS ? cols : rows): rows past the matrix are written as zeros
-template <bool TRANS>
-static int launch_split_planes(const float* src, int64_t ld, int64_t rows, int64_t cols, float* dst, int64_t rows_out, hipStream_t s) {
-    const int64_t ocols = TRANS ? rows : cols;
-    const int64_t total = rows_out * (planes_kp(ocols) / 8);
-    if (total <= 0) return DCV_OK;
-    int64_t blocks = cdiv(total, 256);
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(split_planes_kernel<TRANS>, dim3((unsigned)blocks), dim3(256), 0, s, src, ld, rows, cols, dst, rows_out);
-    DCV_CHECK_LAUNCH();
-    return DCV_OK;
-}
-inline Operand make_plane_operand(const float* planes, int64_t cols, const RowMap& rows = RowMap{nullptr, 0, 0, 0}) {
-    Operand o;
-    o.p = planes;
-    o.ld = planes_ld(cols);
-    o.rows = rows;
-    o.shift = nullptr;
-    o.vec_ok = (reinterpret_cast<uintptr_t>(planes) & 15) == 0;
-    o.planes = 1;
-    o.pstride = planes_pstride(cols);
-    return o;
-}
-
-// Tile shapes of the plane kernels (LDS per workgroup in brackets):
-//   PL = 3 (both operands pre-split, no vector-ALU work in the main loop):
-//          128 x 128, 16-deep stages, ring of 3 [72 KiB] ; 64 x 128, 32-deep stages [72 KiB]
-//   PL = 2 (B pre-split, A split in registers): 128 x 128 [80 KiB] ; 64 x 128 [64 KiB]
-#ifdef DCV_PL3_BIG   // diagnostic override (tools/planes_bench): KB, NBUF of the PL = 3 128 x 128 tile
-template <int PL> using CfgPlBig = TileCfg<2, 2, 2, 2, PL == 3 ? DCV_PL3_BIG : 32, 2, true, PL>;
-#else
-template <int PL> using CfgPlBig = TileCfg<2, 2, 2, 2, PL == 3 ? 16 : 32, PL == 3 ? 3 : 2, true, PL>;
-#endif
-#ifndef DCV_PLH_NBUF
-#define DCV_PLH_NBUF 2
-#endif
-template <int PL> using CfgPlHalf = TileCfg<2, 2, 1, 2, 32, DCV_PLH_NBUF, true, PL>;
-#ifndef DCV_PLQ_NBUF
-#define DCV_PLQ_NBUF 2
-#endif
-template <int PL> using CfgPlQuarter = TileCfg<2, 2, 1, 1, 32, DCV_PLQ_NBUF, true, PL>;   // 64 x 64: two workgroups per CU on a small grid
-
-// NT product with plane operands: C[M,N] = A[M,K] . B[N,K]^T.  Returns DCV_EINVAL-free "not applicable" (1) when the
-// shape or the operands do not qualify -- the caller then takes the fp32-operand kernel -- and a DCV_E* (< 0) on error.
-template <int PL, class Epi>
-static int launch_gemm_planes(const Operand& A, const Operand& B, int64_t M, int64_t N, int64_t K, const Epi& epi, hipStream_t s,
-                              int* tiles_m_out = nullptr) {
-    static_assert(PL >= 1 && PL <= 3, "PL");
-    const bool a_ok = (PL & 1) ? (A.planes == 1 && A.pstride % 4 == 0) : (A.planes == 0);
-    const bool b_ok = (PL & 2) ? (B.planes == 1 && B.pstride % 4 == 0) : (B.planes == 0);
-    if (!a_ok || !b_ok || !A.vec_ok || !B.vec_ok || A.ld % 4 != 0 || B.ld % 4 != 0) return 1;
-    if (K % 32 != 0 || K < 64 || N <= 32 || M <= 32) return 1;
-    if (A.rows.idx != nullptr || B.rows.idx != nullptr || A.shift || B.shift) return 1;
-    if (A.ld >= kMaxAffineLd || B.ld >= kMaxAffineLd) return 1;
-    auto go = [&](auto cfg) -> int {
-        using Cfg = decltype(cfg);
-        GemmDims d;
-        d.M = M; d.N = N; d.K = K; d.k_chunk = K;
-        d.tiles_m = (int)cdiv(M, Cfg::TM);
-        d.tiles_n = (int)cdiv(N, Cfg::TN);
-        if (tiles_m_out) *tiles_m_out = d.tiles_m;
-        static int env = -1;
-        if (env < 0) { const char* e = getenv("DCV_XCD_REMAP"); env = e ? atoi(e) : 1; }
-        d.xcd_remap = env && d.tiles_m % 8 == 0 && d.tiles_n > 1;
-        const int64_t tiles = (int64_t)d.tiles_m * d.tiles_n;
-        DCV_REQUIRE(tiles > 0 && tiles < (1ll << 31), "gemm: grid out of range (tiles=%lld)", (long long)tiles);
-        return launch_gemm_vec<kNT, Cfg, 1, true, false, Epi>(A, B, 0, d, 1, epi, s);
-    };
-    const int64_t want = 2 * (int64_t)num_cus();
-#ifdef DCV_PL_FORCE_BIG
-    return go(CfgPlBig<PL>{});
-#endif
-    if (cdiv(M, 128) * cdiv(N, 128) < want) {
-        // between one and two 64 x 128 workgroups per CU: 64 x 64 tiles, as the fp32-operand kernels choose (pick_cfg)
-#ifndef DCV_NO_PLQ
-        if (cdiv(M, 64) * cdiv(N, 128) < want && cdiv(M, 64) * cdiv(N, 128) >= want / 2 && N % 64 == 0) return go(CfgPlQuarter<PL>{});
-#endif
-        return go(CfgPlHalf<PL>{});
-    }
-    return go(CfgPlBig<PL>{});
-}
 
 inline Operand make_operand(const float* p, int64_t ld, int64_t inner_extent, const RowMap& rows = RowMap{nullptr, 0, 0, 0},
                             const float* shift = nullptr) {

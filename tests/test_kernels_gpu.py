@@ -62,12 +62,20 @@ GEMM_SHAPES = [(128, 128, 64), (300, 200, 100), (64, 4, 128), (4, 128, 1000), (2
                (129, 130, 33), (32, 32, 2), (512, 2, 7), (2, 512, 40)]
 
 
-@pytest.mark.parametrize("mode", ["nt", "nn", "tn"])
+# every product kind in both arithmetic modes; the split case (the library's default mode, the one this test ran in
+# before it had the parameter) keeps the id it always had
+GEMM_KIND_MODES = [pytest.param(kind, gm, id=kind if gm == "split" else kind + "-" + gm)
+                   for kind in ("nt", "nn", "tn") for gm in ("native", "split")]
+
+
+@pytest.mark.parametrize("mode,gemm_mode", GEMM_KIND_MODES)
 @pytest.mark.parametrize("M,N,K", GEMM_SHAPES)
-def test_gemm_exact_on_integers(mode, M, N, K):
+def test_gemm_exact_on_integers(mode, M, N, K, gemm_mode):
     """Small-integer operands make every fp32 product and partial sum exact, so the MFMA
     engine must agree bit for bit with an int64 product whatever the tile / k-slot order;
-    B is asymmetric, so a transposed C write cannot pass."""
+    B is asymmetric, so a transposed C write cannot pass.  Operands in [-4, 4] are exact
+    in bf16 as well, so the same holds for the split flavour: every ragged shape is
+    checked in both arithmetic modes."""
     from deep_cartograph_amd import hip
 
     rng = np.random.Generator(np.random.PCG64(M * 7 + N * 3 + K))
@@ -76,13 +84,19 @@ def test_gemm_exact_on_integers(mode, M, N, K):
     ref = (A @ B).astype(np.float32)
     Af = A.astype(np.float32)
     Bf = B.astype(np.float32)
-    if mode == "nt":
-        out = hip.gemm("nt", dev(Af), dev(np.ascontiguousarray(Bf.T)))
-    elif mode == "nn":
-        out = hip.gemm("nn", dev(Af), dev(Bf))
-    else:
-        out = hip.gemm("tn", dev(np.ascontiguousarray(Af.T)), dev(Bf))
-    np.testing.assert_array_equal(out.cpu().numpy(), ref)
+    start = hip.get_gemm_mode()
+    try:
+        hip.set_gemm_mode(gemm_mode)
+        if mode == "nt":
+            out = hip.gemm("nt", dev(Af), dev(np.ascontiguousarray(Bf.T)))
+        elif mode == "nn":
+            out = hip.gemm("nn", dev(Af), dev(Bf))
+        else:
+            out = hip.gemm("tn", dev(np.ascontiguousarray(Af.T)), dev(Bf))
+        out = out.cpu().numpy()
+    finally:
+        hip.set_gemm_mode(start)
+    np.testing.assert_array_equal(out, ref)
 
 
 @pytest.mark.parametrize("mode", ["nt", "nn", "tn"])

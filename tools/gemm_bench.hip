@@ -2,6 +2,7 @@
 // the Deep-TICA step (not part of the product build):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I deep_cartograph_amd/csrc tools/gemm_bench.hip \
 //         deep_cartograph_amd/csrc/common.hip -o tools/gemm_bench
+//   ./gemm_bench [rows=131072] [iters=20] [cov | wgrad | zero | check]
 #include "gemm_kernels.h"
 #include <vector>
 #include <cstdlib>
@@ -87,8 +88,152 @@ static void dump_stamps(const char* what, int nblk) {
 static void dump_stamps(const char*, int) {}
 #endif
 
+// `check` mode: two correctness checks of the split flavour on the L0 forward shape (M rows, N = 256, K = 512).
+//   * the contraction-split tail tile (GemmDims::tail_split) against the plain launch: only the rows of the ragged last
+//     tile may differ, by rounding, and repeated launches are bit-identical (DCV_TAIL_STRESS=n: n launches that alternate
+//     two A operands);
+//   * DCV_CHECK_BACKWARD=1: dgrad and wgrad, FP32-input MFMA against the split flavour.
+static int check_split(int64_t M, int it) {
+    const int64_t N = 256, K = 512;
+    const int act = DCV_ACT_LEAKY_RELU;
+    set_gemm_split(true);
+    float *A, *B, *C0, *C1, *bias;
+    CK(hipMalloc(&A, (size_t)M * K * 4));
+    CK(hipMalloc(&B, (size_t)N * K * 4));
+    CK(hipMalloc(&C0, (size_t)M * N * 4));
+    CK(hipMalloc(&C1, (size_t)M * N * 4));
+    CK(hipMalloc(&bias, (size_t)N * 4));
+    std::vector<float> h((size_t)M * K), hb((size_t)N * K), hc0((size_t)M * N), hc1((size_t)M * N);
+    srand(7);
+    for (auto& v : h) v = ((float)rand() / RAND_MAX - 0.5f) * 3.f;
+    for (auto& v : hb) v = ((float)rand() / RAND_MAX - 0.5f) * 0.2f;
+    CK(hipMemcpy(A, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(B, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(bias, hb.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+    hipStream_t s = 0;
+    const Operand a = make_operand(A, K, K), b = make_operand(B, K, K);
+    EpiBiasAct e0{C0, N, bias, act, true};
+    EpiBiasAct e1{C1, N, bias, act, true};
+    const double flop = 2.0 * M * N * K;
+    auto report = [&](const char* what, double ms) { printf("%-34s %9.1f us %7.1f TF\n", what, ms * 1e3, flop / ms / 1e9); };
+    int rc = launch_gemm<kNT, EpiBiasAct>(a, b, M, N, K, 0, e0, s);
+    if (rc) { printf("reference launch failed: %s\n", dcv_last_error()); return 1; }
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(hc0.data(), C0, hc0.size() * 4, hipMemcpyDeviceToHost));
+    report("in-register split", time_ms([&] { launch_gemm<kNT, EpiBiasAct>(a, b, M, N, K, 0, e0, s); }, it));
+    {   // contraction-split tail tile (GemmDims::tail_split): only the rows of the ragged last tile may differ, by rounding
+        TailWs tw;
+        if (!alloc_tail_ws(&tw, 8)) { printf("tail workspace: allocation failed\n"); return 1; }
+        CK(hipMemset(C1, 0xff, (size_t)M * N * 4));
+        rc = launch_gemm<kNT, EpiBiasAct>(a, b, M, N, K, 0, e1, s, nullptr, &tw);
+        if (rc) { printf("tail launch failed: %s\n", dcv_last_error()); return 1; }
+        CK(hipDeviceSynchronize());
+        CK(hipMemcpy(hc1.data(), C1, hc1.size() * 4, hipMemcpyDeviceToHost));
+        size_t nd = 0, first = hc0.size();
+        double md = 0;
+        for (size_t i = 0; i < hc0.size(); ++i)
+            if (memcmp(&hc0[i], &hc1[i], 4) != 0) {
+                if (first == hc0.size()) first = i;
+                ++nd;
+                const double dd = fabs((double)hc0[i] - (double)hc1[i]);
+                if (!(dd <= md)) md = dd;
+            }
+        printf("  tail k-split vs plain: %zu elements differ (first in row %zu of %lld, max |d| %.3g)\n", nd, first / (size_t)N, (long long)M, md);
+        report("in-register split + tail k-split", time_ms([&] { launch_gemm<kNT, EpiBiasAct>(a, b, M, N, K, 0, e1, s, nullptr, &tw); }, it));
+        for (int r = 0; r < 3; ++r) {   // repeated launches reuse the tickets
+            launch_gemm<kNT, EpiBiasAct>(a, b, M, N, K, 0, e1, s, nullptr, &tw);
+        }
+        CK(hipDeviceSynchronize());
+        std::vector<float> hc2(hc1.size());
+        CK(hipMemcpy(hc2.data(), C1, hc2.size() * 4, hipMemcpyDeviceToHost));
+        printf("  tail k-split run-to-run: %s\n", memcmp(hc1.data(), hc2.data(), hc1.size() * 4) == 0 ? "bit-identical" : "DIFFERENT");
+        if (getenv("DCV_TAIL_STRESS")) {   // alternate two different A operands: a stale partial of the other one would change bits
+            float* A2;
+            CK(hipMalloc(&A2, (size_t)M * K * 4));
+            std::vector<float> h2(h.size());
+            for (size_t i = 0; i < h.size(); ++i) h2[i] = h[i] * 1.7f + 0.3f;
+            CK(hipMemcpy(A2, h2.data(), h2.size() * 4, hipMemcpyHostToDevice));
+            const Operand a2 = make_operand(A2, K, K);
+            const size_t tail0 = (size_t)(M / 64 * 64) * N, ntail = hc1.size() - tail0;
+            std::vector<float> refA(hc1.begin() + tail0, hc1.end()), refB(ntail), got(ntail);
+            launch_gemm<kNT, EpiBiasAct>(a2, b, M, N, K, 0, e1, s, nullptr, &tw);
+            CK(hipDeviceSynchronize());
+            CK(hipMemcpy(refB.data(), C1 + tail0, ntail * 4, hipMemcpyDeviceToHost));
+            const int iters = atoi(getenv("DCV_TAIL_STRESS"));
+            int bad = 0;
+            for (int r = 0; r < iters; ++r) {
+                const bool useA = (r * 7 % 3) != 0;
+                launch_gemm<kNT, EpiBiasAct>(useA ? a : a2, b, M, N, K, 0, e1, s, nullptr, &tw);
+                CK(hipMemcpyAsync(got.data(), C1 + tail0, ntail * 4, hipMemcpyDeviceToHost, s));
+                CK(hipStreamSynchronize(s));
+                if (memcmp(got.data(), (useA ? refA : refB).data(), ntail * 4) != 0) ++bad;
+            }
+            printf("  tail stress: %d of %d launches with alternating operands differ from their reference\n", bad, iters);
+        }
+    }
+    if (getenv("DCV_CHECK_BACKWARD")) {   // dgrad (NN + activation-gradient epilogue) and wgrad (TN, split-K slabs): fp32-input MFMA vs split flavour
+        const int64_t K2 = 128;   // dZ[M, K2] . W[K2, N] -> dX[M, N] ;  dZ[M, K2]^T . Hin[M, N] -> dW[K2, N]
+        float *dZ, *W, *dX0, *dX1, *bp0, *bp1, *slab0, *slab1;
+        const int64_t kc = 288, splits = (M + kc - 1) / kc;
+        CK(hipMalloc(&dZ, (size_t)M * K2 * 4));
+        CK(hipMalloc(&W, (size_t)K2 * N * 4));
+        CK(hipMalloc(&dX0, (size_t)M * N * 4));
+        CK(hipMalloc(&dX1, (size_t)M * N * 4));
+        CK(hipMalloc(&bp0, (size_t)(M / 32 + 8) * N * 4));
+        CK(hipMalloc(&bp1, (size_t)(M / 32 + 8) * N * 4));
+        CK(hipMalloc(&slab0, (size_t)splits * K2 * N * 4));
+        CK(hipMalloc(&slab1, (size_t)splits * K2 * N * 4));
+        CK(hipMemcpy(dZ, h.data(), (size_t)M * K2 * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(W, hb.data(), (size_t)K2 * N * 4, hipMemcpyHostToDevice));
+        const Operand ad = make_operand(dZ, K2, K2), bd = make_operand(W, N, N), hin = make_operand(C0, N, N);
+        int tm0 = 0, tm1 = 0;
+        EpiActGrad g0{dX0, N, C0, N, DCV_ACT_LEAKY_RELU, bp0, N, true}, g1{dX1, N, C0, N, DCV_ACT_LEAKY_RELU, bp1, N, true};
+        set_gemm_split(true);
+        rc = launch_gemm<kNN, EpiActGrad>(ad, bd, M, N, K2, 0, g0, s, &tm0);
+        EpiSlab s0{slab0, K2, N, 1, 0, true, splits};
+        rc |= launch_gemm<kTN, EpiSlab>(ad, hin, K2, N, M, kc, s0, s);
+        set_gemm_split(false);
+        rc |= launch_gemm<kNN, EpiActGrad>(ad, bd, M, N, K2, 0, g1, s, &tm1);
+        EpiSlab s1{slab1, K2, N, 1, 0, true, splits};
+        rc |= launch_gemm<kTN, EpiSlab>(ad, hin, K2, N, M, kc, s1, s);
+        set_gemm_split(true);
+        if (rc) { printf("backward check launch failed: %s\n", dcv_last_error()); return 1; }
+        CK(hipDeviceSynchronize());
+        auto cmp = [&](const char* what, const float* d0, const float* d1, size_t n) {
+            std::vector<float> a0(n), a1(n);
+            CK(hipMemcpy(a0.data(), d0, n * 4, hipMemcpyDeviceToHost));
+            CK(hipMemcpy(a1.data(), d1, n * 4, hipMemcpyDeviceToHost));
+            double md = 0, mx = 0;
+            size_t w = 0;
+            for (size_t i = 0; i < n; ++i) {
+                const double dd = fabs((double)a0[i] - (double)a1[i]);
+                if (!(dd <= md)) { md = dd; w = i; }
+                if (fabs((double)a0[i]) > mx) mx = fabs((double)a0[i]);
+            }
+            printf("  %s: fp32-input MFMA vs split max |d| %.3g of %.3g (rel %.2e) at element %zu\n", what, md, mx, md / mx, w);
+        };
+        cmp("dgrad dX", dX0, dX1, (size_t)M * N);
+        printf("  (row tiles %d / %d)\n", tm0, tm1);
+        cmp("dgrad bias partials", bp0, bp1, (size_t)(tm0 < tm1 ? tm0 : tm1) * N);
+        // slabs summed on the host
+        std::vector<float> sl0((size_t)splits * K2 * N), sl1(sl0.size());
+        CK(hipMemcpy(sl0.data(), slab0, sl0.size() * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(sl1.data(), slab1, sl1.size() * 4, hipMemcpyDeviceToHost));
+        double md = 0, mx = 0;
+        for (size_t i = 0; i < (size_t)K2 * N; ++i) {
+            double a0 = 0, a1 = 0;
+            for (int64_t z = 0; z < splits; ++z) { a0 += sl0[z * K2 * N + i]; a1 += sl1[z * K2 * N + i]; }
+            if (fabs(a0 - a1) > md) md = fabs(a0 - a1);
+            if (fabs(a0) > mx) mx = fabs(a0);
+        }
+        printf("  wgrad (kc %lld, %lld splits): fp32-input MFMA vs split max |d| %.3g of %.3g (rel %.2e)\n", (long long)kc, (long long)splits, md, mx, md / mx);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const int64_t R = argc > 1 ? atoll(argv[1]) : 131072;
+    if (argc > 3 && !strcmp(argv[3], "check")) return check_split(R, argc > 2 ? atoi(argv[2]) : 20);
     const int F = 512, H1 = 256, H2 = 128;
     float *X, *W1, *Hb, *dZ, *slab, *W2, *H2b, *bpart, *b1;
     CK(hipMalloc(&X, (size_t)R * (F + 64) * 4));
