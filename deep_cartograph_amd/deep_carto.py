@@ -1,14 +1,16 @@
 """`deep_carto`-style entry point for the accelerated part of the workflow:
-(filter_features) -> train_colvars -> (traj_projection of supplementary data) -> traj_cluster,
-starting from pre-computed feature matrices (PLUMED COLVAR text or the binary .npy fast path).
-The reference's steps 0-2 (geometry analysis, augmentation, PLUMED featurisation;
-deep_carto.py:191-290) need MDAnalysis and the plumed binary and are out of scope, so the YAML
-keeps the reference's `filter_features` / `train_colvars` / `traj_cluster` sections and the CLI
-takes colvars files where the reference takes trajectories.  Feature filtering needs only the
-colvars files: it runs when the YAML has a `filter_features` section and no -features file is given.
+(compute_features) -> (filter_features) -> train_colvars -> (traj_projection of supplementary data) -> traj_cluster,
+starting from trajectories (.dcd / .npy coordinates plus a PDB topology: distances and virtual dihedrals are computed
+on the device) or from pre-computed feature matrices (PLUMED COLVAR text or the binary .npy fast path).
+The reference's geometry analysis and augmentation steps (deep_carto.py:191-290) need MDAnalysis and are out of
+scope; its PLUMED featurisation is replaced by `compute_features` for the feature kinds trajectory.py documents.
+The YAML keeps the reference's `compute_features` / `filter_features` / `train_colvars` / `traj_cluster` sections.
+Feature filtering needs only the feature matrices: it runs when the YAML has a `filter_features` section and no
+-features file is given.
 
-    python -m deep_cartograph_amd.deep_carto -conf config.yml -colvars a.dat b.dat -out run1 \
-           [-dim 2] [-cvs pca tica deep_tica] [-sup_colvars c.dat] [-features feats.txt] [-restart]
+    python -m deep_cartograph_amd.deep_carto -conf config.yml -traj a.dcd b.dcd -top a.pdb -out run1 \
+           [-sup_traj c.dcd] [-dim 2] [-cvs pca tica deep_tica] [-features feats.txt] [-restart]
+    python -m deep_cartograph_amd.deep_carto -conf config.yml -colvars a.dat b.dat -out run1 [-sup_colvars c.dat] ...
 """
 from __future__ import annotations
 
@@ -20,34 +22,57 @@ import time
 from typing import Dict, List, Optional
 
 from .common import get_unique_path, read_configuration, read_features_list
-from .tools import filter_features, traj_cluster, traj_projection, train_colvars
+from .tools import compute_features, filter_features, traj_cluster, traj_projection, train_colvars
 
 logger = logging.getLogger("deep_cartograph")
 
 
 def deep_cartograph(configuration: Dict, colvars_paths: List[str], sup_colvars_paths: Optional[List[str]] = None,
                     features_list: Optional[List[str]] = None, dimension: Optional[int] = None, cvs: Optional[List[str]] = None,
-                    restart: bool = False, output_folder: Optional[str] = None) -> Dict[str, Dict]:
-    """(filter_features) -> train_colvars -> traj_projection (supplementary colvars) -> traj_cluster per CV
-    (reference deep_carto.py:292-361).  A `filter_features` section in the configuration selects the features
-    first unless `features_list` is given.  `restart` reuses the output folder and skips what exists."""
+                    restart: bool = False, output_folder: Optional[str] = None, trajectory_data: Optional[List[str]] = None,
+                    topology_data: Optional[List[str]] = None, sup_trajectory_data: Optional[List[str]] = None) -> Dict[str, Dict]:
+    """(compute_features) -> (filter_features) -> train_colvars -> traj_projection (supplementary colvars) -> traj_cluster
+    per CV (reference deep_carto.py:292-361).  With `trajectory_data` (and `topology_data`: one PDB for all, or one per
+    trajectory) the `compute_features` section runs first and its outputs become `colvars_paths`; `sup_trajectory_data`
+    likewise become `sup_colvars_paths`, always with the FIRST topology.  Giving both is an error.  A `filter_features` section in the configuration selects
+    the features first unless `features_list` is given.  `restart` reuses the output folder and skips what exists."""
     t0 = time.time()
     output_folder = output_folder or "deep_cartograph"
     if not restart:
         output_folder = get_unique_path(output_folder)
     os.makedirs(output_folder, exist_ok=True)
+    trajectory_names = None
+    if trajectory_data and colvars_paths:
+        raise ValueError("give either colvars_paths or trajectory_data, not both: the computed features would replace the given ones")
+    if trajectory_data:
+        if not topology_data:
+            raise ValueError("trajectory_data needs topology_data (a PDB file)")
+        topology_data = [topology_data] if isinstance(topology_data, str) else list(topology_data)
+        sup_trajectory_data = [sup_trajectory_data] if isinstance(sup_trajectory_data, str) else sup_trajectory_data
+        cf = configuration.get("compute_features") or {}
+        colvars_paths = compute_features(configuration=cf, trajectory_data=trajectory_data, topology_data=topology_data,
+                                         output_folder=os.path.join(output_folder, "compute_features"))
+        trajectory_names = [os.path.basename(os.path.dirname(p)) for p in colvars_paths]
+        if sup_trajectory_data:
+            sup_colvars_paths = compute_features(configuration=cf, trajectory_data=sup_trajectory_data, topology_data=topology_data[:1],
+                                                 output_folder=os.path.join(output_folder, "compute_features_sup"))
+    elif sup_trajectory_data:
+        raise ValueError("sup_trajectory_data needs trajectory_data: supplementary features must be the training features")
     if "filter_features" in configuration and not features_list:
         features_path = filter_features(configuration=configuration["filter_features"] or {}, colvars_paths=colvars_paths,
                                         output_folder=os.path.join(output_folder, "filter_features"))
         features_list = read_features_list(features_path)
     tc_out = os.path.join(output_folder, "train_colvars")
     cv_paths = train_colvars(configuration=configuration.get("train_colvars", {}), train_colvars_paths=colvars_paths,
-                             features_list=features_list, dimension=dimension, cvs=cvs, output_folder=tc_out)
+                             trajectory_names=trajectory_names, features_list=features_list, dimension=dimension, cvs=cvs,
+                             output_folder=tc_out)
     sup_paths: Dict[str, List[str]] = {}
     if sup_colvars_paths:
         models = [os.path.join(tc_out, cv, "model.zip") for cv in cv_paths]
+        sup_names = [os.path.basename(os.path.dirname(p)) for p in sup_colvars_paths] if sup_trajectory_data else None
         sup_paths = traj_projection(configuration=configuration.get("traj_projection", {}), colvars_paths=sup_colvars_paths,
-                                    model_paths=models, output_folder=os.path.join(output_folder, "traj_projection"))
+                                    trajectory_names=sup_names, model_paths=models,
+                                    output_folder=os.path.join(output_folder, "traj_projection"))
     clusters = {}
     for cv, paths in cv_paths.items():
         clusters[cv] = traj_cluster(configuration=configuration.get("traj_cluster", {}), cv_traj_paths=paths,
@@ -59,7 +84,10 @@ def deep_cartograph(configuration: Dict, colvars_paths: List[str], sup_colvars_p
 def main(argv=None):
     p = argparse.ArgumentParser("deep_carto (MI355X CV-fit path)")
     p.add_argument("-conf", "-configuration", dest="configuration_path", required=True, help="YAML configuration")
-    p.add_argument("-colvars", dest="colvars", nargs="+", required=True, help="training feature matrices (COLVAR text or .npy)")
+    p.add_argument("-colvars", dest="colvars", nargs="+", default=None, help="training feature matrices (COLVAR text or .npy)")
+    p.add_argument("-traj", "-traj_data", dest="traj", nargs="+", default=None, help="training trajectories (.dcd / .npy); replaces -colvars")
+    p.add_argument("-top", "-top_data", dest="top", nargs="+", default=None, help="topology (.pdb): one for all -traj files, or one per -traj file in the same order")
+    p.add_argument("-sup_traj", "-sup_traj_data", dest="sup_traj", nargs="*", default=None, help="supplementary trajectories to project; they are read with the first -top file")
     p.add_argument("-sup_colvars", dest="sup_colvars", nargs="*", default=None, help="supplementary feature matrices to project")
     p.add_argument("-features", dest="features_path", default=None, help="file with the feature names to use (one per line)")
     p.add_argument("-dim", "-dimension", dest="dimension", type=int, default=None)
@@ -68,9 +96,14 @@ def main(argv=None):
     p.add_argument("-out", "-output", dest="output_folder", default=None)
     p.add_argument("-v", "-verbose", dest="verbose", action="store_true")
     a = p.parse_args(argv)
+    if not a.traj and not a.colvars:
+        p.error("one of -colvars or -traj is required")
+    if a.traj and not a.top:
+        p.error("-traj needs -top")
     logging.basicConfig(level=logging.DEBUG if a.verbose else logging.INFO, format="%(asctime)s %(name)s %(levelname)s %(message)s")
     cfg = read_configuration(a.configuration_path)
-    deep_cartograph(cfg, a.colvars, a.sup_colvars, read_features_list(a.features_path), a.dimension, a.cvs, a.restart, a.output_folder)
+    deep_cartograph(cfg, a.colvars or [], a.sup_colvars, read_features_list(a.features_path), a.dimension, a.cvs, a.restart, a.output_folder,
+                    trajectory_data=a.traj, topology_data=a.top, sup_trajectory_data=a.sup_traj)
 
 
 if __name__ == "__main__":

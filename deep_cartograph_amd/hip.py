@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import DcvError, check
+from ._lib import FEAT_DISTANCE, FEAT_TORSION, FEAT_TORSION_SINCOS, DcvError, check
 
 
 def _require_gpu(*tensors):
@@ -102,6 +102,60 @@ def dip_sorted(Xs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tens
     check(lib.dcv_dip_sorted(_ptr(Xs), n, C, Xs.stride(0), _ptr(dip), _ptr(lo), _ptr(hi), _ptr(ws), ws.numel(), _stream()),
           "dcv_dip_sorted")
     return dip, lo, hi
+
+
+# ------------------------------------------------------------------------------- featurisation
+_FEAT_COLUMNS = {FEAT_DISTANCE: 1, FEAT_TORSION_SINCOS: 2, FEAT_TORSION: 1}
+
+
+def featurize(xyz: torch.Tensor, defs, n_atoms: int, strides=None, unit: float = 0.1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[n, F] float32 distances / torsions of every frame (dcv_featurize).
+
+    ``xyz``: float32 coordinates on the device.  With ``strides=None`` a (n, A, 3) tensor, read through its own
+    strides.  Otherwise a 1-D buffer and ``strides = (n_frames, offset, frame_stride, atom_stride, comp_stride)`` in
+    elements -- what ``trajectory.Trajectory.layout()`` returns: coordinate c of atom a of frame f is
+    ``xyz[offset + f*frame_stride + a*atom_stride + c*comp_stride]``.
+    ``defs``: (n_defs, 6) int32 records [kind, a0, a1, a2, a3, out_column] (FEAT_*), on the host.
+    ``out``: optional row-major float32 [n, >= F] tensor; only the columns the records name are written."""
+    _require_gpu(xyz, out)
+    if xyz.dtype != torch.float32:
+        raise DcvError(f"featurize: coordinates must be float32, got {xyz.dtype}")
+    defs = np.ascontiguousarray(np.asarray(defs), dtype=np.int32)
+    if defs.ndim != 2 or defs.shape[1] != 6 or defs.shape[0] == 0:
+        raise DcvError(f"featurize: defs must be a non-empty (n_defs, 6) int32 array, got shape {defs.shape}")
+    n_atoms = int(n_atoms)
+    if strides is None:
+        if xyz.dim() != 3 or xyz.shape[1] != n_atoms or xyz.shape[2] != 3:
+            raise DcvError(f"featurize: expected a (n, {n_atoms}, 3) tensor, got {tuple(xyz.shape)}")
+        n, offset = xyz.shape[0], 0
+        fs, as_, cs = (int(s) for s in xyz.stride())
+        base = xyz.data_ptr()
+    else:
+        n, offset, fs, as_, cs = (int(v) for v in strides)
+        if xyz.dim() != 1 or not xyz.is_contiguous():
+            raise DcvError("featurize: with explicit strides the coordinates must be a contiguous 1-D buffer")
+        last = offset + max(n - 1, 0) * fs + (n_atoms - 1) * as_ + 2 * cs
+        if n < 0 or offset < 0 or min(fs, as_, cs) < 0 or (n > 0 and last >= xyz.numel()):
+            raise DcvError(f"featurize: layout {tuple(strides)} with {n_atoms} atoms reaches element {last} of a buffer of {xyz.numel()}")
+        base = xyz.data_ptr() + 4 * offset
+    F = max(int(r[5]) + _FEAT_COLUMNS.get(int(r[0]), 1) for r in defs)
+    if out is None:
+        out = torch.empty(n, max(F, 1), dtype=torch.float32, device=xyz.device)
+    else:
+        _check_matrix(out)
+        if out.shape[0] != n:
+            raise DcvError(f"featurize: out has {out.shape[0]} rows for {n} frames")
+        # the library checks columns against the row stride; a view may be narrower than that
+        if F > out.shape[1] or int(defs[:, 5].min()) < 0:
+            raise DcvError(f"featurize: the records write columns [{int(defs[:, 5].min())}, {F}), out has {out.shape[1]}")
+    if n == 0:
+        return out   # an empty tensor has no data pointer to hand to the library
+    lib = _lib.load()
+    ws = _ws(lib.dcv_featurize_workspace(n, n_atoms, defs.shape[0]), xyz.device)
+    ldo = max(out.stride(0), out.shape[1])   # the stride of a one-row tensor is arbitrary
+    check(lib.dcv_featurize(base, n, fs, as_, cs, n_atoms, defs.ctypes.data, defs.shape[0], float(unit), _ptr(out), ldo,
+                            _ptr(ws), ws.numel(), _stream()), "dcv_featurize")
+    return out
 
 
 def normalize(X: torch.Tensor, mean: torch.Tensor, rng: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -4,7 +4,7 @@ traj_cluster,traj_projection}.py.  tests/test_host_cpu.py checks model_dump() of
 reference's own dump (tests/golden/schema_defaults.json)."""
 from __future__ import annotations
 
-from typing import List, Literal, Optional, Union
+from typing import Dict, List, Literal, Optional, Union
 
 from pydantic import BaseModel, ConfigDict
 
@@ -202,3 +202,63 @@ class SamplingSettings(BaseModel):
 class FilterFeaturesSchema(BaseModel):
     filter_settings: FilterSettings = FilterSettings()
     sampling_settings: SamplingSettings = SamplingSettings()
+
+
+# ---------------------------------------------------------------- compute_features (yaml_schemas/compute_features.py)
+class CoordinateGroup(BaseModel):
+    selection: str = "not name H*"
+    stride: int = 1
+
+
+class DistanceGroup(BaseModel):
+    first_selection: str = "not name H*"
+    second_selection: str = "not name H*"
+    # keep every first_stride-th / second_stride-th atom of the selections
+    first_stride: int = 1
+    second_stride: int = 5
+    # skip pairs of atoms in the same or in neighbouring residues
+    skip_neigh_residues: bool = False
+    # skip pairs of bonded atoms
+    skip_bonded_atoms: bool = True
+
+
+class DihedralGroup(BaseModel):
+    selection: str = "not name H*"
+    # sin and cos of the angle instead of the angle
+    periodic_encoding: bool = True
+    # only "virtual" is computed here; the other two are refused by trajectory.feature_definitions
+    search_mode: Literal["virtual", "protein_backbone", "real"] = "real"
+
+
+class DistanceToCenterGroup(BaseModel):
+    selection: str = "not name H*"
+    center_selection: str = "not name H*"
+
+
+class Features(BaseModel):
+    coordinate_groups: Dict[str, CoordinateGroup] = {}
+    distance_groups: Dict[str, DistanceGroup] = {}
+    dihedral_groups: Dict[str, DihedralGroup] = {}
+    distance_to_center_groups: Dict[str, DistanceToCenterGroup] = {}
+
+
+class PlumedSettings(BaseModel):
+    # accepted and ignored: there is no PLUMED subprocess to time out
+    timeout: int = 172800
+    # keep one frame in every traj_stride
+    traj_stride: int = 1
+    features: Features = Features()
+
+
+class PlumedEnvironment(BaseModel):
+    # accepted and ignored: the features are computed by libdcv.so
+    bin_path: str = "plumed"
+    kernel_path: Union[str, None] = None
+    env_commands: List[str] = []
+
+
+class ComputeFeaturesSchema(BaseModel):
+    plumed_settings: PlumedSettings = PlumedSettings()
+    plumed_environment: PlumedEnvironment = PlumedEnvironment()
+    # this project's extension: "npy" writes the binary fast path colvars.npy + colvars.names.txt, "dat" a COLVAR text file
+    colvars_format: Literal["npy", "dat"] = "npy"

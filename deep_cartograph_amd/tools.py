@@ -1,5 +1,5 @@
 """The tools of the CV-fit path with the reference's API (argument names, output tree,
-CSV formats): filter_features (tools/filter_features/filter_features.py:22-31), train_colvars (tools/train_colvars/train_colvars.py:20-36), traj_projection
+CSV formats): compute_features (tools/compute_features/compute_features.py:25-227), filter_features (tools/filter_features/filter_features.py:22-31), train_colvars (tools/train_colvars/train_colvars.py:20-36), traj_projection
 (tools/traj_projection/traj_projection.py:19-27), traj_cluster (tools/traj_cluster/traj_cluster.py:
 18-28).  Figures, FES estimation and PDB/XTC extraction (matplotlib / MDAnalysis) are outside the
 accelerated path and are not produced."""
@@ -18,7 +18,7 @@ import pandas as pd
 from . import statistics
 from .common import merge_configurations, save_list, validate_configuration
 from .cv_calculator import CVCalculator, calculator_class
-from .schemas import FilterFeaturesSchema, TrainColvarsSchema, TrajClusterSchema, TrajProjectionSchema
+from .schemas import ComputeFeaturesSchema, FilterFeaturesSchema, TrainColvarsSchema, TrajClusterSchema, TrajProjectionSchema
 
 logger = logging.getLogger(__name__)
 
@@ -27,6 +27,100 @@ def _as_list(x):
     if x is None:
         return None
     return [x] if isinstance(x, str) else list(x)
+
+
+ANGSTROM_TO_NM = 0.1   # PLUMED's length unit
+DEFAULT_CHUNK_BYTES = 4 << 30   # default upper limit of a compute_features chunk (device bytes; the same again on the host)
+
+
+def compute_features(configuration: Dict, trajectory_data: Union[str, List[str]], topology_data: Union[str, List[str]],
+                     reference_topology: Optional[str] = None, traj_stride: Optional[int] = None,
+                     output_folder: str = "compute_features", memory_budget: Optional[int] = None) -> List[str]:
+    """Distances and virtual dihedrals of every trajectory, computed on the device from the coordinates (hip.featurize)
+    instead of by a `plumed driver` subprocess.  Writes <out>/<trajectory stem>/colvars.npy + colvars.names.txt (the
+    binary fast path of colvars.py), or colvars.dat with `colvars_format: dat`, and returns those paths; a trajectory
+    whose output exists is skipped.  One topology serves all trajectories, or one per trajectory; all must give the
+    feature names of `reference_topology` (default: the first).  `traj_stride` overrides plumed_settings.traj_stride.
+    Frames are streamed in chunks of at most `memory_budget` bytes of device memory (default: a quarter of what is free,
+    at most 4 GiB; a chunk's frame records also exist once as a host copy while they are uploaded) and the rows written
+    into a memory-mapped .npy, so neither side ever holds a whole matrix twice.  No CPU fallback."""
+    import torch
+
+    from . import hip, trajectory
+    from ._lib import DcvError
+    from .colvars import write_colvars
+
+    t0 = time.time()
+    trajectories = _as_list(trajectory_data) or []
+    topologies = _as_list(topology_data) or []
+    if not trajectories:
+        raise ValueError("compute_features: no trajectories given")
+    if len(topologies) == 1:
+        topologies = topologies * len(trajectories)
+    if len(trajectories) != len(topologies):
+        raise ValueError(f"Number of trajectories ({len(trajectories)}) and topologies ({len(topologies)}) do not match.")
+    for path in trajectories + topologies + ([reference_topology] if reference_topology else []):
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"File not found: {path}")
+    os.makedirs(output_folder, exist_ok=True)
+    configuration = validate_configuration(configuration or {}, ComputeFeaturesSchema, output_folder)
+    binary = configuration["colvars_format"] == "npy"
+    colvars_paths = [os.path.join(output_folder, Path(t).stem, "colvars.npy" if binary else "colvars.dat") for t in trajectories]
+    if all(os.path.exists(p) for p in colvars_paths):
+        logger.info(f"Colvars files already exist in {output_folder}. Skipping feature computation.")
+        return colvars_paths
+    if not torch.cuda.is_available():
+        raise DcvError("compute_features needs an MI355X (cuda) device: the features are computed by libdcv.so, there is no CPU fallback")
+    stride = int(traj_stride or configuration["plumed_settings"]["traj_stride"])
+    if stride < 1:
+        raise ValueError(f"traj_stride must be at least 1, got {stride}")
+    features_configuration = configuration["plumed_settings"]["features"]
+    ref_names, _ = trajectory.feature_definitions(features_configuration, trajectory.read_topology(reference_topology or topologies[0]))
+    if memory_budget is None:
+        # every chunk also exists once as a pageable host copy on its way up, so the default is capped for the host's sake
+        memory_budget = min(torch.cuda.mem_get_info()[0] // 4, DEFAULT_CHUNK_BYTES)
+    for traj_path, top_path, out_path in zip(trajectories, topologies, colvars_paths):
+        if os.path.exists(out_path):
+            logger.info(f"Skipping {Path(traj_path).stem}. Colvars file already exists.")
+            continue
+        top = trajectory.read_topology(top_path)
+        names, defs = trajectory.feature_definitions(features_configuration, top)
+        if names != ref_names:
+            raise ValueError(f"The features of {top_path} differ from those of the reference topology; translating features "
+                             "between topologies is out of scope")
+        traj = trajectory.open_trajectory(traj_path, top.n_atoms)
+        n = traj.layout(0, None, stride)[0]
+        if n == 0:
+            raise ValueError(f"{traj_path}: no frames")
+        os.makedirs(os.path.dirname(out_path), exist_ok=True)
+        # rows land in a memory-mapped .npy under a temporary name: an interrupted run leaves nothing a restart would take for done
+        tmp_path = os.path.join(os.path.dirname(out_path), "colvars.partial.npy")
+        rows = np.lib.format.open_memmap(tmp_path, mode="w+", dtype=np.float32, shape=(n, len(names)))
+        per_frame = 4 * (stride * traj.frame_stride + len(names))
+        chunk = int(max(1, min(n, memory_budget // per_frame)))
+        logger.info(f"Computing {len(names)} features of {n} frames of {Path(traj_path).name} in chunks of {chunk} frames")
+        for lo in range(0, n, chunk):
+            hi = min(n, lo + chunk)
+            span, layout = traj.span(lo * stride, (hi - 1) * stride + 1, stride)
+            buf = torch.from_numpy(np.array(span, dtype=np.float32)).cuda()
+            block = hip.featurize(buf, defs, top.n_atoms, strides=layout, unit=ANGSTROM_TO_NM).cpu().numpy()
+            if np.isnan(block).any():
+                raise ValueError(f"NaNs in the features of frames {lo * stride}..{(hi - 1) * stride} of {traj_path}: check the coordinates")
+            rows[lo:hi] = block
+            del buf
+        rows.flush()
+        if binary:
+            del rows
+            with open(out_path[:-4] + ".names.txt", "w") as f:
+                f.write("\n".join(names) + "\n")
+            os.replace(tmp_path, out_path)
+        else:
+            write_colvars(out_path + ".partial", rows, names)
+            del rows
+            os.replace(out_path + ".partial", out_path)
+            os.remove(tmp_path)
+    logger.info("Elapsed time (Compute features): %s", time.strftime("%H h %M min %S s", time.gmtime(time.time() - t0)))
+    return colvars_paths
 
 
 def filter_features(configuration: Dict, colvars_paths: Union[str, List[str]], waypoint_colvars_paths: Optional[List[str]] = None,

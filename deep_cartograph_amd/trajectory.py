@@ -1,0 +1,372 @@
+"""Host side of compute_features: topology, atom selections, trajectory files and the feature definitions the
+device kernel (hip.featurize) evaluates.  NumPy only -- no MDAnalysis, no PLUMED.
+
+What the reference does with MDAnalysis and a `plumed driver` subprocess (tools/compute_features/compute_features.py,
+modules/md/md.py) is restated for the feature kinds its own test data pins:
+
+* ``read_topology``        PDB ATOM / HETATM / CONECT records up to the first ENDMDL;
+* ``select_atoms``         a documented subset of the MDAnalysis selection grammar (below);
+* ``open_trajectory``      little-endian CHARMM / NAMD ``.dcd`` (memory-mapped, never transposed) and ``.npy``;
+* ``feature_definitions``  names and kernel records of the distance and virtual-dihedral groups, with the
+                           reference's labelling rules and order (md.py:26-129, 226-273, 479-545, 580-717).
+
+Selection grammar: ``all``; ``name``, ``resname``, ``segid`` / ``chainID`` followed by one or more values, each
+optionally ending in the wildcard ``*``; ``resid`` followed by values ``7``, ``3:9`` or ``3-9`` (inclusive);
+``not``, ``and``, ``or`` (binding in that order) and parentheses.  Anything else -- ``protein``, ``backbone``,
+``around``, ``index``, ``?`` wildcards ... -- raises ValueError naming the token.  A selection is returned in
+topology order, as MDAnalysis returns it.  ``segid`` is the PDB segment identifier (columns 73-76) and falls back to
+the chain identifier where that field is blank, as in MDAnalysis.
+
+Out of scope (ValueError naming the option): ``coordinate_groups`` (need a per-frame optimal fit),
+``distance_to_center_groups``, and the ``protein_backbone`` / ``real`` dihedral search modes.  Periodic boundaries
+are not applied: the reference's distances are NOPBC and its torsions follow a WHOLEMOLECULES step, so a trajectory
+whose molecule is split across the box must be made whole first.  XTC (compressed) is not read."""
+from __future__ import annotations
+
+import os
+import re
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Set, Tuple
+
+import numpy as np
+
+from ._lib import FEAT_DISTANCE, FEAT_TORSION, FEAT_TORSION_SINCOS
+
+COVALENT_BOND_THRESHOLD = 2.0   # Angstrom: the reference's guess for a bond when the topology has no CONECT records
+
+
+# ------------------------------------------------------------------------------------------------ topology
+@dataclass
+class Topology:
+    names: List[str]
+    resnames: List[str]
+    chains: List[str]
+    segids: List[str]
+    resids: np.ndarray            # int64 [A]
+    positions: np.ndarray         # float32 [A, 3], Angstrom
+    bonds: Optional[Set[Tuple[int, int]]]   # pairs (i < j) of 0-based atom indices from CONECT; None without CONECT records
+
+    @property
+    def n_atoms(self) -> int:
+        return len(self.names)
+
+
+def read_topology(path: str) -> Topology:
+    """Atoms (and CONECT bonds, if any) of the first model of a PDB file."""
+    names, resnames, chains, segids, resids, pos, serials = [], [], [], [], [], [], []
+    conect: List[Tuple[int, int]] = []
+    in_first_model = True
+    with open(path) as f:
+        for line in f:
+            rec = line[:6].strip()
+            if rec == "ENDMDL":
+                in_first_model = False
+            elif rec in ("ATOM", "HETATM") and in_first_model:
+                try:
+                    serials.append(int(line[6:11]))
+                except ValueError:
+                    serials.append(len(serials) + 1)   # overflowed serial columns
+                names.append(line[12:16].strip())
+                resnames.append(line[17:21].strip())
+                chains.append(line[21:22].strip())
+                segids.append(line[72:76].strip() or chains[-1])
+                resids.append(int(line[22:26]))
+                pos.append((float(line[30:38]), float(line[38:46]), float(line[46:54])))
+            elif rec == "CONECT":
+                fields = [line[i:i + 5] for i in range(6, min(len(line.rstrip("\n")), 31), 5)]
+                nums = [int(x) for x in fields if x.strip()]
+                conect.extend((nums[0], other) for other in nums[1:])   # a record without partners (or empty) yields no pair
+    if not names:
+        raise ValueError(f"{path}: no ATOM or HETATM records")
+    bonds = None
+    if conect:
+        index = {s: i for i, s in enumerate(serials)}
+        bonds = set()
+        for a, b in conect:
+            if a in index and b in index and index[a] != index[b]:
+                i, j = index[a], index[b]
+                bonds.add((min(i, j), max(i, j)))
+    return Topology(names, resnames, chains, segids, np.asarray(resids, dtype=np.int64),
+                    np.asarray(pos, dtype=np.float32).reshape(-1, 3), bonds)
+
+
+# ------------------------------------------------------------------------------------------------ selections
+_RESERVED = {"and", "or", "not", "(", ")"}
+_STRING_KEYWORDS = {"name": "names", "resname": "resnames", "segid": "segids", "chainID": "chains", "chainid": "chains"}
+_RESID_VALUE = re.compile(r"^(-?\d+)(?:[:-](-?\d+))?$")
+
+
+def _match_strings(values: List[str], patterns: List[str]) -> np.ndarray:
+    mask = np.zeros(len(values), dtype=bool)
+    for p in patterns:
+        stem = p[:-1] if p.endswith("*") else p
+        if not stem and not p.endswith("*") or any(ch in stem for ch in "*?[]"):
+            raise ValueError(f"unsupported selection token '{p}': only a trailing '*' wildcard is understood")
+        if p.endswith("*"):
+            mask |= np.fromiter((v.startswith(stem) for v in values), dtype=bool, count=len(values))
+        else:
+            mask |= np.fromiter((v == stem for v in values), dtype=bool, count=len(values))
+    return mask
+
+
+class _Parser:
+    def __init__(self, top: Topology, selection: str):
+        self.top = top
+        self.tokens = selection.replace("(", " ( ").replace(")", " ) ").split()
+        self.pos = 0
+        if not self.tokens:
+            raise ValueError("empty selection")
+
+    def peek(self) -> Optional[str]:
+        return self.tokens[self.pos] if self.pos < len(self.tokens) else None
+
+    def take(self) -> str:
+        tok = self.tokens[self.pos]
+        self.pos += 1
+        return tok
+
+    def values(self, keyword: str) -> List[str]:
+        vals = []
+        while self.peek() is not None and self.peek() not in _RESERVED:
+            vals.append(self.take())
+        if not vals:
+            raise ValueError(f"selection keyword '{keyword}' needs at least one value")
+        return vals
+
+    def parse(self) -> np.ndarray:
+        mask = self.or_expr()
+        if self.peek() is not None:
+            raise ValueError(f"unsupported selection token '{self.peek()}'")
+        return mask
+
+    def or_expr(self) -> np.ndarray:
+        mask = self.and_expr()
+        while self.peek() == "or":
+            self.take()
+            mask = mask | self.and_expr()
+        return mask
+
+    def and_expr(self) -> np.ndarray:
+        mask = self.not_expr()
+        while self.peek() == "and":
+            self.take()
+            mask = mask & self.not_expr()
+        return mask
+
+    def not_expr(self) -> np.ndarray:
+        if self.peek() == "not":
+            self.take()
+            return ~self.not_expr()
+        return self.primary()
+
+    def primary(self) -> np.ndarray:
+        if self.peek() is None:
+            raise ValueError("selection ends where a term was expected")
+        tok = self.take()
+        if tok == "(":
+            mask = self.or_expr()
+            if self.peek() != ")":
+                raise ValueError("unbalanced parenthesis in selection")
+            self.take()
+            return mask
+        if tok == "all":
+            return np.ones(self.top.n_atoms, dtype=bool)
+        if tok in _STRING_KEYWORDS:
+            return _match_strings(getattr(self.top, _STRING_KEYWORDS[tok]), self.values(tok))
+        if tok == "resid":
+            mask = np.zeros(self.top.n_atoms, dtype=bool)
+            for v in self.values(tok):
+                m = _RESID_VALUE.match(v)
+                if not m:
+                    raise ValueError(f"unsupported selection token '{v}' after resid")
+                lo = int(m.group(1))
+                hi = int(m.group(2)) if m.group(2) is not None else lo
+                mask |= (self.top.resids >= lo) & (self.top.resids <= hi)
+            return mask
+        raise ValueError(f"unsupported selection token '{tok}'")
+
+
+def select_atoms(top: Topology, selection: str) -> np.ndarray:
+    """0-based indices (ascending) of the atoms a selection string names."""
+    return np.flatnonzero(_Parser(top, selection).parse())
+
+
+# ------------------------------------------------------------------------------------------------ trajectories
+@dataclass
+class Trajectory:
+    """A trajectory as one flat float32 buffer (memory-mapped) plus the addressing the kernel needs: coordinate c of
+    atom a of frame f is ``data[offset + f*frame_stride + a*atom_stride + c*comp_stride]`` (Angstrom)."""
+    data: np.ndarray
+    n_frames: int
+    n_atoms: int
+    offset: int
+    frame_stride: int
+    atom_stride: int
+    comp_stride: int
+
+    def layout(self, start: int = 0, stop: Optional[int] = None, step: int = 1) -> Tuple[int, int, int, int, int]:
+        """(n, offset, frame_stride, atom_stride, comp_stride) of frames [start:stop:step] -- the `strides` argument of
+        hip.featurize for the whole buffer."""
+        stop = self.n_frames if stop is None else min(stop, self.n_frames)
+        n = max(0, (stop - start + step - 1) // step)
+        return n, self.offset + start * self.frame_stride, step * self.frame_stride, self.atom_stride, self.comp_stride
+
+    def span(self, start: int, stop: int, step: int = 1) -> Tuple[np.ndarray, Tuple[int, int, int, int, int]]:
+        """The smallest slice of the buffer that holds frames [start:stop:step], and their layout inside that slice: what
+        one chunk uploads.  16-byte alignment of the file is kept (the slice starts on a multiple of 4 elements)."""
+        n, off, fs, as_, cs = self.layout(start, stop, step)
+        if n == 0:
+            return self.data[:0], (0, 0, fs, as_, cs)
+        first = off // 4 * 4
+        last = off + (n - 1) * fs + (self.n_atoms - 1) * as_ + 2 * cs
+        return self.data[first:last + 1], (n, off - first, fs, as_, cs)
+
+    def frames(self, start: int = 0, stop: Optional[int] = None, step: int = 1) -> np.ndarray:
+        """(n, A, 3) float32 copy of frames [start:stop:step] (for host-side checks; the device path never needs it)."""
+        n, off, fs, as_, cs = self.layout(start, stop, step)
+        idx = (off + fs * np.arange(n, dtype=np.int64)[:, None, None] + as_ * np.arange(self.n_atoms, dtype=np.int64)[None, :, None]
+               + cs * np.arange(3, dtype=np.int64)[None, None, :])
+        return np.asarray(self.data[idx], dtype=np.float32)
+
+
+def _open_dcd(path: str, n_atoms: Optional[int]) -> Trajectory:
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        head = f.read(92)
+        if len(head) < 92 or head[4:8] != b"CORD":
+            raise ValueError(f"{path}: not a DCD file (no CORD header)")
+        if np.frombuffer(head, dtype="<i4", count=1)[0] != 84:
+            if np.frombuffer(head, dtype=">i4", count=1)[0] == 84:
+                raise ValueError(f"{path}: big-endian DCD files are not supported (the file is mapped as little-endian float32)")
+            raise ValueError(f"{path}: not a DCD file (header record of {np.frombuffer(head, dtype='<i4', count=1)[0]} bytes)")
+        icntrl = np.frombuffer(head, dtype="<i4", count=20, offset=8)
+        nset, fixed, charmm = int(icntrl[0]), int(icntrl[8]), int(icntrl[19]) != 0
+        has_cell = charmm and int(icntrl[10]) != 0
+        if fixed != 0:
+            raise ValueError(f"{path}: DCD with {fixed} fixed atoms: frames after the first hold only the free atoms, not supported")
+        if charmm and int(icntrl[11]) != 0:
+            raise ValueError(f"{path}: DCD with the 4th-dimension flag set is not supported")
+        rec = np.frombuffer(f.read(8), dtype="<i4", count=2)
+        title_bytes, ntitle = int(rec[0]), int(rec[1])
+        if title_bytes < 4 or (title_bytes - 4) % 80 != 0 or ntitle < 0:
+            raise ValueError(f"{path}: malformed DCD title block ({title_bytes} bytes, {ntitle} lines)")
+        f.seek(title_bytes - 4 + 4, os.SEEK_CUR)   # the title lines and the closing marker
+        rec = np.frombuffer(f.read(12), dtype="<i4", count=3)
+        if rec.size != 3 or rec[0] != 4 or rec[2] != 4:
+            raise ValueError(f"{path}: malformed DCD atom-count block")
+        natom = int(rec[1])
+        header_bytes = f.tell()
+    if n_atoms is not None and natom != n_atoms:
+        raise ValueError(f"{path}: {natom} atoms in the trajectory, {n_atoms} in the topology")
+    cell_words = 14 if has_cell else 0          # marker + 6 float64 + marker
+    frame_words = cell_words + 3 * (natom + 2)
+    if header_bytes + nset * frame_words * 4 != size:
+        raise ValueError(f"{path}: {size} bytes do not match the header's {nset} frames of {natom} atoms "
+                         f"({header_bytes} + {nset} x {frame_words * 4} bytes): truncated or unfinished file")
+    data = np.memmap(path, dtype="<f4", mode="r") if size else np.zeros(0, dtype=np.float32)
+    return Trajectory(data, nset, natom, header_bytes // 4 + cell_words + 1, frame_words, 1, natom + 2)
+
+
+def open_trajectory(path: str, n_atoms: Optional[int] = None) -> Trajectory:
+    """Memory-map a trajectory: ``.dcd`` (little-endian CHARMM / NAMD / X-PLOR, with or without the unit-cell block) or
+    ``.npy`` holding (n, A, 3) float32 in Angstrom.  ``n_atoms`` (the topology's) is checked when given."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".dcd":
+        return _open_dcd(path, n_atoms)
+    if ext == ".npy":
+        arr = np.load(path, mmap_mode="r")
+        if arr.ndim != 3 or arr.shape[2] != 3 or arr.dtype != np.float32:
+            raise ValueError(f"{path}: expected a (frames, atoms, 3) float32 array, got {arr.shape} {arr.dtype}")
+        if n_atoms is not None and arr.shape[1] != n_atoms:
+            raise ValueError(f"{path}: {arr.shape[1]} atoms in the trajectory, {n_atoms} in the topology")
+        return Trajectory(arr.reshape(-1), arr.shape[0], arr.shape[1], 0, 3 * arr.shape[1], 3, 1)
+    raise ValueError(f"{path}: unsupported trajectory format '{ext}' (supported: .dcd, .npy; XTC is compressed and out of scope)")
+
+
+# ------------------------------------------------------------------------------------------------ feature definitions
+def _entity(top: Topology, i: int) -> str:
+    return f"@{top.names[i]}_{int(top.resids[i])}"
+
+
+def _heavy(top: Topology, atoms: np.ndarray) -> np.ndarray:
+    return np.asarray([i for i in atoms if not top.names[i].startswith("H")], dtype=np.int64)   # "not name H*"
+
+
+def _distance_group(top: Topology, group: Dict) -> List[Tuple[str, int, int]]:
+    """(label, atom, atom) of one distance group, md.py:26-129."""
+    sel1, sel2 = group.get("first_selection", "all"), group.get("second_selection", "all")
+    first = _heavy(top, select_atoms(top, sel1))[::int(group.get("first_stride", 1))]
+    second = _heavy(top, select_atoms(top, sel2))[::int(group.get("second_stride", 1))]
+    if len(first) == 0:
+        raise ValueError(f"First selection: '{sel1}' is empty, please review the selection string.")
+    if len(second) == 0:
+        raise ValueError(f"Second selection: '{sel2}' is empty, please review the selection string.")
+    skip_neighbors, skip_bonded = bool(group.get("skip_neigh_residues", False)), bool(group.get("skip_bonded_atoms", False))
+    pos = top.positions.astype(np.float64)
+    seen: Set[str] = set()
+    found = []
+    for i in first:
+        ei = _entity(top, i)
+        for j in second:
+            if i == j:
+                continue
+            ej = _entity(top, j)
+            label = f"{ei}-{ej}"
+            if label in seen or f"{ej}-{ei}" in seen:
+                continue
+            if skip_bonded:
+                if top.bonds is not None:
+                    if (min(i, j), max(i, j)) in top.bonds:
+                        continue
+                elif float(np.sqrt(((pos[i] - pos[j]) ** 2).sum())) < COVALENT_BOND_THRESHOLD:
+                    continue
+            if skip_neighbors and abs(int(top.resids[i]) - int(top.resids[j])) <= 1:
+                continue
+            seen.add(label)
+            found.append((label, int(i), int(j)))
+    return found
+
+
+def _virtual_dihedrals(top: Topology, selection: str) -> List[Tuple[str, int, int, int, int]]:
+    """(label, four atoms) of the virtual dihedrals of a selection, md.py:226-273.  The reference counts the HEAVY atoms
+    of the selection but indexes the selection BEFORE the hydrogens were removed (md.py:265-268); with hydrogens in the
+    selection that yields fewer dihedrals than there are heavy-atom quadruples and quadruples that contain hydrogens.
+    Reproduced as it stands: feature names are the contract with models trained on the reference's output."""
+    atoms = select_atoms(top, selection)
+    n_heavy = len(_heavy(top, atoms))
+    if n_heavy == 0:
+        raise ValueError(f"Selection: '{selection}' is empty, please review the selection string.")
+    found = []
+    for i in range(3, n_heavy):
+        quad = [int(atoms[i - 3]), int(atoms[i - 2]), int(atoms[i - 1]), int(atoms[i])]
+        found.append(("-".join(_entity(top, a) for a in quad), *quad))
+    return found
+
+
+def feature_definitions(features_configuration: Dict, top: Topology) -> Tuple[List[str], np.ndarray]:
+    """(names, defs): the feature names in the reference's order (distance groups, then dihedral groups, each in
+    dictionary order; md.py:580-717) and the (n_defs, 6) int32 records [kind, a0, a1, a2, a3, out_column] of
+    hip.featurize.  The atoms of a record are the ones that produced its label."""
+    cfg = features_configuration or {}
+    if cfg.get("coordinate_groups"):
+        raise ValueError("coordinate_groups are not supported: coordinates need a per-frame optimal fit to a template")
+    if cfg.get("distance_to_center_groups"):
+        raise ValueError("distance_to_center_groups are not supported")
+    names: List[str] = []
+    defs: List[List[int]] = []
+    for group in (cfg.get("distance_groups") or {}).values():
+        for label, i, j in _distance_group(top, group or {}):
+            defs.append([FEAT_DISTANCE, i, j, 0, 0, len(names)])
+            names.append(f"dist-{label}")
+    for group in (cfg.get("dihedral_groups") or {}).values():
+        group = group or {}
+        mode = group.get("search_mode", "real")
+        if mode != "virtual":
+            raise ValueError(f"search_mode '{mode}' is not supported: only 'virtual' dihedrals are computed")
+        encode = bool(group.get("periodic_encoding", True))
+        for label, a, b, c, d in _virtual_dihedrals(top, group.get("selection", "all")):
+            defs.append([FEAT_TORSION_SINCOS if encode else FEAT_TORSION, a, b, c, d, len(names)])
+            names.extend([f"sin-{label}", f"cos-{label}"] if encode else [f"tor-{label}"])
+    if not names:
+        raise ValueError("No features found, please check the features section of the configuration file and the topology.")
+    return names, np.asarray(defs, dtype=np.int32).reshape(-1, 6)

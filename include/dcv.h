@@ -90,6 +90,37 @@ size_t dcv_dip_sorted_workspace(int64_t n, int32_t C);
 int dcv_dip_sorted(const float* Xs_d, int64_t n, int32_t C, int64_t ld, double* dip_d, int32_t* lo_d,
                    int32_t* hi_d, void* ws_d, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- featurisation (compute_features)
+ * Replaces the `plumed driver` subprocess of tools/compute_features/compute_features.py:200-221 and the COLVAR text it
+ * writes, for the DISTANCE (NOPBC) and TORSION actions: n_frames x n_atoms x 3 float32 coordinates in, n_frames rows of
+ * float32 features out.  Coordinate c of atom a in frame f is xyz_d[f*frame_stride + a*atom_stride + c*comp_stride]
+ * (strides in ELEMENTS, frame_stride >= 0, the other two >= 1): a dense (n, A, 3) array has strides (3A, 3, 1); the
+ * frame records of a DCD file viewed as float32 -- three planes X[A], Y[A], Z[A] between 4-byte record markers -- have
+ * atom_stride 1, comp_stride A + 2 and xyz_d on the first X value, which need not be 16-byte aligned.  A frame stride
+ * that is a multiple of the record length keeps every s-th frame without a copy.
+ * defs_h is a HOST array of n_defs records of six int32 [kind, a0, a1, a2, a3, out_column]:
+ *   DCV_FEAT_DISTANCE        out[col]     = |p1 - p0|                      (a2, a3 ignored)
+ *   DCV_FEAT_TORSION_SINCOS  out[col]     = sin, out[col + 1] = cos of the torsion a0-a1-a2-a3
+ *   DCV_FEAT_TORSION         out[col]     = the torsion in radians, (-pi, pi]
+ * Arithmetic in float64 on p = (double)x * unit (unit 0.1: Angstrom -> nm), no fused multiply-adds, one rounding to
+ * float32 on store.  Distance: sqrt of the three squares added in x, y, z order.  Torsion: b0 = p1-p0, b1 = p2-p1,
+ * b2 = p3-p2, n1 = b0 x b1, n2 = b1 x b2, x = n1.n2, y = ((n1 x n2).b1)/|b1| (0 when |b1| = 0); angle = atan2(y, x),
+ * sin = y/r, cos = x/r with r = hypot(x, y), and (0, 1) when r = 0 (collinear or coincident atoms).  Periodic
+ * boundaries are NOT applied.  Non-finite coordinates propagate to the output.
+ * Every record is validated before anything is launched: an atom index outside [0, n_atoms), an output column that
+ * does not fit ldo or an unknown kind is DCV_EINVAL; so is a set of used atoms of which one frame does not fit LDS
+ * (5461 atoms).  The records are copied into the workspace; one that is too small is DCV_ENOMEM, nothing launched.
+ * A workgroup owns 16 frames (fewer when 16 frames of the staged atoms exceed 48 KB of LDS).  Staged per frame: the
+ * index range [min, max] of the atoms the records name when the innermost stride is 1 and they fill at least half of
+ * it, otherwise exactly the named atoms.  Algorithmic traffic per frame: 12 bytes per staged atom + 4 per output column. */
+#define DCV_FEAT_DISTANCE 0
+#define DCV_FEAT_TORSION_SINCOS 1
+#define DCV_FEAT_TORSION 2
+size_t dcv_featurize_workspace(int64_t n_frames, int32_t n_atoms, int32_t n_defs);
+int dcv_featurize(const float* xyz_d, int64_t n_frames, int64_t frame_stride, int64_t atom_stride, int64_t comp_stride,
+                  int32_t n_atoms, const int32_t* defs_h, int32_t n_defs, double unit,
+                  float* out_d, int64_t ldo, void* ws_d, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- normalisation (a3)
  * Replaces LinearCalculator.normalize_data, cv_calculator.py:833-835
  * (data.sub_(mean).div_(range) in float32).  Y may alias X (in place, as the reference). */
