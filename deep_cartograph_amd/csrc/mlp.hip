@@ -14,6 +14,7 @@
 // This unit: lifecycle and accessors, the layer-by-layer forward and backward, the single-step entry points.  mlp_opt.hip:
 // optimisers and gradient reduction; mlp_heads.hip: loss heads; mlp_passes.hip: the passes built on the steps.
 #include "mlp_state.h"
+#include "reduce_quad.h"
 #include <new>
 #include <math.h>
 #include <utility>
@@ -472,6 +473,11 @@ extern "C" int dcv_mlp_layer_output(dcv_mlp* m, int32_t layer, int64_t rows, flo
 extern "C" int64_t dcv_mlp_dropout_step(const dcv_mlp* m) { return m ? m->drop_step : 0; }
 extern "C" int32_t dcv_mlp_last_path(const dcv_mlp* m) { return m ? m->last_path : -1; }
 extern "C" int32_t dcv_mlp_last_eval_group(const dcv_mlp* m) { return m ? m->last_eval_group : -1; }
+extern "C" int32_t dcv_mlp_last_ride(const dcv_mlp* m) { return m ? m->last_ride : -1; }
+extern "C" float* dcv_mlp_opt_state(dcv_mlp* m, int32_t which) {
+    if (!m) return nullptr;
+    return which == 0 ? m->adam_m : which == 1 ? m->adam_v : which == 2 ? m->opt_aux : nullptr;
+}
 
 extern "C" int dcv_mlp_dropout_mask(dcv_mlp* m, int32_t layer, int64_t step, int64_t rows, float* out_d, void* stream) {
     DCV_REQUIRE(m && out_d && layer >= 0 && layer < m->L && rows >= 1 && step >= 0, "dcv_mlp_dropout_mask: bad arguments");
@@ -788,6 +794,9 @@ struct Backward {
     float *dz_cur, *dz_nxt;
     int bblocks;
     ReduceArgs ra;
+    bool fuse_opt = false;   // one-GPU training step: the update rides in the reduction
+    bool ridden = false;     // ride_upper took everything but the weights of layer 0, with the update arguments `oa`
+    OptArgs oa{};
 };
 
 // Deep-TICA after a fused forward (snet_dt.hip): one backward launch from its blob, then the reduction (+ optimiser)
@@ -908,7 +917,22 @@ static int backward_layer(Backward& c, int l) {
     const LayerPlan& p = m->layers[l];
     const int64_t R = c.R;
     const int64_t kc = plan_wgrad(c, l);
-    if (l == 0) return wgrad_alone(c, l, make_operand(c.Xn, c.ld, p.in, c.rm), kc);
+    if (l == 0) {
+        const Operand X = make_operand(c.Xn, c.ld, p.in, c.rm);
+        if (c.fuse_opt) {
+            // the gradients that do not wait for this product reduce and update inside its launch (mlp_opt.hip: ride_upper); a
+            // stamped launch stays one stamped launch, its interval now includes the ride-along blocks
+            prof_mark(m, l, 1, 0, s);
+            const int rc = ride_upper(m, c.ra, make_operand(c.dz_cur, m->ld_dz, p.out), X, p.out, p.in, R, kc, slab_epi(p), &c.oa, s);
+            if (rc < 0) return rc;
+            if (rc == DCV_OK) {
+                prof_mark(m, l, 1, 1, s);
+                c.ridden = true;
+                return DCV_OK;
+            }
+        }
+        return wgrad_alone(c, l, X, kc);
+    }
     const LayerPlan& q = m->layers[l - 1];
     Operand A = make_operand(c.dz_cur, m->ld_dz, p.out);
     Operand B = make_operand(layer_out(m, l - 1), q.ldh, p.in);
@@ -967,10 +991,12 @@ int backward_impl(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t* idx_
     const bool head_in_bwd = tica && m->last_path == 2 && train && !m->head_done && m->snet_fwd_valid;   // the fused backward evaluates the head itself
     int rc = loss_record(m, global_batch, train != 0, head_in_bwd, s);
     if (rc || !train) return rc;
+    m->last_ride = 0;
     if (tica && m->last_path == 2) return backward_blob(m, batch, global_batch, head_in_bwd, fuse_opt, s);
     const int L = m->L;
     Backward c{m, Xn_d, ld, idx_d, batch_rows(m, idx_d, row0, batch), rows_of(m, idx_d, batch), batch, global_batch, s, m->dZ[0], m->dZ[1], 0, ReduceArgs{}};
     c.ra.L = L;
+    c.fuse_opt = fuse_opt;
     const bool fused_head = tica && head_fusable(m);
     rc = seed_gradient(c, fused_head);
     bool upper_done = false;
@@ -986,7 +1012,7 @@ int backward_impl(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t* idx_
         else rc = backward_layer(c, l);
     }
     if (rc) return rc;
-    return finish_grads(m, c.ra, fuse_opt, upper_done, s);
+    return finish_grads(m, c.ra, fuse_opt, upper_done, s, c.ridden ? &c.oa : nullptr);
 }
 
 // One-GPU autoencoder step as ONE fused launch (+ the gradient reduction with the optimiser update) when the network

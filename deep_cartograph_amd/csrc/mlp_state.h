@@ -62,6 +62,7 @@ struct dcv_mlp {   // created value-initialised (dcv_mlp_create): every member s
     dcv::TailWs tail;          // workspace of the contraction-split tail tile of row-tiled products (gemm.h: GemmDims::tail_split)
     dcv::EvalGroupWs eval_ws;  // grouped validation pass (dcv_mlp_eval_steps, block engine)
     int last_eval_group;       // members of the first grouped launch of the last dcv_mlp_eval_steps call (0: it stepped batch by batch)
+    int last_ride;             // reduction blocks that rode in the layer-0 weight-gradient launch of the last backward (0: none; ride_upper)
     void (*upper_cb)(void*);   // data-parallel overlap hook (dcv_mlp_set_upper_grads_callback) or null
     void* upper_cb_user;
     bool head_done;            // the last forward already ran the d x d loss head inside its statistics launch (one-GPU steps)
@@ -304,7 +305,10 @@ int reset_opt_state(dcv_mlp* m, hipStream_t s);
 ReduceArgs reduce_args_of(const dcv_mlp* m, const ReduceArgsView& v);
 int launch_reduce(dcv_mlp* m, const ReduceArgs& ra, int l0, int l1, hipStream_t s);   // layers [l0, l1), no update
 int reduce_upper(dcv_mlp* m, const ReduceArgs& ra, bool fuse_opt, bool* done, hipStream_t s);
-int finish_grads(dcv_mlp* m, const ReduceArgs& ra, bool fuse_opt, bool upper_done, hipStream_t s);
+struct OptArgs;   // reduce_quad.h
+int ride_upper(dcv_mlp* m, const ReduceArgs& ra, const Operand& A, const Operand& B, int64_t M, int64_t N, int64_t K, int64_t k_chunk,
+               const EpiSlab& epi, OptArgs* oa, hipStream_t s);   // 1 = not applicable
+int finish_grads(dcv_mlp* m, const ReduceArgs& ra, bool fuse_opt, bool upper_done, hipStream_t s, const OptArgs* ridden = nullptr);
 int apply_impl(dcv_mlp* m, void* stream);
 // mlp_heads.hip: launchers of the loss-head kernels
 int launch_sum_partials(const double* part, int nblocks, int width, double* out, hipStream_t s);

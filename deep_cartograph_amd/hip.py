@@ -728,6 +728,15 @@ class Mlp:
         """0 = layer by layer, 1 = fused small-network autoencoder step, 2 = fused small-network Deep-TICA kernels."""
         return int(self.lib.dcv_mlp_last_path(self.h))
 
+    def last_ride(self) -> int:
+        """Reduction workgroups that rode in the layer-0 weight-gradient launch of the last training backward (0: none)."""
+        return int(self.lib.dcv_mlp_last_ride(self.h))
+
+    def opt_state_view(self, which: int) -> Optional[torch.Tensor]:
+        """The optimiser's state tensor `which` (0, 1; 2 = the auxiliary one, None without it) as a view, laid out like params_view()."""
+        ptr = self.lib.dcv_mlp_opt_state(self.h, int(which))
+        return self._flat_view(ptr, self.n_params, torch.float32) if ptr else None
+
     def dropout_step(self) -> int:
         return int(self.lib.dcv_mlp_dropout_step(self.h))
 

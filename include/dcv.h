@@ -374,6 +374,14 @@ int32_t dcv_mlp_last_path(const dcv_mlp* m);
 /* Test hook: the batches in the first (largest) grouped launch of the last dcv_mlp_eval_steps call on the block engine, 0 when
  * that call stepped batch by batch or went through the fused small-network kernels. */
 int32_t dcv_mlp_last_eval_group(const dcv_mlp* m);
+/* Test hook: the reduction workgroups that rode in the layer-0 weight-gradient launch of the last training backward (one-GPU
+ * steps of the block engine with the update fused in: every gradient but layer 0's weights is reduced and updated there),
+ * 0 when that backward ended on the single reduction launch.  DCV_NO_REDUCE_RIDE=1 in the environment forces 0. */
+int32_t dcv_mlp_last_ride(const dcv_mlp* m);
+/* Test hook: the optimiser's state tensors on the device, dcv_mlp_num_params() floats each in the layout of dcv_mlp_params():
+ * which = 0 / 1 the two every optimiser owns (Adam: exp_avg / exp_avg_sq), 2 the auxiliary one (amsgrad maximum, centred
+ * RMSprop average) or NULL when the optimiser has none. */
+float* dcv_mlp_opt_state(dcv_mlp* m, int32_t which);
 /* Test hook: post-activation output of Linear `layer` in the last forward (rows x dims[layer + 1] floats, dense).
  * DCV_ESTATE after a fused small-network forward (dcv_mlp_last_path != 0: the activations never left LDS). */
 int dcv_mlp_layer_output(dcv_mlp* m, int32_t layer, int64_t rows, float* out_d, void* stream);
