@@ -1,133 +1,52 @@
 // Featurisation (compute_features): distances and torsions from trajectory coordinates, frames x atoms x 3 float32 in,
 // frames x features float32 out.
 //
-// A workgroup owns a tile of kFeatTile frames (fewer when the atoms it needs do not fit the LDS budget).  It stages
+// A workgroup owns a tile of kStageTile frames (fewer when the atoms it needs do not fit the LDS budget).  It stages
 // the coordinates of the atoms the features use into LDS with coalesced loads, computes every feature of its frames
 // in float64 from LDS (PLUMED computes in double: p = (double)x * unit, one rounding to float32 on store) and writes
 // the output rows with consecutive lanes on consecutive columns.  No atomics, no state between workgroups.
 //
-// Two staging forms, chosen on the host from the strides and the set of atoms the definitions name:
-//   ROWS    the innermost stride is 1 (dense (n, A, 3) rows, or the X / Y / Z planes of a DCD frame record) and the
-//           used atoms fill at least half of their index range [a_lo, a_hi]: that whole range is copied as contiguous
-//           rows with 16-byte loads on the 16-byte grid of the ADDRESS (the rows of a DCD record start anywhere), the
-//           ragged head and tail of a row with guarded scalar loads;
-//   GATHER  everything else (any strides, a sparse subset of an all-atom trajectory): one 4-byte load per coordinate
-//           of a used atom, lanes along the sorted list of used atoms, nothing else is read.
+// The two staging forms (ROWS and GATHER), their host-side choice and the LDS budget live in stage.h, which
+// superpose.hip shares.
 #include <algorithm>
 #include <vector>
 
 #include "common.h"
+#include "stage.h"
 
 namespace dcv {
 
-constexpr int kFeatThreads = 256;
-constexpr int kFeatTile = 16;               // frames per workgroup
-constexpr int kFeatLdsBudget = 48 * 1024;   // three workgroups per CU
-constexpr int kFeatLdsMax = 64 * 1024;      // one frame of the needed atoms must fit: 5461 atoms
+constexpr int kFeatThreads = kStageThreads;
 
 struct FeatArgs {
-    const float* xyz;
-    int64_t frame_stride, atom_stride, comp_stride;
-    int64_t n_frames;
+    StageArgs st;
     const int32_t* defs;   // n_defs x 6: kind, four atom indices REMAPPED to LDS atom slots, output column
-    const int32_t* used;   // GATHER: the nu used atoms, ascending
-    int32_t n_defs, nu;
-    int32_t rows;          // 1 = ROWS staging, 0 = GATHER
-    int32_t rpf;           // ROWS: rows per frame (3 planes, or 1 dense row)
-    int32_t L;             // ROWS: floats per row
-    int64_t row_off;       // ROWS: a_lo * atom_stride
-    int32_t comp_fast;     // GATHER: the component runs fastest over the lanes (comp_stride < atom_stride)
-    int32_t lfs, las, lcs; // LDS strides of frame, atom slot, component
-    int32_t tile;          // frames per workgroup
+    int32_t n_defs;
     double unit;
     float* out;
     int64_t ldo;
 };
 
-__device__ __forceinline__ float4 feat_nt_load4(const float* p) {
-    typedef float nv4 __attribute__((ext_vector_type(4)));
-    const nv4 v = __builtin_nontemporal_load(reinterpret_cast<const nv4*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-
-// Contiguous rows -> LDS.  A slot is one 16-byte-aligned group of four floats of the address space; slot k of a row
-// that starts m floats past such a boundary holds row elements 4k - m .. 4k - m + 3.  Four slots per thread are in
-// flight before the first LDS store.
-__device__ __forceinline__ void feat_stage_rows(const FeatArgs& a, int64_t f0, int nf, float* lds) {
-    const int t = threadIdx.x;
-    const int nsmax = (a.L + 6) >> 2;   // slots of a row for the worst alignment
-    const int total = nf * a.rpf * nsmax;
-    constexpr int U = 4;
-    for (int base = t; base < total; base += kFeatThreads * U) {
-        float4 v[U];
-        const float* g[U];
-        float* l[U];
-        int j0[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = base + u * kFeatThreads;
-            j0[u] = INT32_MIN;
-            if (i >= total) continue;
-            const int row = i / nsmax, k = i - row * nsmax;
-            const int f = row / a.rpf, c = row - f * a.rpf;
-            g[u] = a.xyz + (f0 + f) * a.frame_stride + (int64_t)c * a.comp_stride + a.row_off;
-            l[u] = lds + row * a.L;
-            const int m = (int)((reinterpret_cast<uintptr_t>(g[u]) >> 2) & 3);
-            const int j = 4 * k - m;
-            if (j >= a.L) continue;   // this row has fewer slots than nsmax
-            j0[u] = j;
-            if (j >= 0 && j + 4 <= a.L) v[u] = feat_nt_load4(g[u] + j);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = j0[u];
-            if (j == INT32_MIN) continue;
-            if (j >= 0 && j + 4 <= a.L) {
-                l[u][j] = v[u].x; l[u][j + 1] = v[u].y; l[u][j + 2] = v[u].z; l[u][j + 3] = v[u].w;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (j + e >= 0 && j + e < a.L) l[u][j + e] = g[u][j + e];
-            }
-        }
-    }
-}
-
-// Used atoms only -> LDS laid out [frame][component][slot].
-__device__ __forceinline__ void feat_stage_gather(const FeatArgs& a, int64_t f0, int nf, float* lds) {
-    const int per = 3 * a.nu;
-    const int total = nf * per;
-    for (int i = threadIdx.x; i < total; i += kFeatThreads) {
-        const int f = i / per, r = i - f * per;
-        int c, u;
-        if (a.comp_fast) { u = r / 3; c = r - u * 3; }
-        else { c = r / a.nu; u = r - c * a.nu; }
-        const int64_t off = (f0 + f) * a.frame_stride + (int64_t)a.used[u] * a.atom_stride + (int64_t)c * a.comp_stride;
-        lds[f * per + c * a.nu + u] = a.xyz[off];
-    }
-}
-
 __global__ __launch_bounds__(kFeatThreads) void featurize_kernel(const FeatArgs a, const int dlanes) {
 #pragma clang fp contract(off)   // a*b - c*d of identical products must be exactly 0 (collinear atoms), as in NumPy / PLUMED
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* lds = reinterpret_cast<float*>(smem);
-    const int64_t f0 = (int64_t)blockIdx.x * a.tile;
-    const int nf = a.n_frames - f0 < a.tile ? (int)(a.n_frames - f0) : a.tile;
-    if (a.rows) feat_stage_rows(a, f0, nf, lds);
-    else feat_stage_gather(a, f0, nf, lds);
+    const int64_t f0 = (int64_t)blockIdx.x * a.st.tile;
+    const int nf = a.st.n_frames - f0 < a.st.tile ? (int)(a.st.n_frames - f0) : a.st.tile;
+    stage_tile(a.st, f0, nf, lds);
     __syncthreads();
 
     // lanes along the definitions (consecutive lanes -> consecutive output columns), the rest of the workgroup along frames
     const int t = threadIdx.x;
     const int dl = t & (dlanes - 1), fg = t / dlanes, fgroups = kFeatThreads / dlanes;
     const double unit = a.unit;
-    const int las = a.las, lcs = a.lcs;
+    const int las = a.st.las, lcs = a.st.lcs;
     for (int d = dl; d < a.n_defs; d += dlanes) {
         const int32_t* rec = a.defs + (int64_t)d * 6;
         const int kind = rec[0], s0 = rec[1] * las, s1 = rec[2] * las, s2 = rec[3] * las, s3 = rec[4] * las;
         float* o = a.out + rec[5];
         for (int f = fg; f < nf; f += fgroups) {
-            const float* lf = lds + f * a.lfs;
+            const float* lf = lds + f * a.st.lfs;
             float* of = o + (f0 + f) * a.ldo;
             const double p0x = (double)lf[s0] * unit, p0y = (double)lf[s0 + lcs] * unit, p0z = (double)lf[s0 + 2 * lcs] * unit;
             const double p1x = (double)lf[s1] * unit, p1y = (double)lf[s1 + lcs] * unit, p1z = (double)lf[s1 + 2 * lcs] * unit;
@@ -197,37 +116,16 @@ extern "C" int dcv_featurize(const float* xyz_d, int64_t n_frames, int64_t frame
     if (n_frames == 0) return DCV_OK;
 
     // ---- the atoms to stage and their LDS slots
-    std::vector<int32_t> used, slot((size_t)n_atoms, 0);
-    for (int32_t i = 0; i < n_atoms; ++i)
-        if (is_used[(size_t)i]) used.push_back(i);
-    const int32_t nu = (int32_t)used.size(), a_lo = used.front(), a_hi = used.back();
-    const int64_t range = (int64_t)a_hi - a_lo + 1;
-    const bool planes = atom_stride == 1, dense = comp_stride == 1 && atom_stride == 3;
     FeatArgs a{};
-    a.rows = (planes || dense) && range <= 2 * (int64_t)nu;
-    int64_t per_frame;   // LDS floats per frame
-    if (a.rows) {
-        for (int32_t i = a_lo; i <= a_hi; ++i) slot[(size_t)i] = i - a_lo;
-        per_frame = 3 * range;
-        a.rpf = planes ? 3 : 1;
-        a.L = (int32_t)(planes ? range : 3 * range);
-        a.row_off = (int64_t)a_lo * atom_stride;
-        a.las = planes ? 1 : 3;
-        a.lcs = planes ? (int32_t)range : 1;
-    } else {
-        for (int32_t u = 0; u < nu; ++u) slot[(size_t)used[(size_t)u]] = u;
-        per_frame = 3 * (int64_t)nu;
-        a.comp_fast = comp_stride < atom_stride;
-        a.las = 1;
-        a.lcs = nu;
-    }
-    DCV_REQUIRE(per_frame * (int64_t)sizeof(float) <= kFeatLdsMax,
+    StagePlan plan;
+    stage_plan(is_used, n_atoms, atom_stride, comp_stride, a.st, plan);
+    const std::vector<int32_t>&used = plan.used, &slot = plan.slot;
+    const int64_t per_frame = plan.per_frame;
+    DCV_REQUIRE(per_frame * (int64_t)sizeof(float) <= kStageLdsMax,
                 "dcv_featurize: one frame of the %lld atoms to stage exceeds %d bytes of LDS (at most %d atoms)", (long long)(per_frame / 3),
-                kFeatLdsMax, kFeatLdsMax / 12);
-    a.lfs = (int32_t)per_frame;
-    int tile = (int)(kFeatLdsBudget / (per_frame * (int64_t)sizeof(float)));
-    a.tile = tile < 1 ? 1 : (tile > kFeatTile ? kFeatTile : tile);
-    const int64_t blocks = cdiv(n_frames, a.tile);
+                kStageLdsMax, kStageLdsMax / 12);
+    a.st.tile = stage_tile_frames(per_frame, 0, 0);
+    const int64_t blocks = cdiv(n_frames, a.st.tile);
     DCV_REQUIRE(blocks <= 0x7fffffffLL, "dcv_featurize: %lld frames need more than 2^31 - 1 workgroups", (long long)n_frames);
 
     std::vector<int32_t> rec((size_t)n_defs * 6, 0);
@@ -246,16 +144,17 @@ extern "C" int dcv_featurize(const float* xyz_d, int64_t n_frames, int64_t frame
     DCV_CHECK_HIP(hipMemcpyAsync(defs_d, rec.data(), rec.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     DCV_CHECK_HIP(hipMemcpyAsync(used_d, used.data(), used.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
 
-    a.xyz = xyz_d;
-    a.frame_stride = frame_stride; a.atom_stride = atom_stride; a.comp_stride = comp_stride;
-    a.n_frames = n_frames;
-    a.defs = defs_d; a.used = used_d;
-    a.n_defs = n_defs; a.nu = nu;
+    a.st.xyz = xyz_d;
+    a.st.frame_stride = frame_stride; a.st.atom_stride = atom_stride; a.st.comp_stride = comp_stride;
+    a.st.n_frames = n_frames;
+    a.st.used = used_d;
+    a.defs = defs_d;
+    a.n_defs = n_defs;
     a.unit = unit;
     a.out = out_d; a.ldo = ldo;
     int dlanes = 1;
     while (dlanes < kFeatThreads && dlanes < n_defs) dlanes *= 2;
-    const size_t lds = (size_t)a.tile * (size_t)per_frame * sizeof(float);
+    const size_t lds = (size_t)a.st.tile * (size_t)per_frame * sizeof(float);
     hipLaunchKernelGGL(featurize_kernel, dim3((unsigned)blocks), dim3(kFeatThreads), lds, s, a, dlanes);
     DCV_CHECK_LAUNCH();
     return DCV_OK;

@@ -1,8 +1,9 @@
 """`deep_carto`-style entry point for the accelerated part of the workflow:
-(compute_features) -> (filter_features) -> train_colvars -> (traj_projection of supplementary data) -> traj_cluster,
+(analyze_geometry) -> (compute_features) -> (filter_features) -> train_colvars -> (traj_projection of supplementary data) -> traj_cluster,
 starting from trajectories (.dcd / .npy coordinates plus a PDB topology: distances and virtual dihedrals are computed
 on the device) or from pre-computed feature matrices (PLUMED COLVAR text or the binary .npy fast path).
-The reference's geometry analysis and augmentation steps (deep_carto.py:191-290) need MDAnalysis and are out of
+With trajectories and an `analyze_geometry` section in the YAML, RMSD / RMSF / dRMSD are computed first (on the device,
+geometry.py) into <out>/analyze_geometry.  The reference's augmentation steps (deep_carto.py:191-290) are out of
 scope; its PLUMED featurisation is replaced by `compute_features` for the feature kinds trajectory.py documents.
 The YAML keeps the reference's `compute_features` / `filter_features` / `train_colvars` / `traj_cluster` sections.
 Feature filtering needs only the feature matrices: it runs when the YAML has a `filter_features` section and no
@@ -22,7 +23,7 @@ import time
 from typing import Dict, List, Optional
 
 from .common import get_unique_path, read_configuration, read_features_list
-from .tools import compute_features, filter_features, traj_cluster, traj_projection, train_colvars
+from .tools import analyze_geometry, compute_features, filter_features, traj_cluster, traj_projection, train_colvars
 
 logger = logging.getLogger("deep_cartograph")
 
@@ -31,8 +32,9 @@ def deep_cartograph(configuration: Dict, colvars_paths: List[str], sup_colvars_p
                     features_list: Optional[List[str]] = None, dimension: Optional[int] = None, cvs: Optional[List[str]] = None,
                     restart: bool = False, output_folder: Optional[str] = None, trajectory_data: Optional[List[str]] = None,
                     topology_data: Optional[List[str]] = None, sup_trajectory_data: Optional[List[str]] = None) -> Dict[str, Dict]:
-    """(compute_features) -> (filter_features) -> train_colvars -> traj_projection (supplementary colvars) -> traj_cluster
-    per CV (reference deep_carto.py:292-361).  With `trajectory_data` (and `topology_data`: one PDB for all, or one per
+    """(analyze_geometry) -> (compute_features) -> (filter_features) -> train_colvars -> traj_projection (supplementary
+    colvars) -> traj_cluster per CV (reference deep_carto.py:292-361).  With `trajectory_data` and an `analyze_geometry`
+    section in the configuration that tool runs first, into <out>/analyze_geometry.  With `trajectory_data` (and `topology_data`: one PDB for all, or one per
     trajectory) the `compute_features` section runs first and its outputs become `colvars_paths`; `sup_trajectory_data`
     likewise become `sup_colvars_paths`, always with the FIRST topology.  Giving both is an error.  A `filter_features` section in the configuration selects
     the features first unless `features_list` is given.  `restart` reuses the output folder and skips what exists."""
@@ -49,6 +51,9 @@ def deep_cartograph(configuration: Dict, colvars_paths: List[str], sup_colvars_p
             raise ValueError("trajectory_data needs topology_data (a PDB file)")
         topology_data = [topology_data] if isinstance(topology_data, str) else list(topology_data)
         sup_trajectory_data = [sup_trajectory_data] if isinstance(sup_trajectory_data, str) else sup_trajectory_data
+        if "analyze_geometry" in configuration:
+            analyze_geometry(configuration=configuration["analyze_geometry"] or {}, trajectories=trajectory_data, topologies=topology_data,
+                             output_folder=os.path.join(output_folder, "analyze_geometry"))
         cf = configuration.get("compute_features") or {}
         colvars_paths = compute_features(configuration=cf, trajectory_data=trajectory_data, topology_data=topology_data,
                                          output_folder=os.path.join(output_folder, "compute_features"))

@@ -108,6 +108,25 @@ def dip_sorted(Xs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tens
 _FEAT_COLUMNS = {FEAT_DISTANCE: 1, FEAT_TORSION_SINCOS: 2, FEAT_TORSION: 1}
 
 
+def _coordinates(who: str, xyz: torch.Tensor, n_atoms: int, strides):
+    """(n, base pointer, frame, atom and component stride) of the two coordinate forms the trajectory kernels accept."""
+    if xyz.dtype != torch.float32:
+        raise DcvError(f"{who}: coordinates must be float32, got {xyz.dtype}")
+    if strides is None:
+        if xyz.dim() != 3 or xyz.shape[1] != n_atoms or xyz.shape[2] != 3:
+            raise DcvError(f"{who}: expected a (n, {n_atoms}, 3) tensor, got {tuple(xyz.shape)}")
+        n = xyz.shape[0]
+        fs, as_, cs = (int(s) for s in xyz.stride())
+        return n, xyz.data_ptr(), fs, as_, cs
+    n, offset, fs, as_, cs = (int(v) for v in strides)
+    if xyz.dim() != 1 or not xyz.is_contiguous():
+        raise DcvError(f"{who}: with explicit strides the coordinates must be a contiguous 1-D buffer")
+    last = offset + max(n - 1, 0) * fs + (n_atoms - 1) * as_ + 2 * cs
+    if n < 0 or offset < 0 or min(fs, as_, cs) < 0 or (n > 0 and last >= xyz.numel()):
+        raise DcvError(f"{who}: layout {tuple(strides)} with {n_atoms} atoms reaches element {last} of a buffer of {xyz.numel()}")
+    return n, xyz.data_ptr() + 4 * offset, fs, as_, cs
+
+
 def featurize(xyz: torch.Tensor, defs, n_atoms: int, strides=None, unit: float = 0.1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[n, F] float32 distances / torsions of every frame (dcv_featurize).
 
@@ -118,26 +137,11 @@ def featurize(xyz: torch.Tensor, defs, n_atoms: int, strides=None, unit: float =
     ``defs``: (n_defs, 6) int32 records [kind, a0, a1, a2, a3, out_column] (FEAT_*), on the host.
     ``out``: optional row-major float32 [n, >= F] tensor; only the columns the records name are written."""
     _require_gpu(xyz, out)
-    if xyz.dtype != torch.float32:
-        raise DcvError(f"featurize: coordinates must be float32, got {xyz.dtype}")
     defs = np.ascontiguousarray(np.asarray(defs), dtype=np.int32)
     if defs.ndim != 2 or defs.shape[1] != 6 or defs.shape[0] == 0:
         raise DcvError(f"featurize: defs must be a non-empty (n_defs, 6) int32 array, got shape {defs.shape}")
     n_atoms = int(n_atoms)
-    if strides is None:
-        if xyz.dim() != 3 or xyz.shape[1] != n_atoms or xyz.shape[2] != 3:
-            raise DcvError(f"featurize: expected a (n, {n_atoms}, 3) tensor, got {tuple(xyz.shape)}")
-        n, offset = xyz.shape[0], 0
-        fs, as_, cs = (int(s) for s in xyz.stride())
-        base = xyz.data_ptr()
-    else:
-        n, offset, fs, as_, cs = (int(v) for v in strides)
-        if xyz.dim() != 1 or not xyz.is_contiguous():
-            raise DcvError("featurize: with explicit strides the coordinates must be a contiguous 1-D buffer")
-        last = offset + max(n - 1, 0) * fs + (n_atoms - 1) * as_ + 2 * cs
-        if n < 0 or offset < 0 or min(fs, as_, cs) < 0 or (n > 0 and last >= xyz.numel()):
-            raise DcvError(f"featurize: layout {tuple(strides)} with {n_atoms} atoms reaches element {last} of a buffer of {xyz.numel()}")
-        base = xyz.data_ptr() + 4 * offset
+    n, base, fs, as_, cs = _coordinates("featurize", xyz, n_atoms, strides)
     F = max(int(r[5]) + _FEAT_COLUMNS.get(int(r[0]), 1) for r in defs)
     if out is None:
         out = torch.empty(n, max(F, 1), dtype=torch.float32, device=xyz.device)
@@ -155,6 +159,71 @@ def featurize(xyz: torch.Tensor, defs, n_atoms: int, strides=None, unit: float =
     ldo = max(out.stride(0), out.shape[1])   # the stride of a one-row tensor is arbitrary
     check(lib.dcv_featurize(base, n, fs, as_, cs, n_atoms, defs.ctypes.data, defs.shape[0], float(unit), _ptr(out), ldo,
                             _ptr(ws), ws.numel(), _stream()), "dcv_featurize")
+    return out
+
+
+SUPERPOSE_OUTPUTS = ("transform", "rmsd", "aligned", "moments")
+
+
+def superpose(xyz: torch.Tensor, n_atoms: int, fit, fit_ref, sel=None, sel_ref=None, fit_weights=None, strides=None,
+              want=("rmsd",)) -> dict:
+    """Optimal rigid superposition of every frame onto ``fit_ref`` on the atoms ``fit`` (dcv_superpose); Angstrom in,
+    Angstrom out, float64 arithmetic.  Returns a dict with the outputs named in ``want``:
+
+    ``transform`` [n, 16] float64: R row-major (row-vector convention), c_mob, c_ref, fit RMSD;
+    ``rmsd``      [n, 2] float64: fit RMSD and the unweighted RMSD of ``sel`` to ``sel_ref``; without ``sel_ref`` there is
+                  no second RMSD and the tensor is [n, 1] (the library's placeholder 0 is not handed out);
+    ``aligned``   [n, n_sel, 3] float32: the aligned ``sel`` atoms;
+    ``moments``   [n_sel, 3, 2] float64: per atom and component the sum over frames of d and d^2, d = aligned - sel_ref.
+
+    ``xyz``, ``n_atoms`` and ``strides`` as in :func:`featurize`.  ``fit`` / ``sel``: atom indices; ``fit_ref`` (n_fit, 3)
+    and ``sel_ref`` (n_sel, 3): float64 reference positions, on the host; ``fit_weights``: n_fit non-negative weights."""
+    _require_gpu(xyz)
+    want = tuple(want)
+    unknown = [w for w in want if w not in SUPERPOSE_OUTPUTS]
+    if unknown or not want:
+        raise DcvError(f"superpose: want must name some of {SUPERPOSE_OUTPUTS}, got {want}")
+    n_atoms = int(n_atoms)
+    n, base, fs, as_, cs = _coordinates("superpose", xyz, n_atoms, strides)
+    fit = np.ascontiguousarray(np.asarray(fit).reshape(-1), dtype=np.int32)
+    fit_ref = np.ascontiguousarray(np.asarray(fit_ref, dtype=np.float64))
+    if fit.size == 0 or fit_ref.shape != (fit.size, 3):
+        raise DcvError(f"superpose: fit_ref must be ({fit.size}, 3) for {fit.size} fit atoms (at least one), got {fit_ref.shape}")
+    if fit_weights is not None:
+        fit_weights = np.ascontiguousarray(np.asarray(fit_weights, dtype=np.float64).reshape(-1))
+        if fit_weights.size != fit.size:
+            raise DcvError(f"superpose: {fit_weights.size} weights for {fit.size} fit atoms")
+    n_sel = 0
+    if sel is not None:
+        sel = np.ascontiguousarray(np.asarray(sel).reshape(-1), dtype=np.int32)
+        n_sel = int(sel.size)
+    if sel_ref is not None:
+        sel_ref = np.ascontiguousarray(np.asarray(sel_ref, dtype=np.float64))
+        if n_sel == 0 or sel_ref.shape != (n_sel, 3):
+            raise DcvError(f"superpose: sel_ref must be ({n_sel}, 3) for a selection of {n_sel} atoms, got {sel_ref.shape}")
+    if ("aligned" in want or "moments" in want) and n_sel == 0:
+        raise DcvError("superpose: aligned coordinates and moments need a selection (sel)")
+    dev = xyz.device
+    out = {}
+    if "transform" in want:
+        out["transform"] = torch.empty(n, 16, dtype=torch.float64, device=dev)
+    if "rmsd" in want:
+        out["rmsd"] = torch.empty(n, 2, dtype=torch.float64, device=dev)
+    if "aligned" in want:
+        out["aligned"] = torch.empty(n, n_sel, 3, dtype=torch.float32, device=dev)
+    if "moments" in want:
+        out["moments"] = torch.zeros(n_sel, 3, 2, dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    ws = _ws(lib.dcv_superpose_workspace(n, n_atoms, fit.size, n_sel), dev)
+    # with no frames the library only validates; an empty tensor has no data pointer to hand over
+    check(lib.dcv_superpose(base if n else ws.data_ptr(), n, fs, as_, cs, n_atoms, fit.ctypes.data,
+                            None if fit_weights is None else fit_weights.ctypes.data, fit_ref.ctypes.data, fit.size,
+                            None if sel is None or n_sel == 0 else sel.ctypes.data, None if sel_ref is None else sel_ref.ctypes.data, n_sel,
+                            _ptr(out.get("transform")) if n else None, _ptr(out.get("rmsd")) if n else None,
+                            _ptr(out.get("aligned")) if n else None, 3 * n_sel, _ptr(out.get("moments")), _ptr(ws), ws.numel(), _stream()),
+          "dcv_superpose")
+    if "rmsd" in out and sel_ref is None:
+        out["rmsd"] = out["rmsd"][:, :1]
     return out
 
 

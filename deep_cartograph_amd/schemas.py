@@ -262,3 +262,42 @@ class ComputeFeaturesSchema(BaseModel):
     plumed_environment: PlumedEnvironment = PlumedEnvironment()
     # this project's extension: "npy" writes the binary fast path colvars.npy + colvars.names.txt, "dat" a COLVAR text file
     colvars_format: Literal["npy", "dat"] = "npy"
+
+
+# ---------------------------------------------------------------- analyze_geometry (yaml_schemas/analyze_geometry.py)
+# The reference's default selections are "protein and name CA"; the selection grammar here has no `protein` keyword
+# (trajectory.select_atoms), so the defaults are "name CA".
+class RMSSettings(BaseModel):
+    title: str
+    # atoms the RMS is computed for
+    selection: str = "name CA"
+    # atoms every frame is fitted on before the RMS is computed
+    fit_selection: str = "name CA"
+
+
+class RMSDSettings(RMSSettings):
+    title: str = "Protein Backbone RMSD"
+
+
+class RMSFSettings(RMSSettings):
+    title: str = "Protein Backbone RMSF"
+
+
+class dRMSDSettings(BaseModel):
+    title: str = "Protein Backbone dRMSD"
+    selection: str = "name CA"
+    # keep every selection_stride-th atom of the selection
+    selection_stride: int = 5
+
+
+class AnalysisList(BaseModel):
+    RMSD: Dict[str, RMSDSettings] = {}
+    RMSF: Dict[str, RMSFSettings] = {}
+    dRMSD: Dict[str, dRMSDSettings] = {}
+
+
+class AnalyzeGeometrySchema(BaseModel):
+    analysis: AnalysisList = AnalysisList()
+    # time between frames in ps
+    dt_per_frame: float = 1.0
+    run: bool = True

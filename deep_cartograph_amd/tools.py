@@ -1,5 +1,5 @@
 """The tools of the CV-fit path with the reference's API (argument names, output tree,
-CSV formats): compute_features (tools/compute_features/compute_features.py:25-227), filter_features (tools/filter_features/filter_features.py:22-31), train_colvars (tools/train_colvars/train_colvars.py:20-36), traj_projection
+CSV formats): analyze_geometry (tools/analyze_geometry/analyze_geometry.py:13-143), compute_features (tools/compute_features/compute_features.py:25-227), filter_features (tools/filter_features/filter_features.py:22-31), train_colvars (tools/train_colvars/train_colvars.py:20-36), traj_projection
 (tools/traj_projection/traj_projection.py:19-27), traj_cluster (tools/traj_cluster/traj_cluster.py:
 18-28).  Figures, FES estimation and PDB/XTC extraction (matplotlib / MDAnalysis) are outside the
 accelerated path and are not produced."""
@@ -18,7 +18,7 @@ import pandas as pd
 from . import statistics
 from .common import merge_configurations, save_list, validate_configuration
 from .cv_calculator import CVCalculator, calculator_class
-from .schemas import ComputeFeaturesSchema, FilterFeaturesSchema, TrainColvarsSchema, TrajClusterSchema, TrajProjectionSchema
+from .schemas import AnalyzeGeometrySchema, ComputeFeaturesSchema, FilterFeaturesSchema, TrainColvarsSchema, TrajClusterSchema, TrajProjectionSchema
 
 logger = logging.getLogger(__name__)
 
@@ -121,6 +121,71 @@ def compute_features(configuration: Dict, trajectory_data: Union[str, List[str]]
             os.remove(tmp_path)
     logger.info("Elapsed time (Compute features): %s", time.strftime("%H h %M min %S s", time.gmtime(time.time() - t0)))
     return colvars_paths
+
+
+def analyze_geometry(configuration: Dict, trajectories: List[str], topologies: List[str], ref_topologies: Optional[List[str]] = None,
+                     output_folder: str = "analyze_geometry", memory_budget: Optional[int] = None) -> Dict[str, str]:
+    """RMSD, per-residue RMSF and dRMSD of every trajectory, computed on the device (geometry.py) instead of frame by
+    frame with MDAnalysis.  The loop, the keys and the x axes are the reference's: RMSD per trajectory and reference
+    (`<traj>first_frame` against the topology's own positions, `<traj>_to_<ref stem>` otherwise) and dRMSD per
+    trajectory and reference (the topology when there is none) over arange(n) * dt_per_frame * 1e-3, RMSF per trajectory
+    over residue numbers.  Each series goes to a CSV in the format of the reference's save_data (header
+    `x_label,y_label`, np.savetxt); the files are named `<analysis name>_<category>_<key>.csv` -- the reference names
+    them `<key>.csv`, so two analyses of one trajectory overwrite each other.  No figures.  Returns {file stem: path}
+    of what was written (empty with `run: false`).  dRMSD values are in nm under the reference's "(A)" label, as the
+    reference's are.  `memory_budget` bounds a chunk of frames on the device.  Limits: fit and selected atoms together
+    at most 5 461 per analysis, and an RMSF's fit selection at most 2 726 atoms (geometry.rmsf).  No CPU fallback."""
+    import torch
+
+    from . import geometry
+    from ._lib import DcvError
+
+    t0 = time.time()
+    trajectories, topologies = _as_list(trajectories) or [], _as_list(topologies) or []
+    ref_topologies = _as_list(ref_topologies)
+    if len(topologies) == 1:
+        topologies = topologies * len(trajectories)
+    if len(trajectories) != len(topologies):
+        raise ValueError(f"Number of trajectories ({len(trajectories)}) and topologies ({len(topologies)}) do not match.")
+    for path in trajectories + topologies + (ref_topologies or []):
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"File not found: {path}")
+    os.makedirs(output_folder, exist_ok=True)
+    configuration = validate_configuration(configuration or {}, AnalyzeGeometrySchema, output_folder)
+    written: Dict[str, str] = {}
+    if not configuration["run"]:
+        logger.info("Skipping Analyze Geometry step.")
+        return written
+    if any(configuration["analysis"].values()) and not torch.cuda.is_available():
+        raise DcvError("analyze_geometry needs an MI355X (cuda) device: the geometry is computed by libdcv.so, there is no CPU fallback")
+    dt_per_frame = float(configuration["dt_per_frame"]) * 1e-3   # ns
+    for category, analyses in configuration["analysis"].items():
+        for name, params in (analyses or {}).items():
+            logger.info(f"Analyzing {category}: {name}")
+            y_label = f"{category} (A)"
+            x_label = "Residue" if category == "RMSF" else "Time (ns)"
+            x_data, y_data = {}, {}
+            for traj_path, top_path in zip(trajectories, topologies):
+                traj_name = Path(traj_path).stem
+                if category == "RMSD":
+                    for ref in ref_topologies or [None]:
+                        key = traj_name + (f"_to_{Path(ref).stem}" if ref else "first_frame")
+                        y_data[key] = geometry.rmsd(traj_path, top_path, params["selection"], params["fit_selection"], ref, memory_budget)
+                        x_data[key] = np.arange(len(y_data[key])) * dt_per_frame
+                elif category == "RMSF":
+                    y_data[traj_name], x_data[traj_name] = geometry.rmsf(traj_path, top_path, params["selection"], params["fit_selection"],
+                                                                         memory_budget)
+                elif category == "dRMSD":
+                    for ref in ref_topologies or [top_path]:
+                        key = f"{traj_name}_to_{Path(ref).stem}"
+                        y_data[key] = geometry.drmsd(traj_path, top_path, params["selection"], params["selection_stride"], ref, memory_budget)
+                        x_data[key] = np.arange(len(y_data[key])) * dt_per_frame
+            for key, y in y_data.items():
+                stem = f"{name}_{category}_{key}"
+                written[stem] = os.path.join(output_folder, stem + ".csv")
+                np.savetxt(written[stem], np.column_stack((x_data[key], y)), delimiter=",", header=f"{x_label},{y_label}", comments="")
+    logger.info("Elapsed time (Analyze geometry): %s", time.strftime("%H h %M min %S s", time.gmtime(time.time() - t0)))
+    return written
 
 
 def filter_features(configuration: Dict, colvars_paths: Union[str, List[str]], waypoint_colvars_paths: Optional[List[str]] = None,

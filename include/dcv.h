@@ -121,6 +121,43 @@ int dcv_featurize(const float* xyz_d, int64_t n_frames, int64_t frame_stride, in
                   int32_t n_atoms, const int32_t* defs_h, int32_t n_defs, double unit,
                   float* out_d, int64_t ldo, void* ws_d, size_t ws_bytes, void* stream);
 
+/* ---- optimal rigid superposition (analyze_geometry: RMSD, average structure, RMSF) --------------------------------
+ * Fits every frame onto a reference structure on the n_fit atoms fit_h (weights fit_w_h, NULL = all 1) and measures
+ * on the n_sel atoms sel_h.  Coordinates are addressed as in dcv_featurize (xyz_d, the three strides, n_atoms); no
+ * unit conversion: Angstrom in, Angstrom out.  Row-vector convention.  Per frame, with c_mob and c_ref the weighted
+ * centroids of the frame's fit atoms and of fit_ref_h (n_fit x 3), R is the PROPER rotation (det = +1) that minimises
+ * sum_i w_i |(x_i - c_mob) . R - (y_i - c_ref)|^2 and aligned = (x - c_mob) . R + c_ref.  Outputs, each may be NULL:
+ *   transform_d  n x 16   R row-major (9), c_mob (3), c_ref (3), fit RMSD sqrt(sum_i w_i |residual_i|^2 / sum_i w_i)
+ *   rmsd_d       n x 2    fit RMSD, then the unweighted sqrt(mean over sel |aligned - sel_ref|^2); the second entry is
+ *                         0 when sel_ref_h (n_sel x 3) is NULL
+ *   aligned_d    n x lda  the selected atoms of every frame (x, y, z of atom 0, of atom 1, ...), rounded once to
+ *                         float32; lda >= 3 n_sel
+ *   moments_d    n_sel x 3 x 2   per selected atom and component the sum over the frames of d and of d^2, with
+ *                         d = aligned - sel_ref (the shift keeps the sums free of cancellation); needs sel_ref_h
+ * Arithmetic: float64 behind the float32 load.  The coordinates are centred before the 3 x 3 correlation is formed;
+ * the rotation is the eigenvector of the largest eigenvalue of Horn's symmetric 4 x 4 quaternion matrix, found by
+ * cyclic Jacobi rotations (convergence test, at most 16 sweeps); both RMSDs come from the residuals of the
+ * transformed coordinates.  A mirror image of the reference comes back with the (larger) RMSD of the best proper
+ * rotation.  One or two fit atoms, collinear and coplanar sets are legal: the RMSD is unique where R is not, and R is
+ * a rotation in every case.  Non-finite coordinates propagate to the outputs of their frame.
+ * One launch stages the union of the fit and the selected atoms of 16 frames per workgroup into LDS as dcv_featurize
+ * does (fewer frames when 48 KB would be exceeded) and reads them from there only; at most DCV_SUPERPOSE_MAX_GROUPS
+ * workgroups stride over the tiles.  The moments are kept as float64 partials per workgroup in LDS (48 bytes per
+ * selected atom), written once and added in workgroup order by a second small launch: no floating-point atomics,
+ * bit-identical from run to run.
+ * Everything is validated before anything is launched.  DCV_EINVAL: an index outside [0, n_atoms); n_fit < 1; a
+ * weight that is negative or not finite, or weights that do not sum to a positive number; lda < 3 n_sel; moments
+ * without sel_ref_h; bad strides; one frame of the staged atoms above 64 KB of LDS (5461 atoms), or that frame plus
+ * the parked transform (96 bytes, with aligned_d or moments_d) and the moment partials above 64 KB.  DCV_ENOMEM: a
+ * workspace that is too small.  n_frames = 0 is DCV_OK.  The reference and both atom lists are copied into the
+ * workspace.  Algorithmic traffic per frame: 12 bytes per staged atom, plus 12 per selected atom with aligned_d. */
+#define DCV_SUPERPOSE_MAX_GROUPS 768   /* upper bound of workgroups (and of moment partials) of one call */
+size_t dcv_superpose_workspace(int64_t n_frames, int32_t n_atoms, int32_t n_fit, int32_t n_sel);
+int dcv_superpose(const float* xyz_d, int64_t n_frames, int64_t frame_stride, int64_t atom_stride, int64_t comp_stride,
+                  int32_t n_atoms, const int32_t* fit_h, const double* fit_w_h, const double* fit_ref_h, int32_t n_fit,
+                  const int32_t* sel_h, const double* sel_ref_h, int32_t n_sel, double* transform_d, double* rmsd_d,
+                  float* aligned_d, int64_t lda, double* moments_d, void* ws_d, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- normalisation (a3)
  * Replaces LinearCalculator.normalize_data, cv_calculator.py:833-835
  * (data.sub_(mean).div_(range) in float32).  Y may alias X (in place, as the reference). */
