@@ -161,6 +161,8 @@ SIGNATURES = {
     "dcv_mr_mst_workspace": (_SZ, [_I64, _I32]),
     "dcv_mr_mst": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _P, _SZ, _P]),
     "dcv_gemm_f32": (C.c_int, [_I32, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P]),
+    "dcv_debug_gemm_log_reset": (None, []),
+    "dcv_debug_gemm_log_read": (_I32, [C.POINTER(_I32), _I32]),
 }
 
 _lib = None

@@ -52,4 +52,10 @@ int num_cus();
 bool gemm_split();
 void set_gemm_split(bool on);
 
+// Test hook (dcv_debug_gemm_log_*): host-side record of the product plans the block engine's launchers enqueued, so that a
+// test can assert which tile family, loader and arithmetic flavour a shape reached instead of assuming it.  Fixed capacity;
+// entries behind it are dropped.  Written on the host by the launch wrappers only: no kernel knows of it.
+enum GemmLaunchForm { kFormSingle = 0, kFormGroup = 1, kFormPair = 2, kFormRide = 3 };
+void gemm_log_push(int form, int mode, int tm, int tn, bool split, bool vec, bool gather, int64_t splits, int tail_split);
+
 }  // namespace dcv

@@ -1,6 +1,7 @@
 #include "common.h"
 #include <string.h>
 #include <stdlib.h>
+#include <atomic>
 
 namespace dcv {
 static thread_local char g_err[512] = "";
@@ -33,7 +34,30 @@ bool gemm_split() {
     return g_gemm_split == 1;
 }
 void set_gemm_split(bool on) { g_gemm_split = on ? 1 : 0; }
+
+// ---- launch-plan log (common.h).  A full log costs a launch one relaxed load.
+constexpr int kGemmLogCap = 256, kGemmLogFields = 9;
+static int32_t g_gemm_log[kGemmLogCap][kGemmLogFields];
+static std::atomic<int> g_gemm_log_n{0};
+void gemm_log_push(int form, int mode, int tm, int tn, bool split, bool vec, bool gather, int64_t splits, int tail_split) {
+    if (g_gemm_log_n.load(std::memory_order_relaxed) >= kGemmLogCap) return;
+    const int i = g_gemm_log_n.fetch_add(1, std::memory_order_relaxed);
+    if (i >= kGemmLogCap) {   // lost a race for the last slot
+        g_gemm_log_n.store(kGemmLogCap, std::memory_order_relaxed);
+        return;
+    }
+    int32_t* e = g_gemm_log[i];
+    e[0] = form; e[1] = mode; e[2] = tm; e[3] = tn; e[4] = split; e[5] = vec; e[6] = gather;
+    e[7] = (int32_t)splits; e[8] = tail_split;
+}
 }  // namespace dcv
+
+extern "C" void dcv_debug_gemm_log_reset(void) { dcv::g_gemm_log_n.store(0); }
+extern "C" int32_t dcv_debug_gemm_log_read(int32_t* out, int32_t cap) {
+    const int n = dcv::g_gemm_log_n.load() < dcv::kGemmLogCap ? dcv::g_gemm_log_n.load() : dcv::kGemmLogCap;
+    for (int i = 0; out != nullptr && i < n && i < cap; ++i) memcpy(out + (size_t)i * dcv::kGemmLogFields, dcv::g_gemm_log[i], sizeof(dcv::g_gemm_log[i]));
+    return n;
+}
 
 extern "C" int dcv_set_gemm_mode(int mode) {
     DCV_REQUIRE(mode == DCV_GEMM_NATIVE_F32 || mode == DCV_GEMM_SPLIT_BF16X6, "dcv_set_gemm_mode: unknown mode %d", mode);

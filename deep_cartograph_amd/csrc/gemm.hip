@@ -1,5 +1,11 @@
-// Plain C = op(A) . op(B) entry point over the FP32 MFMA engine (building block, used by the
-// parity tests to check every operand form and tile shape against a float64 product).
+// Plain C = op(A) . op(B) entry points over the block engine (building block of the parity tests, which compare it with a
+// float64 product).  Which tile family a shape reaches follows pick_cfg and the CU count; the tests assert it from the
+// launch-plan log (dcv_debug_gemm_log_read):
+//   tests/test_kernels_gpu.py     (test_gemm_exact_on_integers, test_gemm_random_fp32) reaches the narrow tiles (128 x 32,
+//                                 32 x 128) and 64 x 128 for NT / NN, the narrow tiles and 64 x 64 for TN;
+//   tests/test_gemm_tiles_gpu.py  128 x 128 and 64 x 64 in every mode, both arithmetic flavours, split-K slab by slab;
+//   tests/test_mlp_gpu.py         (test_step_at_128_row_tiles_kink_aware) the engine's own epilogues, the pair and ride
+//                                 launches and the tail-tile cut at 128 x 128, as whole steps against float64.
 #include <type_traits>
 #include "gemm_kernels.h"
 

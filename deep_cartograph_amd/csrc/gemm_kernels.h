@@ -87,6 +87,23 @@ __device__ __forceinline__ void map_quads(float4 (&v)[N], F f) {
 }
 __device__ __forceinline__ float f4c(const float4& v, int c) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); }
 
+// act(x + bias) for the activations outside the ReLU family, shared by the forward epilogues (EpiBiasAct, EpiBiasActHead).
+// Two passes with the pre-activations pinned in registers between them -- a WORKAROUND whose cause is unknown.  Written as one
+// pass, map_quads(act_fwd(act, x + bias)), the split-flavour 128 x 128 EpiBiasAct kernel lost the product term of 16 elements
+// at a time (one dword of one row segment in lanes 48..63 of a wave; output exactly act(bias)) on a few waves of every launch,
+// other waves each launch; the native flavour of the same source and the ReLU-family arms of the same binary never did
+// (tests/test_mlp_gpu.py::test_forward_at_128_row_tiles_other_activations has the figures).  Nothing in the one-pass source is
+// wrong, and no single instruction of its code explains a loss that moves between launches: the two-pass form only changes
+// what hipcc generates (the bias adds run first, on the register pairs as the LDS reads deliver them, as in the ReLU-family
+// arms), after which 30 + 30 forwards were clean.  Keep every forward epilogue on this one function.
+template <int N>
+__device__ __forceinline__ void bias_then_act(float4 (&v)[N], const float4& b, int act) {
+    map_quads<N>(v, [&](float x, int c, int) { return x + f4c(b, c); });
+#pragma unroll
+    for (int q = 0; q < N; ++q) asm volatile("" : "+v"(v[q].x), "+v"(v[q].y), "+v"(v[q].z), "+v"(v[q].w));
+    map_quads<N>(v, [&](float z, int, int) { return act_fwd(act, z); });
+}
+
 struct EpiStore {  // C = acc
     static constexpr bool kDrop = false;
     static constexpr bool kColSum = false;
@@ -126,7 +143,7 @@ struct EpiBiasAct {  // H = dropout(act(acc + bias[col]))
             case DCV_ACT_LEAKY_RELU: map_quads<N>(v, [&](float x, int c, int) { const float z = x + f4c(b, c); return z > 0.f ? z : 0.01f * z; }); break;
             case DCV_ACT_RELU: map_quads<N>(v, [&](float x, int c, int) { const float z = x + f4c(b, c); return z > 0.f ? z : 0.f; }); break;
             case DCV_ACT_NONE: map_quads<N>(v, [&](float x, int c, int) { return x + f4c(b, c); }); break;
-            default: map_quads<N>(v, [&](float x, int c, int) { return act_fwd(act, x + f4c(b, c)); }); break;
+            default: bias_then_act<N>(v, b, act); break;
         }
     }
     __device__ __forceinline__ float* out_ptr(int, int64_t r, int64_t c) const { return C + r * ldc + c; }
@@ -199,7 +216,7 @@ struct EpiBiasActHead {
             case DCV_ACT_LEAKY_RELU: map_quads<N>(v, [&](float x, int c, int) { const float z = x + f4c(b, c); return z > 0.f ? z : 0.01f * z; }); break;
             case DCV_ACT_RELU: map_quads<N>(v, [&](float x, int c, int) { const float z = x + f4c(b, c); return z > 0.f ? z : 0.f; }); break;
             case DCV_ACT_NONE: map_quads<N>(v, [&](float x, int c, int) { return x + f4c(b, c); }); break;
-            default: map_quads<N>(v, [&](float x, int c, int) { return act_fwd(act, x + f4c(b, c)); }); break;
+            default: bias_then_act<N>(v, b, act); break;
         }
     }
     // v[q]: columns col..col+3 (nvalid of them in range) of row row0 + q * row_step, after transform()
@@ -447,6 +464,7 @@ static int launch_gemm_vec(const Operand& A, const Operand& B, int64_t lag2, con
         }
     }
     const int64_t blocks = d.tail_split > 0 ? (int64_t)(d.tiles_m - 1 + d.tail_split) * d.tiles_n : (int64_t)d.tiles_m * d.tiles_n;
+    gemm_log_push(kFormSingle, MODE, Cfg::TM, Cfg::TN, Cfg::SPLIT, VEC, GATHER, splits, d.tail_split);
     if (g_launch_ev.start != nullptr) {   // a profiled launch: the events carry the kernel's own begin / end (common.h)
         const LaunchEvents ev = g_launch_ev;
         g_launch_ev = LaunchEvents{};
@@ -697,6 +715,7 @@ static int launch_gemm_group_mode(const Operand& A, const Operand& B, int64_t M,
         static_assert(lds <= 64 * 1024, "grouped launch: LDS beyond the default limit");
         const GemmDims& d = pl.d;
         const int64_t blocks = d.tail_split > 0 ? (int64_t)(d.tiles_m - 1 + d.tail_split) * d.tiles_n : (int64_t)d.tiles_m * d.tiles_n;
+        gemm_log_push(kFormGroup, kNT, Cfg::TM, Cfg::TN, Cfg::SPLIT, true, pl.gather, 1, d.tail_split);
         if (pl.gather)
             hipLaunchKernelGGL((gemm_group_kernel<Cfg, true, true, Epi>), dim3((unsigned)blocks, (unsigned)members), dim3(256), lds, s, A, B, d, epi, g);
         else

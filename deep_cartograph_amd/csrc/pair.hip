@@ -22,6 +22,8 @@ static int launch_pair_cfg(const Operand& A1, const Operand& B1, int64_t M1, int
     constexpr size_t l1 = gemm_lds_bytes<Cfg1, 1>(), l2 = gemm_lds_bytes<Cfg2, 1>();
     constexpr size_t lds = l1 > l2 ? l1 : l2;
     auto kern = wgrad_dgrad_kernel<Cfg1, Cfg2>;
+    gemm_log_push(kFormPair, kTN, Cfg1::TM, Cfg1::TN, S, true, false, p1.splits, 0);
+    gemm_log_push(kFormPair, kNN, Cfg2::TM, Cfg2::TN, S, true, false, 1, p2.d.tail_split);
     if (lds > 64 * 1024) {
         static bool attr_set = false;  // per instantiation
         if (!attr_set) {

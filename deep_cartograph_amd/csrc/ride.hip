@@ -49,6 +49,7 @@ static int launch_ride_cfg(const Operand& A, const Operand& B, int64_t M, int64_
         }
     }
     const dim3 grid((unsigned)(blocks1 + qblocks));
+    gemm_log_push(kFormRide, kTN, Cfg::TM, Cfg::TN, Cfg::SPLIT, true, false, p.splits, 0);
     if (g_launch_ev.start != nullptr) {   // a profiled launch: the events carry the kernel's own begin / end (common.h)
         const LaunchEvents ev = g_launch_ev;
         g_launch_ev = LaunchEvents{};

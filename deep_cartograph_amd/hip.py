@@ -6,6 +6,8 @@ otherwise -- there is no CPU path.
 """
 from __future__ import annotations
 
+import collections
+import ctypes as C
 import os
 from typing import Optional, Tuple
 
@@ -295,7 +297,10 @@ def project_linear(X: torch.Tensor, W: torch.Tensor, *, fmean=None, frange=None,
 
 # ------------------------------------------------------------------------------- GEMM block
 def gemm(mode: str, A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
-    """Building block (tests): 'nt' A[M,K].B[N,K]^T, 'nn' A[M,K].B[K,N], 'tn' A[K,M]^T.B[K,N]."""
+    """Building block (tests): 'nt' A[M,K].B[N,K]^T, 'nn' A[M,K].B[K,N], 'tn' A[K,M]^T.B[K,N].  Any row stride, unit column
+    stride.  The tile family follows the extents and the CU count (gemm_log() says which was launched):
+    tests/test_kernels_gpu.py covers the narrow, 64 x 128 and (TN) 64 x 64 tiles, tests/test_gemm_tiles_gpu.py the 128 x 128
+    and 64 x 64 families in every mode."""
     _require_gpu(A, B)
     _check_matrix(A)
     _check_matrix(B)
@@ -326,6 +331,32 @@ def gemm_tn_split(A: torch.Tensor, B: torch.Tensor, k_chunk: int, slab_cap: int)
     check(_lib.load().dcv_gemm_tn_split(_ptr(A), A.stride(0), _ptr(B), B.stride(0), _ptr(slab), slab_cap, M, N, K, int(k_chunk), _stream()),
           "dcv_gemm_tn_split")
     return slab
+
+
+# ------------------------------------------------------------------------------- launch-plan log (test hook)
+GemmLaunch = collections.namedtuple("GemmLaunch", "form mode tm tn split vec gather splits tail_split")
+_GEMM_FORMS = ("single", "group", "pair", "ride")
+_GEMM_MODES = ("nt", "nn", "tn")
+
+
+def gemm_log_reset() -> None:
+    """Forget the product plans recorded so far (dcv_debug_gemm_log_reset)."""
+    _lib.load().dcv_debug_gemm_log_reset()
+
+
+def gemm_log() -> list:
+    """Plans of the block-engine products launched since the last reset, in launch order: GemmLaunch tuples of
+    form ('single' | 'group' | 'pair' | 'ride'), mode ('nt' | 'nn' | 'tn'), tile rows and columns, split flavour, 16-byte
+    loaders, gather-capable kernel form, split-K slabs and tail-tile chunks (0 = tail tile whole).  The log holds 256 entries;
+    a replayed graph records nothing."""
+    cap = 256
+    buf = (C.c_int32 * (9 * cap))()
+    n = min(int(_lib.load().dcv_debug_gemm_log_read(buf, cap)), cap)
+    out = []
+    for i in range(n):
+        e = buf[9 * i:9 * i + 9]
+        out.append(GemmLaunch(_GEMM_FORMS[e[0]], _GEMM_MODES[e[1]], e[2], e[3], bool(e[4]), bool(e[5]), bool(e[6]), e[7], e[8]))
+    return out
 
 
 # ------------------------------------------------------------------------------- arithmetic mode

@@ -644,6 +644,14 @@ int dcv_gemm_f32(int32_t mode, const float* A_d, int64_t lda, const float* B_d, 
  * slabs the buffer holds; a launch that needs more returns DCV_ENOMEM without touching memory. */
 int dcv_gemm_tn_split(const float* A_d, int64_t lda, const float* B_d, int64_t ldb, float* slab_d, int64_t slab_cap,
                       int64_t M, int64_t N, int64_t K, int64_t k_chunk, void* stream);
+/* Test hook: the plans of the block-engine products launched since the last reset, in launch order (a host-side log of fixed
+ * capacity, 256 entries; later ones are dropped).  An entry is 9 int32: launch form (0 single product, 1 grouped NT products,
+ * 2 weight gradient + input gradient in one launch -- two entries, 3 layer-0 weight gradient + reduction), mode (0 NT, 1 NN,
+ * 2 TN), tile rows, tile columns, split (BF16 x 6) flavour, 16-byte loaders, gather-capable kernel form, split-K slabs,
+ * chunks of a contraction-split tail tile (0 = whole).  read copies at most cap entries and returns the number recorded.
+ * A replayed graph launches without the host wrappers and records nothing. */
+void dcv_debug_gemm_log_reset(void);
+int32_t dcv_debug_gemm_log_read(int32_t* out, int32_t cap);
 
 #ifdef __cplusplus
 }

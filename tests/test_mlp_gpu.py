@@ -1,5 +1,6 @@
 """Parity of the HIP MLP engine (Deep-TICA / autoencoder steps, training, inference) against
 the torch-CPU autograd oracle.  Run on the GPU box: python -m pytest tests -m gpu"""
+import functools
 import os
 
 import numpy as np
@@ -138,77 +139,347 @@ def test_deeptica_step_matches_autograd(features, dims, n, lag, batch, gather, m
     print(f"{mode} {dims} batch {batch}: worst gradient deviation from float64 = {worst:.2e} of the largest entry")
 
 
+def ar_features_fast(n, F, seed, k_slow=3):
+    """ar_features' process (same generator, same draws) with the AR(1) recurrence in blocks of 256 rows instead of a Python
+    loop over every row: inside a block z[i] = rho^(i+1) z[-1] + rho^i cumsum(c eta[j] rho^-j)[i], exact up to float64
+    rounding (rho^-256 <= 18 for the shortest time scale)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    T = np.array([2000, 700, 250, 90][:k_slow], dtype=np.float64)
+    rho = np.exp(-1.0 / T)
+    eta = rng.standard_normal((n, k_slow)) * np.sqrt(1 - rho ** 2)
+    eta[0] = 0.0
+    z = np.empty((n, k_slow))
+    prev = np.zeros(k_slow)
+    blk = 256
+    up, down = rho ** np.arange(blk)[:, None], rho ** -np.arange(blk)[:, None]
+    for b0 in range(0, n, blk):
+        m = min(blk, n - b0)
+        z[b0:b0 + m] = up[:m] * (rho * prev + np.cumsum(eta[b0:b0 + m] * down[:m], axis=0))
+        prev = z[b0 + m - 1]
+    A = rng.standard_normal((F, k_slow)) / np.sqrt(k_slow)
+    X = z @ A.T + 0.5 * rng.standard_normal((n, F))
+    X = X * rng.uniform(0.1, 10, F) + rng.uniform(-5, 5, F)
+    return X.astype(np.float32)
+
+
+def step_oracle(x, Ws, bs, hidden_act, patterns, n_t, lag_off, dtype=torch.float64):
+    """One Deep-TICA step on the rows x (the engine's logical order: f_t = f[:n_t], f_lag = f[lag_off:lag_off + n_t]) with
+    plain torch in `dtype`.  leaky_relu: patterns[l] is a boolean slope pattern of hidden layer l to hold fixed (the network
+    is then piecewise linear), or None for the layer's own.  Returns the pre-activations' slope decisions, sum f_t, f_t^T f_t,
+    f_t^T f_lag, the loss and the weight / bias gradients as float64 NumPy arrays."""
+    W = [w.to(dtype).clone().requires_grad_(True) for w in Ws]
+    b = [v.to(dtype).clone().requires_grad_(True) for v in bs]
+    h, own, zs = x.to(dtype), [], []
+    for l in range(len(W) - 1):
+        z = h @ W[l].T + b[l]
+        if hidden_act == "leaky_relu":
+            own.append(z.detach() > 0)
+            zs.append(z.detach())
+            m = own[-1] if patterns is None or patterns[l] is None else patterns[l]
+            h = z * torch.where(m, 1.0, 0.01).to(dtype)
+        else:
+            assert hidden_act == "tanh"
+            h = torch.tanh(z)
+    f = h @ W[-1].T + b[-1]
+    f_t, f_l = f[:n_t], f[lag_off:lag_off + n_t]
+    evals, _, _ = onn.batch_tica(f_t, f_l, 1e-6)
+    loss = onn.deeptica_loss(evals)
+    loss.backward()
+    np64 = lambda t: t.detach().double().numpy()
+    return dict(own=own, z=zs, sum_t=np64(f_t.sum(0)), c00=np64(f_t.T @ f_t), c0t=np64(f_t.T @ f_l), loss=float(loss.detach()),
+                gw=[np64(w.grad) for w in W], gb=[np64(v.grad) for v in b])
+
+
+def check_step_against_float64(mode, dims, batch, lag, row0, gather, row_sharing, *, Xn, weight_seed, hidden_act="leaky_relu",
+                               train_step=False, label=""):
+    """One step of the block engine on `batch` pairs of Xn against float64, kink-aware for leaky-ReLU networks: (i) the
+    engine's slope decisions (sign of its stored activations) may differ from the float64 ones only where the float64
+    pre-activation is within 1e-5 of zero; (ii) given the engine's slope pattern -- the network is then piecewise linear with
+    that pattern fixed -- every gradient tensor, the statistics and the loss must agree with the float64 evaluation to the
+    tolerances of test_deeptica_step_matches_autograd.  train_step: the same batch once more as a one-GPU training step (update
+    fused in), whose gradients are held to the same criterion.  Returns the product plans the engine launched
+    (hip.gemm_log()) for the forward + backward and for the training step."""
+    from deep_cartograph_amd import hip
+
+    L = len(dims) - 1
+    acts = [hidden_act] * (L - 1) + [None]
+    torch.manual_seed(weight_seed)
+    ref = onn.DeepTICAModel(dims, acts, None, None, None, 1e-6)
+    if gather:
+        idx = torch.from_numpy(np.random.Generator(np.random.PCG64(weight_seed)).permutation(Xn.shape[0] - lag)[:batch].astype(np.int64))
+        kw = dict(idx=idx.cuda())
+    else:
+        idx = torch.arange(row0, row0 + batch)
+        kw = dict(row0=row0, batch=batch)
+    shared = not gather and row_sharing
+    rows = torch.arange(row0, row0 + batch + lag) if shared else torch.cat([idx, idx + lag])
+    R, lag_off = int(rows.numel()), (lag if shared else batch)
+    prev = hip.get_gemm_mode()
+    hip.set_gemm_mode(mode)
+    logs, g_step = {}, None
+    try:
+        eng = hip.Mlp("deep_tica", dims, acts, max_batch=batch, lag=lag, tica_reg=1e-6)
+        push_params(eng, linears_of(ref.nn))
+        eng.set_row_sharing(row_sharing)
+        Xd = torch.from_numpy(Xn).cuda()
+        eng.reset_log(4)
+        hip.gemm_log_reset()
+        eng.forward(Xd, **kw)
+        stats = eng.stats_view().cpu().numpy()
+        H = [eng.layer_output(l, R).cpu().numpy() for l in range(L - 1)] if hidden_act == "leaky_relu" else []
+        eng.backward(Xd, **kw)
+        g = eng.grads_view().cpu().numpy()
+        rec = eng.read_log()[0]
+        assert eng.last_path() == 0, eng.last_path()
+        logs["step"] = hip.gemm_log()
+        if train_step:
+            hip.gemm_log_reset()
+            eng.train_step(Xd, **kw)
+            g_step = eng.grads_view().cpu().numpy()
+            rec_step = eng.read_log()[1]
+            assert eng.last_path() == 0, eng.last_path()
+            logs["train_step"] = hip.gemm_log()
+            logs["ride"] = eng.last_ride()
+        offsets = list(eng.offsets)
+        eng.close()
+    finally:
+        hip.set_gemm_mode(prev)
+    print(f"{label} {mode}: product plans {[tuple(e) for e in logs['step']]}" + (f"; training step {[tuple(e) for e in logs['train_step']]}" if train_step else ""))
+    Ws = [l.weight.detach() for l in linears_of(ref.nn)]
+    bs = [l.bias.detach() for l in linears_of(ref.nn)]
+    x = torch.from_numpy(Xn)[rows]
+    patterns = [torch.from_numpy(h > 0) for h in H] if hidden_act == "leaky_relu" else None
+    o = step_oracle(x, Ws, bs, hidden_act, patterns, batch, lag_off)
+    flips = []
+    for l in range(len(H)):
+        differ = patterns[l] != o["own"][l]
+        flips.append(int(differ.sum()))
+        if differ.any():   # (i): only units within float32 rounding of the kink
+            assert float(o["z"][l].abs()[differ].max()) < 1e-5, f"layer {l}: slope decision differs away from the kink"
+    d = dims[-1]
+    np.testing.assert_allclose(stats[:d], o["sum_t"], rtol=1e-5, atol=1e-4)
+    np.testing.assert_allclose(stats[2 * d:2 * d + d * d].reshape(d, d), o["c00"], rtol=2e-5, atol=2e-5)
+    np.testing.assert_allclose(stats[2 * d + d * d:].reshape(d, d), o["c0t"], rtol=2e-5, atol=2e-5)
+    loss = o["loss"]
+    print(f"{label} {mode}: loss deviation {abs(rec[0] - loss) / max(1.0, abs(loss)):.2e}")
+    assert abs(rec[0] - loss) < 1e-5 * max(1.0, abs(loss))
+    if train_step:
+        assert abs(rec_step[0] - loss) < 1e-5 * max(1.0, abs(loss))
+    for what, gv in (("", g), (" (training step)", g_step)):
+        if gv is None:
+            continue
+        dev = {}
+        for l in range(L):
+            wo, bo = offsets[l]
+            gw, gb = o["gw"][l], o["gb"][l]
+            dev[f"layer {l} weight"] = rel_err(gv[wo:wo + gw.size].reshape(gw.shape), gw)
+            if l < L - 1:
+                dev[f"layer {l} bias"] = rel_err(gv[bo:bo + gb.size], gb)
+        last_bias = float(np.max(np.abs(gv[offsets[L - 1][1]:offsets[L - 1][1] + dims[-1]])))
+        print(f"{label} {mode}{what}: slope decisions differing from float64 (all within 1e-5 of the kink): {flips}; gradient deviations "
+              f"from float64 given the slope pattern, of the largest entry: { {k: '%.2e' % v for k, v in dev.items()} }; last bias {last_bias:.2e}")
+        for k, v in dev.items():
+            assert v < 2e-5, f"{k}{what}: {v:.2e}"
+        # the loss is invariant to a constant shift of the outputs (TICA removes the mean), so the exact gradient of the last
+        # bias is 0: the engine holds float32 rounding noise only
+        assert last_bias < 2e-5 * max(1.0, np.max(np.abs(o["gw"][L - 1]))), "last bias" + what
+    return logs
+
+
 @pytest.mark.parametrize("mode", ["split", "native"])
 def test_contract_batch_leaky_relu_step_kink_aware(mode):
     """The bench's own configuration -- 512-256-128-4, leaky-ReLU, 8192 contiguous pairs + lag 10 -- against float64.
     Among the three million hidden units of such a batch a few pre-activations sit within float32 rounding of the kink,
     and one flipped slope (1 vs 0.01) moves a gradient entry by 1e-4 of the largest one in ANY float32 implementation.
-    Kink-aware criterion: (i) the engine's slope decisions (sign of its stored activations) may differ from the float64
-    ones only where the float64 pre-activation is within 1e-5 of zero; (ii) given the engine's slope pattern -- the
-    network is then piecewise linear with that pattern fixed -- every gradient tensor, the statistics and the loss must
-    agree with the float64 evaluation to the tolerances of test_deeptica_step_matches_autograd."""
+    Kink-aware criterion: see check_step_against_float64."""
+    Xn, _, _ = normalized(ar_features(8300, 512, 31))
+    check_step_against_float64(mode, [512, 256, 128, 4], 8192, 10, 7, False, True, Xn=Xn, weight_seed=6, label="contract batch, leaky-ReLU")
+
+
+@functools.lru_cache(maxsize=None)
+def big_features(n, F):
+    """Normalised AR(1) features of the 128-row-tile cases, generated once per shape and shared (never written to)."""
+    return normalized(ar_features_fast(n, F, 41))[0]
+
+
+def _ncu():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+# Whole-step float64 oracle where the row-parallel products take 128 x 128 tiles: from 128 * 2 * CUs / column tiles rows up,
+# i.e. more rows than any other oracle test gathers.  Shapes follow the CU count; on 256 CUs: 32 878 shared rows = 257 row
+# tiles (cases a, b, d), 65 510 rows = 512 row tiles of a one-column-tile layer (c), 2 x 16 500 gathered rows (e), two halves
+# of 16 450 rows (f); and 16 310 rows (g: the ride launch, see there).  name -> (dims, hidden activation, batch, gather, row sharing, training step too)
+def _big_case(name):
+    n = _ncu()
+    return {
+        # layer 0 NT 128 x 128 with the contraction-split tail tile (257 x 2 workgroups, K = 512), sign-mask store and its
+        # read-back by the 128 x 128 NN input gradient (side-operand prefetch); layer 1 at 64 x 128 with the fused head;
+        # layer-0 weight gradient TN 128 x 128 on its own.  NOT here: the 128 x 128 / 128 x 128 pair (layer 1's 128 x 256 weight
+        # gradient takes 64 x 64 tiles at this row count, so its two products launch apart: cases b, e have the pair) and the
+        # ride launch (case g)
+        "a": ([512, 256, 128, 4], "leaky_relu", 128 * n + 100, False, True, False),
+        # both hidden forward products 128 x 128 with the tail cut at K = 256; unfused narrow head; NN 128 x 128 with K = 3
+        # (scalar loaders, gather-capable kernel form); weight + input gradient of layer 1 as one 128 x 128 / 128 x 128 launch
+        "b": ([256, 256, 160, 3], "tanh", 128 * n + 100, False, True, False),
+        # the fused head on a 128 x 128 tile (one column tile: 2 * CUs row tiles of 128 rows), head backward
+        "c": ([64, 128, 4], "leaky_relu", 256 * n - 36, False, True, False),
+        # layer 1: input gradient 128 wide (64 x 128 tiles), weight gradient 512 x 128 in 128 x 128 tiles: one launch of
+        # mixed families (a 256-wide layer's weight gradient takes 64 x 64 tiles at this row count: 2 tiles x 64 chunks)
+        "d": ([96, 128, 512, 3], "leaky_relu", 128 * n + 100, False, True, False),
+        # case b through a random int64 index: the gathering loaders at 128 x 128 (NT layer 0, TN layer-0 weight gradient)
+        # gathered rows are not wrapped by the weight gradient + reduction launch: as a training step too, which must end on
+        # the single reduction (no ride) with the layer-0 weight gradient launched alone
+        "e": ([256, 256, 160, 3], "tanh", 64 * n + 116, True, True, True),
+        # case a as two halves: the x_t / x_lag seam inside a 128-row tile and inside a weight-gradient chunk
+        "f": ([512, 256, 128, 4], "leaky_relu", 64 * n + 66, False, False, False),
+        # The layer-0 weight gradient + reduction launch at 128 x 128 (test_step_chain_gpu.py's big_tiles shape).  It needs the
+        # flat-grid reduction -- at most 512 partials per weight -- and the head's backward leaves one partial per 32 rows, so it
+        # ends at 16 384 rows, while the 256 x 512 weight gradient takes 128 x 128 tiles from 64 * CUs - 255 rows: a window below
+        # every case above, where the forward products take 64 x 64 tiles.  64 * CUs - 74 rows.  So the 128 x 128 ride launch
+        # is only ever checked next to 64 x 64 forwards, and no whole step above 32 768 pairs rides: none can.
+        "g": ([512, 256, 128, 4], "leaky_relu", 64 * n - 84, False, True, True),
+    }[name]
+
+
+def _has(log, **want):
+    """an entry of hip.gemm_log() with these fields; a callable value is a predicate on the field"""
+    hit = lambda e: all(v(getattr(e, k)) if callable(v) else getattr(e, k) == v for k, v in want.items())
+    return any(hit(e) for e in log)
+
+
+@pytest.mark.parametrize("mode", ["split", "native"])
+@pytest.mark.parametrize("case", ["a", "b", "c", "d", "e", "f", "g"])
+def test_step_at_128_row_tiles_kink_aware(case, mode):
+    """check_step_against_float64 at the batch sizes where the block engine takes its 128 x 128 tile family, with the launched
+    plans asserted from hip.gemm_log() (see _big_case for what each case reaches).  Tolerances: those of the contract-batch test;
+    the float32 torch-CPU oracle's own deviation from float64 on these cases (slope pattern fixed) is at most 1.5e-6 per gradient
+    tensor, 4.8e-7 on the loss and 4.0e-6 on the statistics, so 2e-5 / 1e-5 stand.
+    MEASURED on MI355X (256 CUs), both flavours, cases a, c, d, f, g: worst gradient deviation 7.5e-7 of the largest entry
+    (case f, layer-0 weights), loss 3.2e-8, at most 2 slope decisions differing from float64, all within 1e-5 of the kink.
+    Cases b and e (tanh): gradients 3.7e-7, loss 1.4e-8 (native).  Their split cases failed on sum f_t (1.9e-4 and 1.4e-3
+    relative) until the defect described in test_forward_at_128_row_tiles_other_activations was fixed."""
+    dims, act, batch, gather, sharing, train_step = _big_case(case)
+    lag, row0 = 10, 7
+    n = 2 * batch if gather else batch + lag + row0 + 5
+    logs = check_step_against_float64(mode, dims, batch, lag, row0, gather, sharing, Xn=big_features(n, dims[0]), weight_seed=6,
+                                      hidden_act=act, train_step=train_step, label=f"128-row tiles, case {case}")
+    log = logs["step"]
+    assert all(e.split == (mode == "split") for e in log), log
+    big = dict(tm=128, tn=128)
+    cut = lambda t: t >= 2
+    if case == "a":
+        assert _has(log, form="single", mode="nt", vec=True, gather=False, tail_split=cut, **big), log
+        assert _has(log, form="single", mode="nt", tm=64, tn=128), log
+        assert _has(log, mode="nn", vec=True, **big), log
+        assert _has(log, form="single", mode="tn", splits=cut, **big), log
+    elif case == "b":
+        assert sum(1 for e in log if e.mode == "nt" and (e.tm, e.tn) == (128, 128) and e.tail_split >= 2 and e.vec) == 2, log
+        assert _has(log, mode="nt", tn=32), log
+        assert _has(log, form="single", mode="nn", vec=False, gather=True, **big), log
+        assert _has(log, form="pair", mode="tn", splits=cut, **big) and _has(log, form="pair", mode="nn", **big), log
+        assert _has(log, form="single", mode="tn", splits=cut, **big), log
+    elif case == "c":
+        assert log[0].mode == "nt" and (log[0].tm, log[0].tn) == (128, 128) and log[0].vec, log
+        assert sum(1 for e in log if e.mode == "nt") == 1, log   # the head rode in layer 0's epilogue
+        assert _has(log, form="single", mode="tn", splits=cut, **big), log
+    elif case == "d":
+        assert _has(log, form="single", mode="nt", tm=64, tn=128), log
+        assert _has(log, form="single", mode="nt", **big), log
+        assert _has(log, form="pair", mode="tn", splits=cut, **big) and _has(log, form="pair", mode="nn", tm=64, tn=128), log
+    elif case == "e":
+        assert _has(log, form="single", mode="nt", vec=True, gather=True, **big), log
+        assert _has(log, form="single", mode="tn", vec=True, gather=True, splits=cut, **big), log
+        assert _has(log, form="pair", mode="tn", **big) and _has(log, form="pair", mode="nn", **big), log
+        step = logs["train_step"]
+        assert all(e.split == (mode == "split") for e in step), step
+        assert logs["ride"] == 0 and not _has(step, form="ride"), (logs["ride"], step)
+        assert _has(step, form="single", mode="tn", vec=True, gather=True, splits=cut, **big), step
+    elif case == "f":
+        assert _has(log, form="single", mode="nt", vec=True, gather=False, **big), log
+        assert _has(log, mode="nn", vec=True, **big), log
+        assert _has(log, form="single", mode="tn", splits=cut, **big), log
+    else:
+        ride = logs["train_step"]
+        assert all(e.split == (mode == "split") for e in ride), ride
+        assert logs["ride"] > 0 and _has(ride, form="ride", mode="tn", splits=cut, **big), (logs["ride"], ride)
+
+
+def forward_layers_against_float64(case, act, mode):
+    """One forward of the case's network with `act` on its hidden layers; the launch log and, per layer, the engine's output,
+    its float64 value computed from the engine's own input to that layer, and the element-wise bound: the fp32 product bound of
+    test_gemm_random_fp32 on the pre-activation (tanh and elu have slope <= 1) plus 4 ulp of the result for the library
+    function."""
     from deep_cartograph_amd import hip
 
-    dims, lag, batch, row0 = [512, 256, 128, 4], 10, 8192, 7
-    acts = ["leaky_relu", "leaky_relu", None]
-    Xn, _, _ = normalized(ar_features(8300, dims[0], 31))
+    dims, _, batch, _, _, _ = _big_case(case)
+    L = len(dims) - 1
+    lag, row0 = 10, 7
+    R = batch + lag
+    Xn = big_features(batch + lag + row0 + 5, dims[0])
     torch.manual_seed(6)
-    ref = onn.DeepTICAModel(dims, acts, None, None, None, 1e-6)
+    lins = [torch.nn.Linear(dims[i], dims[i + 1]) for i in range(L)]
     prev = hip.get_gemm_mode()
     hip.set_gemm_mode(mode)
-    R = batch + lag
     try:
-        eng = hip.Mlp("deep_tica", dims, acts, max_batch=batch, lag=lag, tica_reg=1e-6)
-        push_params(eng, linears_of(ref.nn))
-        Xd = torch.from_numpy(Xn).cuda()
+        eng = hip.Mlp("deep_tica", dims, [act] * (L - 1) + [None], max_batch=batch, lag=lag, tica_reg=1e-6)
+        push_params(eng, lins)
         eng.reset_log(2)
-        eng.forward(Xd, row0=row0, batch=batch)
-        stats = eng.stats_view().cpu().numpy()
-        H = [eng.layer_output(l, R).cpu().numpy() for l in (0, 1)]
-        eng.backward(Xd, row0=row0, batch=batch)
-        g = eng.grads_view().cpu().numpy()
-        rec = eng.read_log()[0]
-        offsets = list(eng.offsets)
+        hip.gemm_log_reset()
+        eng.forward(torch.from_numpy(Xn).cuda(), row0=row0, batch=batch)
+        log = hip.gemm_log()
+        H = [eng.layer_output(l, R).cpu().numpy()[:, :dims[l + 1]] for l in range(L)]
+        assert eng.last_path() == 0
         eng.close()
     finally:
         hip.set_gemm_mode(prev)
-    W = [l.weight.detach().double().clone().requires_grad_(True) for l in linears_of(ref.nn)]
-    b = [l.bias.detach().double().clone().requires_grad_(True) for l in linears_of(ref.nn)]
-    x = torch.from_numpy(Xn[row0:row0 + R]).double()
-    h, flips = x, []
-    for l in (0, 1):
-        z = h @ W[l].T + b[l]
-        m_eng = torch.from_numpy(H[l] > 0)
-        differ = m_eng != (z.detach() > 0)
-        flips.append(int(differ.sum()))
-        if differ.any():   # (i): only units within float32 rounding of the kink
-            assert float(z.detach().abs()[differ].max()) < 1e-5, f"layer {l}: slope decision differs away from the kink"
-        h = z * torch.where(m_eng, 1.0, 0.01).double()   # (ii): the engine's slope pattern, fixed
-    f = h @ W[2].T + b[2]
-    f_t, f_l = f[:batch], f[lag:lag + batch]
-    evals, _, _ = onn.batch_tica(f_t, f_l, 1e-6)
-    loss = onn.deeptica_loss(evals)
-    loss.backward()
-    d = dims[-1]
-    np.testing.assert_allclose(stats[:d], f_t.detach().sum(0).numpy(), rtol=1e-5, atol=1e-4)
-    np.testing.assert_allclose(stats[2 * d:2 * d + d * d].reshape(d, d), (f_t.T @ f_t).detach().numpy(), rtol=2e-5, atol=2e-5)
-    np.testing.assert_allclose(stats[2 * d + d * d:].reshape(d, d), (f_t.T @ f_l).detach().numpy(), rtol=2e-5, atol=2e-5)
-    assert abs(rec[0] - float(loss)) < 1e-5 * max(1.0, abs(float(loss)))
-    worst = 0.0
-    for l in range(3):
-        wo, bo = offsets[l]
-        gw, gb = W[l].grad.numpy(), b[l].grad.numpy()
-        ew = rel_err(g[wo:wo + gw.size].reshape(gw.shape), gw)
-        worst = max(worst, ew)
-        assert ew < 2e-5, f"layer {l} weight: {ew:.2e}"
-        if l < 2:
-            eb = rel_err(g[bo:bo + gb.size], gb)
-            worst = max(worst, eb)
-            assert eb < 2e-5, f"layer {l} bias: {eb:.2e}"
-        else:
-            assert np.max(np.abs(g[bo:bo + gb.size])) < 2e-5 * max(1.0, np.max(np.abs(gw))), "last bias"
-    print(f"{mode} contract batch, leaky-ReLU: slope decisions differing from float64 (all within 1e-5 of the kink): {flips}; "
-          f"worst gradient deviation from float64 given the slope pattern = {worst:.2e} of the largest entry")
+    out, x = [], Xn[row0:row0 + R].astype(np.float64)
+    for l in range(L):
+        W, b = lins[l].weight.detach().double().numpy(), lins[l].bias.detach().double().numpy()
+        z = x @ W.T + b
+        ref = z if l == L - 1 else (np.tanh(z) if act == "tanh" else np.where(z > 0, z, np.expm1(np.minimum(z, 0))))
+        bound = 4e-7 * (np.abs(x) @ np.abs(W).T + np.abs(b)) + 1e-6 + 4 * 2.0 ** -24 * np.abs(ref)
+        out.append((H[l], ref, bound))
+        x = H[l].astype(np.float64)
+    return log, out
+
+
+def assert_within(name, got, ref, bound):
+    err = np.abs(got - ref)
+    print(f"{name}: worst error / bound {np.max(err / bound):.3g}, elements beyond the bound {int((err > bound).sum())}")
+    assert np.all(err <= bound), f"{name}: {int((err > bound).sum())} elements beyond the bound, worst {err.max():.3e}"
+
+
+@pytest.mark.parametrize("mode", ["split", "native"])
+@pytest.mark.parametrize("act", ["tanh", "elu"])
+def test_forward_at_128_row_tiles_other_activations(act, mode):
+    """Layer 0 of case b alone (256 -> 256 on 128 * CUs + 110 rows: NT, 128 x 128 tiles, EpiBiasAct) with an activation outside
+    the ReLU family, element by element against float64 (bound: forward_layers_against_float64).
+    This test found a defect whose cause is unknown: while the epilogues applied act(x + bias) in one pass (gemm_kernels.h:
+    bias_then_act has the two-pass form they use now), the split flavour lost 16 .. 192 elements per forward here (six forwards
+    each with tanh, elu, softplus; also with plain stores, DCV_WT=0): always 16 at a time -- one row, every fourth column of
+    the upper half of a column tile, i.e. the third float of the first row segment an epilogue thread handles, in lanes 48..63
+    of its wave -- other elements each launch, their value exactly act(bias): the product term was lost.  The native flavour
+    and leaky-ReLU / ReLU / linear layers were never affected.
+    MEASURED on MI355X (256 CUs) since: 0 elements beyond the bound in 30 split forwards; worst error 0.29 of the bound (native)."""
+    log, layers = forward_layers_against_float64("b", act, mode)
+    assert (log[0].mode, log[0].tm, log[0].tn, log[0].split, log[0].vec) == ("nt", 128, 128, mode == "split", True), log
+    assert_within(f"{act} {mode} layer 0", *layers[0])
+
+
+@pytest.mark.parametrize("mode", ["split", "native"])
+@pytest.mark.parametrize("act", ["tanh", "elu"])
+def test_fused_head_forward_at_128_row_tiles_other_activations(act, mode):
+    """The same for the fused head on a 128 x 128 tile (case c's 64 -> 128 -> 4 on 256 * CUs - 26 rows: EpiBiasActHead<4>, one
+    NT launch for both layers): the hidden activations H it stores, and the head's outputs given those H.
+    MEASURED on MI355X (256 CUs): 0 elements beyond either bound in 4 forwards per activation and flavour, with the one-pass
+    form of the epilogue as with bias_then_act: the loss seen in EpiBiasAct never showed here.  As its cause is unknown, that
+    is no proof of absence; the epilogue shares bias_then_act and this test watches it."""
+    log, layers = forward_layers_against_float64("c", act, mode)
+    assert (log[0].mode, log[0].tm, log[0].tn, log[0].split, log[0].vec) == ("nt", 128, 128, mode == "split", True), log
+    assert sum(1 for e in log if e.mode == "nt") == 1, log   # the head rode in layer 0's epilogue
+    assert_within(f"{act} {mode} hidden layer", *layers[0])
+    assert_within(f"{act} {mode} head", *layers[1])
 
 
 def test_contract_batch_step_is_reproducible():
