@@ -6,36 +6,34 @@
 //            query, the points streamed through LDS in tiles, a sorted list of the k smallest SQUARED sums per lane in LDS
 //            (entry e of lane t at [e * 64 + t]: no bank conflicts; the LDS of a launch is sized by k and d), one correctly
 //            rounded sqrt of the k-th at the end.
-//            The squares are added in coordinate order, every product and sum rounded on its own (no fma), as
-//            linkage_pdist_kernel does it.
+//            The squares are added in coordinate order, every product and sum rounded on its own (no fma):
+//            sqdist_exact (points.h), as in linkage.hip's distance matrix.
 //   step     one launch per step of Prim's algorithm over the implicit mutual-reachability graph
 //            mrd(c, j) = max(core[c], core[j], dist(c, j)).  Every workgroup owns a contiguous slice of the points and is
 //            the only one to read or write that slice's running minimum, source and in-tree flag (the owner of the current
 //            node c marks it).  It lowers the minima against c with a strict '<', reduces its slice to the lexicographic
-//            minimum of (value, index), and hands (value, index, source) over (handoff.h).  The last workgroup to arrive
-//            combines the partials, appends the edge and names the next current node in the state.
+//            minimum of (value, index), and hands (value, index, source) over (ticketed_argmin, points.h).  The last workgroup
+//            to arrive combines the partials, appends the edge and names the next current node in the state.
 //
 // Nothing waits on another workgroup: the host enqueues exactly n - 1 steps in blocks and reads a few words of state
 // between blocks; steps enqueued after an error return at once.  The state is O(n): no n x n matrix.
 #include <cfloat>
 #include <vector>
 
-#include "common.h"
-#include "handoff.h"
+#include "points.h"
 
 namespace dcv {
 
-constexpr int kHdMaxD = 16;
+constexpr int kHdMaxD = kPtMaxD;
 constexpr int kHdMaxK = 64;                  // min_samples the core-distance kernel holds per lane
 constexpr int kCoreLanes = 64;               // queries per workgroup: one wave
 constexpr int kCoreTile = 128;               // points per LDS tile
-constexpr int kMstThreads = 256;
+constexpr int kMstThreads = kPtThreads;
 constexpr int64_t kHdMaxN = ((int64_t)1 << 31) - 1;   // indices travel as int32 and as exact doubles
 constexpr size_t kCoreWsBytes = 256;         // one status word
 
 __global__ __launch_bounds__(kCoreLanes) void core_distances_kernel(const double* __restrict__ P, int64_t n, int d, int k,
                                                                      double* __restrict__ core, int32_t* __restrict__ status) {
-#pragma clang fp contract(off)
     extern __shared__ double s_core[];          // k * 64 list entries, then a tile of 128 * d coordinates: 48 KB at most
     double* s_list = s_core;
     double* s_pts = s_core + k * kCoreLanes;
@@ -54,15 +52,7 @@ __global__ __launch_bounds__(kCoreLanes) void core_distances_kernel(const double
         for (int x = t; x < cnt * d; x += kCoreLanes) s_pts[x] = P[base * d + x];
         __syncthreads();
         for (int j = 0; j < cnt; ++j) {
-            const double* p = s_pts + j * d;   // the same address in every lane: an LDS broadcast
-            double s = 0.0;
-#pragma unroll
-            for (int c = 0; c < kHdMaxD; ++c)
-                if (c < d) {
-                    const double df = q[c] - p[c];
-                    const double sq = df * df;   // plain operators under the pragma: never one fma
-                    s = s + sq;
-                }
+            const double s = sqdist_exact(q, s_pts + j * d, d);   // the same address in every lane: an LDS broadcast
             if (s < worst) {   // a NaN never enters
                 int e = k - 1;
                 for (; e > 0; --e) {
@@ -106,36 +96,6 @@ __global__ void mst_init_kernel(MstState* __restrict__ st, double* __restrict__ 
     }
 }
 
-// lexicographic minimum of (value, index) with the source riding along; an index < 0 is "no candidate"
-__device__ __forceinline__ void mst_take(double& bd, int& bi, int& bs, double od, int oi, int os) {
-    if (oi >= 0 && (bi < 0 || od < bd || (od == bd && oi < bi))) {
-        bd = od;
-        bi = oi;
-        bs = os;
-    }
-}
-
-__device__ __forceinline__ void mst_block_min(double& bd, int& bi, int& bs, double* s_d, int* s_i, int* s_s) {
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        const double od = __shfl_down(bd, o);
-        const int oi = __shfl_down(bi, o);
-        const int os = __shfl_down(bs, o);
-        mst_take(bd, bi, bs, od, oi, os);
-    }
-    const int w = threadIdx.x / kWave;
-    if (threadIdx.x % kWave == 0) {
-        s_d[w] = bd;
-        s_i[w] = bi;
-        s_s[w] = bs;
-    }
-    __syncthreads();
-    bd = s_d[0];
-    bi = s_i[0];
-    bs = s_s[0];
-    for (int k = 1; k < kMstThreads / kWave; ++k) mst_take(bd, bi, bs, s_d[k], s_i[k], s_s[k]);
-    __syncthreads();
-}
-
 // One step of Prim's algorithm from the current node c, as sklearn's mst_from_data_matrix runs it: for every j outside
 // the tree, m = max(core[c], core[j], dist(c, j)); a strictly smaller m replaces min_reach[j] (source c); the candidate
 // of j is its (updated) minimum, and the new node is the lowest index among the candidates of minimal value --
@@ -146,11 +106,7 @@ __global__ __launch_bounds__(kMstThreads) void mst_step_kernel(MstState* __restr
                                                                int32_t* __restrict__ e_src, int32_t* __restrict__ e_dst,
                                                                double* __restrict__ e_w, double* __restrict__ part, int n, int d,
                                                                int per) {
-#pragma clang fp contract(off)
-    __shared__ double s_d[kMstThreads / kWave];
-    __shared__ int s_i[kMstThreads / kWave];
-    __shared__ int s_s[kMstThreads / kWave];
-    __shared__ unsigned s_flag;
+    __shared__ ArgminLds<true> s_min;
     if (st->done | st->error) return;   // uniform over the grid: the state only changes behind every workgroup's ticket
     // what the last arriver needs, read ahead of the ticket by everybody
     const int nedge = st->edges;
@@ -162,22 +118,14 @@ __global__ __launch_bounds__(kMstThreads) void mst_step_kernel(MstState* __restr
 
     const int begin = blockIdx.x * per;
     const int end = n - begin < per ? n : begin + per;   // begin < n: the grid is cdiv(n, per)
-    double bd = DBL_MAX;
-    int bi = -1, bs = -1;
+    Cand<true> best = {DBL_MAX, -1, -1};   // (minimum, node, its source)
     for (int64_t j = begin + (int)threadIdx.x; j < end; j += kMstThreads) {   // upwards within a lane; 64-bit: no wrap near 2^31
         if (in_tree[j]) continue;
         if (j == c) {
             in_tree[j] = 1;
             continue;
         }
-        double s = 0.0;
-#pragma unroll
-        for (int q = 0; q < kHdMaxD; ++q)
-            if (q < d) {
-                const double df = pc[q] - P[j * d + q];
-                const double sq = df * df;
-                s = s + sq;
-            }
+        const double s = sqdist_exact(pc, P + j * d, d);
         double m = cc;
         const double cj = core[j];
         if (cj > m) m = cj;
@@ -191,29 +139,11 @@ __global__ __launch_bounds__(kMstThreads) void mst_step_kernel(MstState* __restr
             min_reach[j] = m;
             source[j] = c;
         }
-        if (mr < bd) {
-            bd = mr;
-            bi = (int)j;
-            bs = sj;
-        }
+        if (mr < best.v) best = {mr, (int)j, sj};
     }
-    mst_block_min(bd, bi, bs, s_d, s_i, s_s);
-    if (threadIdx.x == 0) {
-        handoff_store(part + 3 * blockIdx.x, bd);
-        handoff_store(part + 3 * blockIdx.x + 1, (double)bi);
-        handoff_store(part + 3 * blockIdx.x + 2, (double)bs);
-    }
-    if (!handoff_arrive_last(&st->ticket, gridDim.x, &s_flag)) return;
-
-    double md = DBL_MAX;
-    int mi = -1, ms = -1;
-    if (threadIdx.x < gridDim.x) {   // at most kMstThreads workgroups
-        md = handoff_load(part + 3 * threadIdx.x);
-        mi = (int)handoff_load(part + 3 * threadIdx.x + 1);
-        ms = (int)handoff_load(part + 3 * threadIdx.x + 2);
-    }
-    mst_block_min(md, mi, ms, s_d, s_i, s_s);
-    if (threadIdx.x != 0) return;
+    if (!ticketed_argmin(best, part, &st->ticket, s_min) || threadIdx.x != 0) return;
+    const double md = best.v;
+    const int mi = best.i, ms = best.p;
     if (mi < 0 || nedge >= n - 1) {   // nothing comparable outside the tree: non-finite input; never write past the edges
         st->error = 1;
         return;
@@ -226,30 +156,16 @@ __global__ __launch_bounds__(kMstThreads) void mst_step_kernel(MstState* __restr
     if (nedge + 1 == n - 1) st->done = 1;
 }
 
-struct MstLayout {
-    int per, grid;
-    size_t off_state, off_reach, off_source, off_tree, off_esrc, off_edst, off_ew, off_part, total;
+struct MstLayout {   // the regions in workspace order
+    MstLayout(int64_t n_, int cus) : n((size_t)n_), g(step_grid(n_, kMstThreads, cus)) {}
+    size_t n;
+    StepGrid g;   // one workgroup covers a whole number of passes of its threads
+    Carver c;
+    Region<MstState> state = c.take<MstState>(1);
+    Region<double> reach = c.take<double>(n);
+    Region<int32_t> source = c.take<int32_t>(n), tree = c.take<int32_t>(n), esrc = c.take<int32_t>(n), edst = c.take<int32_t>(n);
+    Region<double> ew = c.take<double>(n), part = c.take<double>(3 * kMstThreads);
 };
-
-static MstLayout mst_layout(int64_t n, int cus) {
-    MstLayout L;
-    // one workgroup per CU at most, each a whole number of passes of its threads; never more than kMstThreads of them
-    // (the last arriver reads one partial per thread)
-    const int cap = cus < kMstThreads ? (cus > 0 ? cus : 1) : kMstThreads;
-    L.per = (int)align_up((size_t)cdiv(n, cap), kMstThreads);
-    L.grid = (int)cdiv(n, L.per);
-    size_t o = 0;
-    L.off_state = o;  o += align_up(sizeof(MstState), 256);
-    L.off_reach = o;  o += align_up((size_t)n * sizeof(double), 256);
-    L.off_source = o; o += align_up((size_t)n * sizeof(int32_t), 256);
-    L.off_tree = o;   o += align_up((size_t)n * sizeof(int32_t), 256);
-    L.off_esrc = o;   o += align_up((size_t)n * sizeof(int32_t), 256);
-    L.off_edst = o;   o += align_up((size_t)n * sizeof(int32_t), 256);
-    L.off_ew = o;     o += align_up((size_t)n * sizeof(double), 256);
-    L.off_part = o;   o += align_up((size_t)3 * kMstThreads * sizeof(double), 256);
-    L.total = o;
-    return L;
-}
 
 }  // namespace dcv
 
@@ -266,10 +182,7 @@ extern "C" int dcv_core_distances(const double* P_d, int64_t n, int32_t d, int32
     DCV_REQUIRE(d >= 1 && d <= kHdMaxD, "dcv_core_distances: d = %d, supported 1..%d", d, kHdMaxD);
     DCV_REQUIRE(k >= 1 && k <= kHdMaxK && k <= n, "dcv_core_distances: k = %d, supported 1..min(n, %d)", k, kHdMaxK);
     DCV_REQUIRE(P_d && core_d, "dcv_core_distances: null points or result");
-    if (!ws_d || ws_bytes < kCoreWsBytes) {
-        set_error("dcv_core_distances: workspace of %zu bytes, %zu needed", ws_bytes, kCoreWsBytes);
-        return DCV_ENOMEM;
-    }
+    DCV_REQUIRE_WORKSPACE("dcv_core_distances", ws_d, ws_bytes, kCoreWsBytes);
     hipStream_t s = as_stream(stream);
     int32_t* status = static_cast<int32_t*>(ws_d);
     DCV_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
@@ -287,7 +200,7 @@ extern "C" int dcv_core_distances(const double* P_d, int64_t n, int32_t d, int32
 extern "C" size_t dcv_mr_mst_workspace(int64_t n, int32_t d) {
     if (n < 2 || n > kHdMaxN || d < 1 || d > kHdMaxD) return 0;
     // no offset depends on the CU count (only `per` does): one size for every device
-    return mst_layout(n, kMstThreads).total;
+    return MstLayout(n, kMstThreads).c.total;
 }
 
 extern "C" int dcv_mr_mst(const double* P_d, int64_t n, int32_t d, const double* core_d, int64_t* src_h, int64_t* dst_h, double* w_h,
@@ -295,22 +208,17 @@ extern "C" int dcv_mr_mst(const double* P_d, int64_t n, int32_t d, const double*
     DCV_REQUIRE(n >= 2 && n <= kHdMaxN, "dcv_mr_mst: n = %lld, supported 2..%lld", (long long)n, (long long)kHdMaxN);
     DCV_REQUIRE(d >= 1 && d <= kHdMaxD, "dcv_mr_mst: d = %d, supported 1..%d", d, kHdMaxD);
     DCV_REQUIRE(P_d && core_d && src_h && dst_h && w_h, "dcv_mr_mst: null points, core distances or result");
-    if (!ws_d || ws_bytes < dcv_mr_mst_workspace(n, d)) {
-        set_error("dcv_mr_mst: workspace of %zu bytes, %zu needed", ws_bytes, dcv_mr_mst_workspace(n, d));
-        return DCV_ENOMEM;
-    }
+    DCV_REQUIRE_WORKSPACE("dcv_mr_mst", ws_d, ws_bytes, dcv_mr_mst_workspace(n, d));
     DCV_REQUIRE((reinterpret_cast<uintptr_t>(ws_d) & 7) == 0, "dcv_mr_mst: workspace not 8-byte aligned");
     hipStream_t s = as_stream(stream);
-    const MstLayout L = mst_layout(n, num_cus());
-    char* w = static_cast<char*>(ws_d);
-    MstState* st = reinterpret_cast<MstState*>(w + L.off_state);
-    double* min_reach = reinterpret_cast<double*>(w + L.off_reach);
-    int32_t* source = reinterpret_cast<int32_t*>(w + L.off_source);
-    int32_t* in_tree = reinterpret_cast<int32_t*>(w + L.off_tree);
-    int32_t* e_src = reinterpret_cast<int32_t*>(w + L.off_esrc);
-    int32_t* e_dst = reinterpret_cast<int32_t*>(w + L.off_edst);
-    double* e_w = reinterpret_cast<double*>(w + L.off_ew);
-    double* part = reinterpret_cast<double*>(w + L.off_part);
+    const MstLayout L(n, num_cus());
+    MstState* st = L.state.in(ws_d);
+    double* min_reach = L.reach.in(ws_d);
+    int32_t* source = L.source.in(ws_d);
+    int32_t* in_tree = L.tree.in(ws_d);
+    int32_t* e_src = L.esrc.in(ws_d);
+    int32_t* e_dst = L.edst.in(ws_d);
+    double* e_w = L.ew.in(ws_d);
 
     hipLaunchKernelGGL(mst_init_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, st, min_reach, source, in_tree, n);
     DCV_CHECK_LAUNCH();
@@ -319,17 +227,13 @@ extern "C" int dcv_mr_mst(const double* P_d, int64_t n, int32_t d, const double*
         int32_t edges, done, error, current;
     } h = {0, 0, 0, 0};
     const int64_t total = n - 1;   // every step records exactly one edge or sets the error word
-    int64_t enqueued = 0;
-    while (!h.done && !h.error && enqueued < total) {
-        const int64_t steps = total - enqueued < 4096 ? total - enqueued : 4096;
-        for (int64_t k = 0; k < steps; ++k)
-            hipLaunchKernelGGL(mst_step_kernel, dim3(L.grid), dim3(kMstThreads), 0, s, st, P_d, core_d, min_reach, source, in_tree, e_src,
-                               e_dst, e_w, part, (int)n, (int)d, L.per);
-        DCV_CHECK_LAUNCH();
-        enqueued += steps;
-        DCV_CHECK_HIP(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
-        DCV_CHECK_HIP(hipStreamSynchronize(s));
-    }
+    const int rc = run_steps(
+        s, st, h, total, [](const auto&, int64_t left) { return left < 4096 ? left : (int64_t)4096; },
+        [&] {
+            hipLaunchKernelGGL(mst_step_kernel, dim3(L.g.grid), dim3(kMstThreads), 0, s, st, P_d, core_d, min_reach, source, in_tree, e_src, e_dst,
+                               e_w, L.part.in(ws_d), (int)n, (int)d, L.g.per);
+        });
+    if (rc) return rc;
     DCV_REQUIRE(h.error == 0 && h.done, "dcv_mr_mst: the tree did not finish (%s; %d of %lld edges): non-finite input?",
                 h.error ? "a step found no candidate" : "steps missing", h.edges, (long long)total);
 

@@ -5,99 +5,24 @@
 // Determinism: every wave owns a private LDS accumulator, waves are combined in wave order,
 // blocks in block order, and each thread walks its points in increasing index order.
 //
-// Layout.  The shared device pieces come first, ONE copy each: block_range (a block's points), load_point (runtime d and
-// <D>), block_sum (the 256-value LDS tree), take_min / wave_min (the (distance, row) minimum), glds_stream (LDS-DMA) and the
-// two point streams reg_stream (registers: two alternating batches, the D == 4 pair path) and ring_stream (per-wave LDS-DMA
-// ring), which both call a per-point f(x, i, old).  The kernels pass what differs between them as template parameters and
+// Layout.  What the other float64 point kernels use as well lives in points.h: point_blocks (the grid), block_range (a
+// block's points), load_point (runtime d and <D>), block_sum (the 256-value LDS tree), sum_blocks (the final sum over the
+// blocks, defined here) and take_min / wave_min (the (distance, row) minimum).  The shared device pieces of this file come
+// first, ONE copy each: glds_stream (LDS-DMA) and the two point streams reg_stream (registers: two alternating batches, the
+// D == 4 pair path) and ring_stream (per-wave LDS-DMA ring), which both call a per-point f(x, i, old).  The kernels pass what differs between them as template parameters and
 // callables.  In the C-ABI at the end a runtime d / k becomes an instantiation through for_value, and every entry reads
 // "choose kernel, blocks and LDS; launch; final".
 #include "gemm_kernels.h"   // butterfly_sum
+#include "points.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace dcv {
 
-constexpr int kKmThreads = 256;
-constexpr int kKmMaxD = 16;
+constexpr int kKmThreads = kPtThreads;
+constexpr int kKmMaxD = kPtMaxD;
 constexpr int kKmMaxK = 64;
-constexpr int kKmMaxBlocks = 1024;
-
-static int km_blocks(int64_t n) {
-    int64_t b = cdiv(n, (int64_t)kKmThreads * 4);
-    const int64_t cap = (int64_t)num_cus() * 4;
-    if (b > cap) b = cap;
-    if (b > kKmMaxBlocks) b = kKmMaxBlocks;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-__device__ __forceinline__ void load_point(const double* __restrict__ P, int64_t i, int d, double* x) {
-    const double* p = P + i * d;
-    if ((d & 1) == 0) {
-#pragma unroll
-        for (int c = 0; c < kKmMaxD; c += 2) {
-            if (c < d) {
-                const double2 v = *reinterpret_cast<const double2*>(p + c);
-                x[c] = v.x;
-                x[c + 1] = v.y;
-            }
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < kKmMaxD; ++c)
-            if (c < d) x[c] = p[c];
-    }
-}
-template <int D>
-__device__ __forceinline__ void load_point(const double* __restrict__ P, int64_t i, double (&x)[D]) {
-    const double* p = P + i * D;
-    if constexpr (D % 2 == 0) {
-#pragma unroll
-        for (int c = 0; c < D; c += 2) {
-            const double2 v = *reinterpret_cast<const double2*>(p + c);
-            x[c] = v.x;
-            x[c + 1] = v.y;
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < D; ++c) x[c] = p[c];
-    }
-}
-
-// the block's contiguous range of points [begin, end)
-struct Range {
-    int64_t begin, end;
-};
-__device__ __forceinline__ Range block_range(int64_t n) {
-    const int64_t per_block = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t begin = (int64_t)blockIdx.x * per_block;
-    return {begin, begin + per_block < n ? begin + per_block : n};
-}
-
-// s_red[0] = the sum of the block's 256 values v by a fixed LDS tree (pairs 128 apart, then 64, ...), valid after the call
-__device__ __forceinline__ void block_sum(double v, double (&s_red)[kKmThreads], int t) {
-    s_red[t] = v;
-    __syncthreads();
-    for (int o = kKmThreads / 2; o > 0; o >>= 1) {
-        if (t < o) s_red[t] += s_red[t + o];
-        __syncthreads();
-    }
-}
-// lexicographic (distance, row) minimum: the smaller distance wins, ties go to the smaller row
-__device__ __forceinline__ void take_min(double& best, int64_t& besti, double v, int64_t i) {
-    if (v < best || (v == best && i < besti)) {
-        best = v;
-        besti = i;
-    }
-}
-__device__ __forceinline__ void wave_min(double& best, int64_t& besti) {   // lane 0 ends up with the wave's minimum
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double v2 = __shfl_down(best, off, 64);
-        const int64_t i2 = __shfl_down(besti, off, 64);
-        take_min(best, besti, v2, i2);
-    }
-}
+constexpr int kKmMaxBlocks = kPtMaxBlocks;
 
 // ---- D = 4 float64 coordinates = 32 bytes per point.  A lane that reads its own point issues two 16-byte loads at a
 // 32-byte lane stride: every wave-instruction touches 2 KB of lines and uses half of them (measured 3.9 - 4.2 TB/s where the
@@ -485,16 +410,17 @@ __global__ __launch_bounds__(kKmThreads, (KMAX * (D + 1) > 48 ? 1 : 2)) void kme
         my_part[i] = ((s_red[0][src] + s_red[1][src]) + s_red[2][src]) + s_red[3][src];
     }
 }
-// acc[i] = sum over the blocks of part[b][i]: one workgroup per output, its threads take b = t, t + 256, ... (all loads
-// in flight at once; one thread walking 1024 partials with dependent loads cost 0.4 ms -- most of the pass) and a fixed
-// LDS tree adds them up.
-__global__ __launch_bounds__(256) void kmeans_final_kernel(const double* __restrict__ part, int nblocks, int width, double* __restrict__ acc) {
-    __shared__ double s_red[256];
+// points.h: sum_blocks
+__global__ __launch_bounds__(kPtThreads) void sum_blocks_kernel(const double* __restrict__ part, int nblocks, int width, double* __restrict__ acc) {
+    __shared__ double s_red[kPtThreads];
     const int i = blockIdx.x, t = threadIdx.x;
     double s = 0.0;
-    for (int b = t; b < nblocks; b += 256) s += part[(int64_t)b * width + i];
+    for (int b = t; b < nblocks; b += kPtThreads) s += part[(int64_t)b * width + i];
     block_sum(s, s_red, t);
     if (t == 0) acc[i] = s_red[0];
+}
+void sum_blocks(const double* part, int nblocks, int width, double* acc, hipStream_t s) {
+    hipLaunchKernelGGL(sum_blocks_kernel, dim3((unsigned)width), dim3(kPtThreads), 0, s, part, nblocks, width, acc);
 }
 
 // ------------------------------------------------------------------ k-means++ seeding passes
@@ -896,7 +822,7 @@ extern "C" int dcv_kmeans_step(const double* P_d, int64_t n, int32_t d, const do
     DCV_REQUIRE(d >= 1 && d <= kKmMaxD && k >= 1 && k <= kKmMaxK, "dcv_kmeans_step: d=%d (1..16) k=%d (1..64) unsupported", d, k);
     DCV_REQUIRE(ws_d && ws_bytes >= dcv_kmeans_workspace(n, d, k), "dcv_kmeans_step: workspace too small");
     hipStream_t s = as_stream(stream);
-    int nb = km_blocks(n);
+    int nb = point_blocks(n);
     const int W = k * d + k;
     double* part = static_cast<double*>(ws_d);
     static const bool no_reg = env_starts_with("DCV_KMEANS_ATOMIC", '1');   // diagnostic: general kernel
@@ -917,7 +843,7 @@ extern "C" int dcv_kmeans_step(const double* P_d, int64_t n, int32_t d, const do
         hipLaunchKernelGGL(kmeans_step_kernel, dim3(nb), dim3(kKmThreads), lds, s, P_d, n, d, offset_d, centers_d, k, labels_d, mindist_d, part);
     }
     DCV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(kmeans_final_kernel, dim3(W + 2), dim3(256), 0, s, part, nb, W + 2, acc_d);
+    sum_blocks(part, nb, W + 2, acc_d, s);
     DCV_CHECK_LAUNCH();
     return DCV_OK;
 }
@@ -935,7 +861,7 @@ extern "C" int dcv_nearest_rows(const double* P_d, int64_t n, int32_t d, const d
     DCV_REQUIRE(d >= 1 && d <= kKmMaxD && k >= 1 && k <= 1024, "dcv_nearest_rows: d=%d k=%d unsupported", d, k);
     DCV_REQUIRE(ws_d && ws_bytes >= dcv_nearest_rows_workspace(n, d, k), "dcv_nearest_rows: workspace too small");
     hipStream_t s = as_stream(stream);
-    const int nb = km_blocks(n);
+    const int nb = point_blocks(n);
     double* pdist = static_cast<double*>(ws_d);
     int64_t* prow = reinterpret_cast<int64_t*>(pdist + (size_t)kKmMaxBlocks * k);
     static const bool multi_off = env_starts_with("DCV_NEAREST_PER_CENTROID", '1');
@@ -973,13 +899,13 @@ extern "C" int dcv_kmeanspp_potentials(const double* P_d, int64_t n, int32_t d, 
     DCV_REQUIRE(trials >= 1 && trials <= kPpMaxTrials, "dcv_kmeanspp_potentials: trials=%d (1..%d)", trials, kPpMaxTrials);
     DCV_REQUIRE(ws_d && ws_bytes >= dcv_kmeanspp_workspace(n, trials), "dcv_kmeanspp_potentials: workspace too small");
     hipStream_t s = as_stream(stream);
-    const int nb = km_blocks(n);
+    const int nb = point_blocks(n);
     double* part = static_cast<double*>(ws_d);
     const auto kern = for_value<kKmMaxD>(d, [](auto D) { return &kmeanspp_potentials_kernel<D()>; });
     DCV_REQUIRE(kern, "k-means++ passes: d=%d (1..16) unsupported", d);
     hipLaunchKernelGGL(kern, dim3(nb), dim3(kKmThreads), 0, s, P_d, n, offset_d, cand_d, (int)trials, closest_d, part);
     DCV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(kmeans_final_kernel, dim3((unsigned)trials), dim3(256), 0, s, part, nb, (int)trials, pot_d);
+    sum_blocks(part, nb, (int)trials, pot_d, s);
     DCV_CHECK_LAUNCH();
     return DCV_OK;
 }
@@ -989,13 +915,13 @@ extern "C" int dcv_kmeanspp_update(const double* P_d, int64_t n, int32_t d, cons
     DCV_REQUIRE(P_d && centre_d && closest_d && pot_d && n > 0, "dcv_kmeanspp_update: bad arguments");
     DCV_REQUIRE(ws_d && ws_bytes >= dcv_kmeanspp_workspace(n, 1), "dcv_kmeanspp_update: workspace too small");
     hipStream_t s = as_stream(stream);
-    const int nb = km_blocks(n);
+    const int nb = point_blocks(n);
     double* part = static_cast<double*>(ws_d);
     const auto kern = for_value<kKmMaxD>(d, [](auto D) { return &kmeanspp_update_kernel<D()>; });
     DCV_REQUIRE(kern, "k-means++ passes: d=%d (1..16) unsupported", d);
     hipLaunchKernelGGL(kern, dim3(nb), dim3(kKmThreads), 0, s, P_d, n, offset_d, centre_d, (int)first, closest_d, part);
     DCV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(kmeans_final_kernel, dim3(1), dim3(256), 0, s, part, nb, 1, pot_d);
+    sum_blocks(part, nb, 1, pot_d, s);
     DCV_CHECK_LAUNCH();
     return DCV_OK;
 }

@@ -9,8 +9,8 @@
 //   step     one launch per chain step.  Head: the row update of the merge the previous step recorded (Lance-Williams
 //            on row y and column y).  Body: every workgroup reads the chain state the previous launch left, scans its
 //            contiguous slice of row x = top of the chain (dead clusters and x itself masked by `size`), reduces to the
-//            lexicographic minimum of (distance, index) and hands it over (handoff.h).  The last workgroup to arrive
-//            combines the partials, applies scipy's rule "the previous chain element wins unless something is strictly
+//            lexicographic minimum of (distance, index) and hands it over (ticketed_argmin, points.h).  The last workgroup to
+//            arrive combines the partials, applies scipy's rule "the previous chain element wins unless something is strictly
 //            closer" and either pushes the neighbour or records the merge, retires x, and describes the row update
 //            that is now due in the state.
 //
@@ -20,14 +20,13 @@
 #include <numeric>
 #include <vector>
 
-#include "common.h"
-#include "handoff.h"
+#include "points.h"
 
 namespace dcv {
 
-constexpr int kLkThreads = 256;
+constexpr int kLkThreads = kPtThreads;
 constexpr int kLkSlice = 2 * kLkThreads;   // doubles of a row one workgroup covers per pass (16-byte loads)
-constexpr int kLkMaxD = 16;
+constexpr int kLkMaxD = kPtMaxD;
 constexpr int kLkPdRows = 8;               // rows of the matrix per pdist workgroup
 
 enum { kLkComplete = 0, kLkAverage = 1, kLkWard = 2 };
@@ -53,7 +52,6 @@ struct dbl2 {
 
 __global__ __launch_bounds__(kLkThreads) void linkage_pdist_kernel(const double* __restrict__ P, int64_t n, int d, int64_t ld,
                                                                     double* __restrict__ D, int col_blocks) {
-#pragma clang fp contract(off)
     const int64_t rb = blockIdx.x / col_blocks;
     const int cb = blockIdx.x - rb * col_blocks;
     const int64_t j = (int64_t)cb * kLkSlice + 2 * threadIdx.x;
@@ -69,18 +67,8 @@ __global__ __launch_bounds__(kLkThreads) void linkage_pdist_kernel(const double*
     for (int r = 0; r < kLkPdRows; ++r) {
         const int64_t i = r0 + r;
         if (i >= n) break;
-        double sa = 0.0, sb = 0.0;
-#pragma unroll
-        for (int q = 0; q < kLkMaxD; ++q)
-            if (q < d) {
-                const double x = P[i * d + q];
-                const double da = x - a[q], db = x - b[q];
-                // plain operators under the pragma: the __dmul_rn / __dadd_rn wrappers are inlined with the default
-                // contraction and fuse into one fma (seen in the ISA)
-                const double qa = da * da, qb = db * db;
-                sa = sa + qa;
-                sb = sb + qb;
-            }
+        double sa, sb;
+        sqdist_exact2<kLkMaxD, true>(a, b, P + i * d, d, sa, sb);   // P[i] - P[j], P[i] - P[j + 1]: row i is loaded once
         dbl2 v;
         v.a = __dsqrt_rn(sa);
         v.b = __dsqrt_rn(sb);
@@ -98,32 +86,6 @@ __global__ void linkage_init_kernel(LinkState* __restrict__ st, int32_t* __restr
         *st = s;
         chain[0] = 0;
     }
-}
-
-// lexicographic minimum of (distance, index); an index < 0 is "no candidate"
-__device__ __forceinline__ void lk_take(double& bd, int& bi, double od, int oi) {
-    if (oi >= 0 && (bi < 0 || od < bd || (od == bd && oi < bi))) {
-        bd = od;
-        bi = oi;
-    }
-}
-
-__device__ __forceinline__ void lk_block_min(double& bd, int& bi, double* s_d, int* s_i) {
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        const double od = __shfl_down(bd, o);
-        const int oi = __shfl_down(bi, o);
-        lk_take(bd, bi, od, oi);
-    }
-    const int w = threadIdx.x / kWave;
-    if (threadIdx.x % kWave == 0) {
-        s_d[w] = bd;
-        s_i[w] = bi;
-    }
-    __syncthreads();
-    bd = s_d[0];
-    bi = s_i[0];
-    for (int k = 1; k < kLkThreads / kWave; ++k) lk_take(bd, bi, s_d[k], s_i[k]);
-    __syncthreads();
 }
 
 template <int METHOD>
@@ -156,9 +118,7 @@ __global__ __launch_bounds__(kLkThreads) void linkage_step_kernel(LinkState* __r
                                                                    int32_t* __restrict__ size, int32_t* __restrict__ chain,
                                                                    double* __restrict__ merges, double* __restrict__ part, int n,
                                                                    int64_t ld, int per, int64_t max_searches) {
-    __shared__ double s_d[kLkThreads / kWave];
-    __shared__ int s_i[kLkThreads / kWave];
-    __shared__ unsigned s_flag;
+    __shared__ ArgminLds<false> s_min;
     if (st->done | st->error) return;   // uniform over the grid: the state only changes behind every workgroup's ticket
     const int len = st->chain_len;
     const int x = chain[len - 1];
@@ -185,8 +145,7 @@ __global__ __launch_bounds__(kLkThreads) void linkage_step_kernel(LinkState* __r
     double* ry = D + (int64_t)(pend ? uy : 0) * ld;
     const int begin = blockIdx.x * per;
     const int end = begin + per < (int)ld ? begin + per : (int)ld;
-    double bd = INFINITY;   // scipy starts from infinity: a NaN or an infinite distance is never a candidate
-    int bi = -1;
+    Cand<false> best = {INFINITY, -1};   // scipy starts from infinity: a NaN or an infinite distance is never a candidate
     for (int i = begin + 2 * threadIdx.x; i < end; i += kLkSlice) {   // i even, ld even: i + 1 < ld
         dbl2 v = *reinterpret_cast<const dbl2*>(row + i);
         const int2 s = *reinterpret_cast<const int2*>(size + i);
@@ -211,30 +170,12 @@ __global__ __launch_bounds__(kLkThreads) void linkage_step_kernel(LinkState* __r
             if (fix && i + 1 == uy) v.b = v_fix;
         }
         // upwards with a strict '<', as scipy scans
-        if (s.x > 0 && i != x && v.a < bd) {
-            bd = v.a;
-            bi = i;
-        }
-        if (s.y > 0 && i + 1 != x && v.b < bd) {
-            bd = v.b;
-            bi = i + 1;
-        }
+        if (s.x > 0 && i != x && v.a < best.v) best = {v.a, i};
+        if (s.y > 0 && i + 1 != x && v.b < best.v) best = {v.b, i + 1};
     }
-    lk_block_min(bd, bi, s_d, s_i);
-    if (threadIdx.x == 0) {
-        handoff_store(part + 2 * blockIdx.x, bd);
-        handoff_store(part + 2 * blockIdx.x + 1, (double)bi);
-    }
-    if (!handoff_arrive_last(&st->ticket, gridDim.x, &s_flag)) return;
-
-    double md = 0.0;
-    int mi = -1;
-    if (threadIdx.x < gridDim.x) {   // at most one workgroup per 512 columns and at most kLkThreads of them
-        md = handoff_load(part + 2 * threadIdx.x);
-        mi = (int)handoff_load(part + 2 * threadIdx.x + 1);
-    }
-    lk_block_min(md, mi, s_d, s_i);
-    if (threadIdx.x != 0) return;
+    if (!ticketed_argmin(best, part, &st->ticket, s_min) || threadIdx.x != 0) return;
+    const double md = best.v;
+    const int mi = best.i;
     if (fix) D[(int64_t)x * ld + uy] = v_fix;   // every workgroup has read the old entry: all of them are behind their tickets
     st->searches = nsearch + 1;
     if (mi < 0 && p < 0) {   // nothing comparable in the row: non-finite input
@@ -287,30 +228,16 @@ __global__ __launch_bounds__(kLkThreads) void linkage_step_kernel(LinkState* __r
     if (nsearch + 1 >= max_searches && !st->done) st->error = 2;   // the chain needs at most 3 (n - 1) searches
 }
 
-struct LinkLayout {
-    int64_t ld;
-    int per, grid;
-    size_t off_state, off_size, off_chain, off_merges, off_part, off_D, total;
+struct LinkLayout {   // the regions in workspace order
+    LinkLayout(int64_t n_, int cus) : n((size_t)n_), ld((int64_t)align_up(n, 16)), g(step_grid(ld, kLkSlice, cus)) {}
+    size_t n;
+    int64_t ld;   // rows are ld doubles apart
+    StepGrid g;   // one workgroup covers a whole number of 512-column passes
+    Carver c;
+    Region<LinkState> state = c.take<LinkState>(1);
+    Region<int32_t> size = c.take<int32_t>((size_t)ld), chain = c.take<int32_t>((size_t)ld);
+    Region<double> merges = c.take<double>(n * 4), part = c.take<double>(2 * kLkThreads), D = c.take<double>(n * (size_t)ld);
 };
-
-static LinkLayout link_layout(int64_t n, int cus) {
-    LinkLayout L;
-    L.ld = (int64_t)align_up((size_t)n, 16);
-    // one workgroup per CU at most, each a whole number of 512-column passes; never more than kLkThreads of them
-    // (the last arriver reads one partial per thread)
-    const int cap = cus < kLkThreads ? (cus > 0 ? cus : 1) : kLkThreads;
-    L.per = (int)align_up((size_t)cdiv(L.ld, cap), kLkSlice);
-    L.grid = (int)cdiv(L.ld, L.per);
-    size_t o = 0;
-    L.off_state = o;  o += align_up(sizeof(LinkState), 256);
-    L.off_size = o;   o += align_up((size_t)L.ld * sizeof(int32_t), 256);
-    L.off_chain = o;  o += align_up((size_t)L.ld * sizeof(int32_t), 256);
-    L.off_merges = o; o += align_up((size_t)n * 4 * sizeof(double), 256);
-    L.off_part = o;   o += align_up((size_t)2 * kLkThreads * sizeof(double), 256);
-    L.off_D = o;      o += (size_t)n * (size_t)L.ld * sizeof(double);
-    L.total = o;
-    return L;
-}
 
 constexpr int64_t kLkMaxN = (int64_t)1 << 24;   // indices travel as int32 and as exact doubles
 
@@ -322,22 +249,19 @@ extern "C" size_t dcv_linkage_workspace(int64_t n, int32_t d) {
     if (n < 2 || n > kLkMaxN || d < 1 || d > kLkMaxD) return 0;
     // sized for the largest grid the driver may pick, whatever the device: the layout only depends on the CU count through
     // `per`, not through any offset
-    return link_layout(n, kLkThreads).total;
+    return LinkLayout(n, kLkThreads).c.total;
 }
 
 // the matrix fill alone, into a workspace laid out as dcv_linkage lays it out (tools/linkage_bench.py times it)
 extern "C" int dcv_linkage_pdist(const double* P_d, int64_t n, int32_t d, void* ws_d, size_t ws_bytes, void* stream) {
     DCV_REQUIRE(n >= 2 && n <= kLkMaxN && d >= 1 && d <= kLkMaxD && P_d, "dcv_linkage_pdist: bad arguments (n=%lld d=%d)", (long long)n, d);
-    if (!ws_d || ws_bytes < dcv_linkage_workspace(n, d)) {
-        set_error("dcv_linkage_pdist: workspace of %zu bytes, %zu needed", ws_bytes, dcv_linkage_workspace(n, d));
-        return DCV_ENOMEM;
-    }
-    const LinkLayout L = link_layout(n, kLkThreads);
+    DCV_REQUIRE_WORKSPACE("dcv_linkage_pdist", ws_d, ws_bytes, dcv_linkage_workspace(n, d));
+    const LinkLayout L(n, kLkThreads);
     const int col_blocks = (int)cdiv(n, kLkSlice);
     const int64_t pd_blocks = cdiv(n, kLkPdRows) * col_blocks;
     DCV_REQUIRE(pd_blocks < ((int64_t)1 << 31), "dcv_linkage_pdist: n = %lld needs too many workgroups", (long long)n);
     hipLaunchKernelGGL(linkage_pdist_kernel, dim3((unsigned)pd_blocks), dim3(kLkThreads), 0, as_stream(stream), P_d, n, (int)d, L.ld,
-                       reinterpret_cast<double*>(static_cast<char*>(ws_d) + L.off_D), col_blocks);
+                       L.D.in(ws_d), col_blocks);
     DCV_CHECK_LAUNCH();
     return DCV_OK;
 }
@@ -349,52 +273,40 @@ extern "C" int dcv_linkage(const double* P_d, int64_t n, int32_t d, int32_t meth
     DCV_REQUIRE(method == kLkComplete || method == kLkAverage || method == kLkWard,
                 "dcv_linkage: method %d (0 complete, 1 average, 2 ward)", method);
     DCV_REQUIRE(P_d && Z_h, "dcv_linkage: null points or result");
-    if (!ws_d || ws_bytes < dcv_linkage_workspace(n, d)) {
-        set_error("dcv_linkage: workspace of %zu bytes, %zu needed", ws_bytes, dcv_linkage_workspace(n, d));
-        return DCV_ENOMEM;
-    }
+    DCV_REQUIRE_WORKSPACE("dcv_linkage", ws_d, ws_bytes, dcv_linkage_workspace(n, d));
     DCV_REQUIRE((reinterpret_cast<uintptr_t>(ws_d) & 15) == 0, "dcv_linkage: workspace not 16-byte aligned");
     hipStream_t s = as_stream(stream);
-    const LinkLayout L = link_layout(n, num_cus());
-    char* w = static_cast<char*>(ws_d);
-    LinkState* st = reinterpret_cast<LinkState*>(w + L.off_state);
-    int32_t* size = reinterpret_cast<int32_t*>(w + L.off_size);
-    int32_t* chain = reinterpret_cast<int32_t*>(w + L.off_chain);
-    double* merges = reinterpret_cast<double*>(w + L.off_merges);
-    double* part = reinterpret_cast<double*>(w + L.off_part);
-    double* D = reinterpret_cast<double*>(w + L.off_D);
+    const LinkLayout L(n, num_cus());
+    LinkState* st = L.state.in(ws_d);
+    int32_t* size = L.size.in(ws_d);
+    int32_t* chain = L.chain.in(ws_d);
+    double* merges = L.merges.in(ws_d);
 
     hipLaunchKernelGGL(linkage_init_kernel, dim3((unsigned)cdiv(L.ld, 256)), dim3(256), 0, s, st, size, chain, n, L.ld);
     DCV_CHECK_LAUNCH();
     if (const int rc = dcv_linkage_pdist(P_d, n, d, ws_d, ws_bytes, stream)) return rc;
 
     const int64_t max_searches = 3 * (n - 1);
+    const auto step = method == kLkComplete ? linkage_step_kernel<kLkComplete>
+                      : method == kLkAverage ? linkage_step_kernel<kLkAverage>
+                                             : linkage_step_kernel<kLkWard>;
     struct {
         int32_t merges, done, error, chain_len;
         int64_t searches;
     } h = {0, 0, 0, 1, 0};
-    int64_t enqueued = 0;
-    while (!h.done && !h.error && enqueued < max_searches) {
-        // every merge still missing costs at least one step: a block of that many steps cannot run past the end
-        int64_t steps = (int64_t)(n - 1) - h.merges;
-        steps = steps < 256 ? 256 : (steps > 4096 ? 4096 : steps);
-        if (steps > max_searches - enqueued) steps = max_searches - enqueued;
-        for (int64_t k = 0; k < steps; ++k) {
-            if (method == kLkComplete)
-                hipLaunchKernelGGL(linkage_step_kernel<kLkComplete>, dim3(L.grid), dim3(kLkThreads), 0, s, st, D, size, chain, merges, part,
-                                   (int)n, L.ld, L.per, max_searches);
-            else if (method == kLkAverage)
-                hipLaunchKernelGGL(linkage_step_kernel<kLkAverage>, dim3(L.grid), dim3(kLkThreads), 0, s, st, D, size, chain, merges, part,
-                                   (int)n, L.ld, L.per, max_searches);
-            else
-                hipLaunchKernelGGL(linkage_step_kernel<kLkWard>, dim3(L.grid), dim3(kLkThreads), 0, s, st, D, size, chain, merges, part,
-                                   (int)n, L.ld, L.per, max_searches);
-        }
-        DCV_CHECK_LAUNCH();
-        enqueued += steps;
-        DCV_CHECK_HIP(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
-        DCV_CHECK_HIP(hipStreamSynchronize(s));
-    }
+    const int rc = run_steps(
+        s, st, h, max_searches,
+        [&](const auto& head, int64_t left) {
+            // every merge still missing costs at least one step: a block of that many steps cannot run past the end
+            int64_t steps = (int64_t)(n - 1) - head.merges;
+            steps = steps < 256 ? 256 : (steps > 4096 ? 4096 : steps);
+            return steps < left ? steps : left;
+        },
+        [&] {
+            hipLaunchKernelGGL(step, dim3(L.g.grid), dim3(kLkThreads), 0, s, st, L.D.in(ws_d), size, chain, merges, L.part.in(ws_d), (int)n, L.ld,
+                               L.g.per, max_searches);
+        });
+    if (rc) return rc;
     if (searches_h) *searches_h = h.searches;
     DCV_REQUIRE(h.error == 0 && h.done, "dcv_linkage: the chain did not finish (%s; %d of %lld merges after %lld searches): non-finite input?",
                 h.error == 1 ? "a search found no candidate" : "more than 3 (n - 1) searches", h.merges, (long long)(n - 1),

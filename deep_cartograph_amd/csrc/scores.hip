@@ -5,24 +5,15 @@
 // compute-bound on the float64 vector pipe and practical up to a few million points per GPU.
 // float64 throughout (the points are the CSV values the reference clusters).
 //
-// Determinism: per-wave LDS accumulators combined in wave then block order, as in kmeans.hip.
-#include "common.h"
+// Determinism: per-wave LDS accumulators combined in wave then block order, as in kmeans.hip; the grid, a block's range of
+// points and the final sum over the blocks are the streaming pieces of points.h.
+#include "points.h"
 
 namespace dcv {
 
-constexpr int kScThreads = 256;
-constexpr int kScMaxD = 16;
+constexpr int kScThreads = kPtThreads;
+constexpr int kScMaxD = kPtMaxD;
 constexpr int kScMaxK = 64;
-constexpr int kScMaxBlocks = 1024;
-
-static int sc_blocks(int64_t n) {
-    int64_t b = cdiv(n, (int64_t)kScThreads * 4);
-    const int64_t cap = (int64_t)num_cus() * 4;
-    if (b > cap) b = cap;
-    if (b > kScMaxBlocks) b = kScMaxBlocks;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 
 // part[block] = [sums k*d | counts k | sum ||x - c_label||^2 k | sum ||x - c_label|| k]; without centres
 // only the first two groups are meaningful
@@ -39,10 +30,8 @@ __global__ __launch_bounds__(kScThreads) void label_stats_kernel(const double* _
     for (int i = t; i < 4 * W; i += kScThreads) s_acc[i] = 0.0;
     __syncthreads();
     double* my = s_acc + wave * W;
-    const int64_t per_block = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t begin = (int64_t)blockIdx.x * per_block;
-    const int64_t end = begin + per_block < n ? begin + per_block : n;
-    for (int64_t i = begin + t; i < end; i += kScThreads) {
+    const Range r = block_range(n);
+    for (int64_t i = r.begin + t; i < r.end; i += kScThreads) {
         const int lab = labels[i];
         if (lab < 0 || lab >= k) continue;   // noise labels (-1) of other algorithms are not scored
         double ss = 0.0;
@@ -61,22 +50,6 @@ __global__ __launch_bounds__(kScThreads) void label_stats_kernel(const double* _
     __syncthreads();
     double* out = part + (int64_t)blockIdx.x * W;
     for (int i = t; i < W; i += kScThreads) out[i] = ((s_acc[i] + s_acc[W + i]) + s_acc[2 * W + i]) + s_acc[3 * W + i];
-}
-
-// acc[i] = sum over the blocks of part[b][i]: one workgroup per output, threads take b = t, t + 256, ... (independent
-// loads, all in flight), fixed LDS tree -- a single thread walking the partials pays one memory latency per partial.
-__global__ __launch_bounds__(256) void sum_blocks_kernel(const double* __restrict__ part, int nblocks, int width, double* __restrict__ acc) {
-    __shared__ double s_red[256];
-    const int i = blockIdx.x, t = threadIdx.x;
-    double s = 0.0;
-    for (int b = t; b < nblocks; b += 256) s += part[(int64_t)b * width + i];
-    s_red[t] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) s_red[t] += s_red[t + o];
-        __syncthreads();
-    }
-    if (t == 0) acc[i] = s_red[0];
 }
 
 // S[i][c] = sum over the points j of cluster c of ||Q_i - P_j||.  P is sorted by cluster (cluster c
@@ -232,7 +205,7 @@ __global__ void binning_to_double_kernel(const unsigned long long* __restrict__ 
 using namespace dcv;
 
 extern "C" size_t dcv_label_stats_workspace(int64_t n, int32_t d, int32_t k) {
-    return (size_t)sc_blocks(n) * (size_t)(k * d + 3 * k) * sizeof(double);
+    return (size_t)point_blocks(n) * (size_t)(k * d + 3 * k) * sizeof(double);
 }
 
 extern "C" int dcv_label_stats(const double* P_d, int64_t n, int32_t d, const int32_t* labels_d, const double* centers_d,
@@ -242,12 +215,12 @@ extern "C" int dcv_label_stats(const double* P_d, int64_t n, int32_t d, const in
                 (long long)n, d, k);
     DCV_REQUIRE(ws_bytes >= dcv_label_stats_workspace(n, d, k), "dcv_label_stats: workspace too small");
     hipStream_t s = as_stream(stream);
-    const int nb = sc_blocks(n);
+    const int nb = point_blocks(n);
     const int W = k * d + 3 * k;
     const size_t lds = ((size_t)k * d + 4 * (size_t)W) * sizeof(double);
     hipLaunchKernelGGL(label_stats_kernel, dim3(nb), dim3(kScThreads), lds, s, P_d, n, d, labels_d, centers_d, k, static_cast<double*>(ws_d));
     DCV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(sum_blocks_kernel, dim3((unsigned)W), dim3(256), 0, s, static_cast<const double*>(ws_d), nb, W, acc_d);
+    sum_blocks(static_cast<const double*>(ws_d), nb, W, acc_d, s);
     DCV_CHECK_LAUNCH();
     return DCV_OK;
 }
@@ -270,17 +243,17 @@ extern "C" int dcv_cluster_dist_sums(const double* Q_d, int64_t nq, const double
     return DCV_OK;
 }
 
-extern "C" size_t dcv_silhouette_sum_workspace(int64_t nq) { return (size_t)sc_blocks(nq) * sizeof(double); }
+extern "C" size_t dcv_silhouette_sum_workspace(int64_t nq) { return (size_t)point_blocks(nq) * sizeof(double); }
 
 extern "C" int dcv_silhouette_sum(const double* S_d, int64_t nq, int32_t k, const int32_t* qlabels_d, const int64_t* start_d,
                                   double* sum_d, void* ws_d, size_t ws_bytes, void* stream) {
     DCV_REQUIRE(S_d && qlabels_d && start_d && sum_d && ws_d, "dcv_silhouette_sum: null argument");
-    const int nb = sc_blocks(nq);
+    const int nb = point_blocks(nq);
     DCV_REQUIRE(ws_bytes >= (size_t)nb * sizeof(double), "dcv_silhouette_sum: workspace too small");
     hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(silhouette_sum_kernel, dim3(nb), dim3(kScThreads), 0, s, S_d, nq, k, qlabels_d, start_d, static_cast<double*>(ws_d));
     DCV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(sum_blocks_kernel, dim3(1), dim3(256), 0, s, static_cast<const double*>(ws_d), nb, 1, sum_d);
+    sum_blocks(static_cast<const double*>(ws_d), nb, 1, sum_d, s);
     DCV_CHECK_LAUNCH();
     return DCV_OK;
 }

@@ -52,6 +52,35 @@ def test_product_does_not_import_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", src, flags=re.M), f"{f} imports the oracle"
 
 
+@pytest.mark.parametrize("d", [1, 16])
+@pytest.mark.parametrize("n", [2, 3, 16, 17, 513, 4097])
+def test_step_workspace_sizes_are_pinned(n, d):
+    """The workspace layouts of the per-step kernels (csrc/points.h: Carver), restated: every region starts on a 256-byte
+    boundary.  Prim's state: the state words, two double and four int32 arrays of n, 3 x 256 partials.  The chain's state:
+    the state words, two int32 arrays of ld = n rounded up to 16, n merges of four doubles, 2 x 256 partials and the
+    n x ld matrix at the end.  Neither function touches a device."""
+    import __graft_entry__ as ge
+    from deep_cartograph_amd import _lib
+
+    ge.build()
+    lib = _lib.load()
+    a = lambda x: (x + 255) // 256 * 256
+    ld = (n + 15) // 16 * 16
+    assert lib.dcv_mr_mst_workspace(n, d) == 256 + 2 * a(8 * n) + 4 * a(4 * n) + a(6144)
+    assert lib.dcv_linkage_workspace(n, d) == 256 + 2 * a(4 * ld) + a(32 * n) + a(4096) + 8 * n * ld
+
+
+def test_step_workspace_sizes_out_of_range_are_zero():
+    import __graft_entry__ as ge
+    from deep_cartograph_amd import _lib
+
+    ge.build()
+    lib = _lib.load()
+    for n, d in ((1, 2), (0, 2), (-5, 2), (8, 0), (8, 17), (8, -1)):
+        assert lib.dcv_mr_mst_workspace(n, d) == 0 and lib.dcv_linkage_workspace(n, d) == 0
+    assert lib.dcv_linkage_workspace((1 << 24) + 1, 2) == 0 and lib.dcv_mr_mst_workspace(1 << 31, 2) == 0
+
+
 # ------------------------------------------------------------------ in-launch hand-offs: the emitted instruction order
 _OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
@@ -87,7 +116,8 @@ def _device_disassembly(tmp_path):
 @pytest.mark.skipif(not os.path.exists(_OBJDUMP), reason="llvm-objdump of the ROCm toolchain not present")
 def test_handoff_isa_order(tmp_path):
     """Every ticketed hand-off between workgroups (csrc/handoff.h: the contraction-split tail tile of the row-tiled
-    products, the Deep-TICA batch statistics + loss head, the autoencoder SSE) must be emitted in the order
+    products, the Deep-TICA batch statistics + loss head, the autoencoder SSE, the grid-wide argmin of the linkage and
+    Prim steps) must be emitted in the order
     MI355X_MICROARCH.md validates: write-through (sc1) payload stores -> s_waitcnt vmcnt(0) in the storing wave ->
     s_barrier -> the ticket (a returning global_atomic_add) -> in the last arriver buffer_inv sc1 + s_waitcnt vmcnt(0)
     -> s_barrier -> the loads.  Checked on the code that ships: the gfx950 code objects inside libdcv.so.
@@ -150,6 +180,10 @@ def test_handoff_isa_order(tmp_path):
     for d in (1, 2, 3, 4):
         assert f"tica_stats_rows_kernelILi{d}E" in names
     assert sum(1 for n in ticketed if "gemm_kernel" in n) >= 100   # NT / NN instantiations carry the tail-tile hand-off
+    # the per-step kernels of the clustering chains (points.h: ticketed_argmin): one hand-off each
+    for method in (0, 1, 2):
+        assert sum(v for n, v in ticketed.items() if f"linkage_step_kernelILi{method}E" in n) == 1
+    assert sum(v for n, v in ticketed.items() if "mst_step_kernel" in n) == 1
     # nothing in the library publishes through a workgroup-scope fence any more
     src = "".join(open(os.path.join(ROOT, "deep_cartograph_amd", "csrc", f)).read() for f in os.listdir(os.path.join(ROOT, "deep_cartograph_amd", "csrc")) if f.endswith((".h", ".hip")))
     assert not re.search(r'fence\(__ATOMIC_RELEASE,\s*"workgroup"\)', src)
