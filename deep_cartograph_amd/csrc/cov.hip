@@ -42,7 +42,9 @@ static CovPlan cov_plan(int64_t n_pairs, int F, int lag) {
     // then falls back to the plain one when the count is no multiple of 8 -- slower, never wrong)
     while (cdiv(n_pairs, p.k_chunk) * per_split > kCovMaxSlabBytes) p.k_chunk += 32;
     p.splits = cdiv(n_pairs, p.k_chunk);
-    p.stats_ws = align_up(dcv_col_stats_workspace(n_pairs, F), 256);
+    // one workspace serves three statistics passes: all pairs, and the `lag` head and tail rows -- a lag longer than the
+    // pair count makes those two the larger ones
+    p.stats_ws = align_up(dcv_col_stats_workspace(n_pairs > lag ? n_pairs : (int64_t)lag, F), 256);
     p.sums = align_up((size_t)3 * 4 * F * sizeof(double), 256);
     p.slab = align_up((size_t)p.splits * per_split, 256);
     p.asum = align_up((size_t)p.splits * F * sizeof(float), 256);

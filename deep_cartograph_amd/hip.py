@@ -41,6 +41,18 @@ def _check_matrix(X: torch.Tensor, dtype=torch.float32):
         raise DcvError(f"expected a row-major 2-D {dtype} tensor, got shape {tuple(X.shape)} dtype {X.dtype} strides {X.stride()}")
 
 
+def _check_vector(v: Optional[torch.Tensor], length: int, name: str, device=None):
+    """The kernels read ``length`` consecutive float32 values from the vector's base address: anything else (a float64
+    NumPy default, a shorter or strided vector, another device) would be read as garbage or past its end.  None passes."""
+    if v is None:
+        return
+    if v.dim() != 1 or v.dtype != torch.float32 or v.shape[0] != length or not v.is_contiguous():
+        raise DcvError(f"{name}: expected a contiguous float32 vector of {length} elements, got shape {tuple(v.shape)} "
+                       f"dtype {v.dtype} strides {v.stride()}")
+    if device is not None and v.device != device:
+        raise DcvError(f"{name}: on {v.device}, the matrix is on {device}")
+
+
 # ------------------------------------------------------------------------------- statistics
 def col_stats_raw(X: torch.Tensor) -> torch.Tensor:
     """[4, F] float64: sum, sum of squares, min, max (dcv_col_stats)."""
@@ -237,6 +249,10 @@ def normalize(X: torch.Tensor, mean: torch.Tensor, rng: torch.Tensor, out: Optio
         out = torch.empty_like(X)
     _check_matrix(out)
     n, F = X.shape
+    if out.shape != X.shape or out.device != X.device:
+        raise DcvError(f"normalize: out has shape {tuple(out.shape)} on {out.device}, X {tuple(X.shape)} on {X.device}")
+    _check_vector(mean, F, "normalize: mean", X.device)
+    _check_vector(rng, F, "normalize: range", X.device)
     check(_lib.load().dcv_normalize(_ptr(X), _ptr(out), n, F, X.stride(0), out.stride(0), _ptr(mean), _ptr(rng), _stream()),
           "dcv_normalize")
     return out
@@ -251,6 +267,7 @@ def lagged_cov_raw(X: torch.Tensor, n_pairs: int, lag: int, shift: Optional[torc
     n, F = X.shape
     if n_pairs + lag > n:
         raise DcvError(f"lagged_cov: n_pairs + lag = {n_pairs + lag} exceeds the {n} rows available")
+    _check_vector(shift, F, "lagged_cov: shift", X.device)
     out = torch.empty(2 * F + 2 * F * F, dtype=torch.float64, device=X.device)
     ws = _ws(lib.dcv_lagged_cov_workspace(n_pairs, F, lag), X.device)
     check(lib.dcv_lagged_cov(_ptr(X), n_pairs, F, X.stride(0), lag, _ptr(shift), _ptr(out), _ptr(ws), ws.numel(), _stream()),
@@ -286,6 +303,9 @@ def project_linear(X: torch.Tensor, W: torch.Tensor, *, fmean=None, frange=None,
     if W.dim() != 2 or W.shape[0] != F or not W.is_contiguous() or W.dtype != torch.float32:
         raise DcvError("project_linear: W must be a contiguous float32 F x d tensor")
     d = W.shape[1]
+    for v, length, name in ((fmean, F, "fmean"), (frange, F, "frange"), (bias, d, "bias"), (cvmean, d, "cvmean"),
+                            (cvrange, d, "cvrange")):
+        _check_vector(v, length, "project_linear: " + name, X.device)
     out = torch.empty(n, d, dtype=torch.float32, device=X.device) if want_out else None
     mm = torch.empty(2, d, dtype=torch.float32, device=X.device) if want_minmax else None
     ws = _ws(lib.dcv_project_linear_workspace(n, F, d), X.device)

@@ -70,6 +70,25 @@ def test_step_workspace_sizes_are_pinned(n, d):
     assert lib.dcv_linkage_workspace(n, d) == 256 + 2 * a(4 * ld) + a(32 * n) + a(4096) + 8 * n * ld
 
 
+@pytest.mark.parametrize("P,F,lag", [(100, 8, 200), (1000, 12, 4000), (100, 8, 0), (2048, 54, 1)])
+def test_lagged_cov_workspace_covers_the_lag_passes(P, F, lag):
+    """dcv_lagged_cov's workspace (csrc/cov.hip: cov_plan), restated for one chunk (P <= 2048): the column-statistics
+    partials, three [4][F] float64 blocks, one slab of A (and one of B at lag > 0), one row of chunk sums, each rounded up
+    to 256 bytes.  The partials serve three statistics passes -- all P pairs, the `lag` head rows, the `lag` tail rows --
+    and must hold the largest: a lag longer than P needs more blocks than the pairs do (300 frames at lag 200: 4 against
+    2).  Neither function touches a device."""
+    import __graft_entry__ as ge
+    from deep_cartograph_amd import _lib
+
+    ge.build()
+    lib = _lib.load()
+    a = lambda x: (x + 255) // 256 * 256
+    nb = 2 if lag else 1
+    stats = lib.dcv_col_stats_workspace(max(P, lag), F)
+    assert stats == min(-(-max(P, lag) // 64), 2048) * 4 * F * 8
+    assert lib.dcv_lagged_cov_workspace(P, F, lag) == a(stats) + a(96 * F) + a(nb * 4 * F * F) + a(4 * F)
+
+
 def test_step_workspace_sizes_out_of_range_are_zero():
     import __graft_entry__ as ge
     from deep_cartograph_amd import _lib
