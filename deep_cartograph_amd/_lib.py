@@ -15,6 +15,7 @@ MODEL_AE = 2
 MODEL_VAE = 3
 FEAT_DISTANCE, FEAT_TORSION_SINCOS, FEAT_TORSION = 0, 1, 2   # DCV_FEAT_*: record kinds of dcv_featurize
 SUPERPOSE_MAX_GROUPS = 768   # DCV_SUPERPOSE_MAX_GROUPS
+INTERP_PCHIP, INTERP_MAKIMA = 0, 1   # DCV_INTERP_*: kinds of dcv_interpolate
 
 
 class MlpDesc(C.Structure):
@@ -75,6 +76,8 @@ SIGNATURES = {
     "dcv_featurize": (C.c_int, [_P, _I64, _I64, _I64, _I64, _I32, _P, _I32, C.c_double, _P, _I64, _P, _SZ, _P]),
     "dcv_superpose_workspace": (_SZ, [_I64, _I32, _I32, _I32]),
     "dcv_superpose": (C.c_int, [_P, _I64, _I64, _I64, _I64, _I32, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P, _I64, _P, _P, _SZ, _P]),
+    "dcv_interpolate_workspace": (_SZ, [_I64, _I32, _I32, _I64]),
+    "dcv_interpolate": (C.c_int, [_P, _I64, _I64, _I64, _I64, _I32, _P, _I32, _I32, _I32, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
     "dcv_normalize": (C.c_int, [_P, _P, _I64, _I32, _I64, _I64, _P, _P, _P]),
     "dcv_lagged_cov_workspace": (_SZ, [_I64, _I32, _I32]),
     "dcv_lagged_cov": (C.c_int, [_P, _I64, _I32, _I64, _I32, _P, _P, _P, _SZ, _P]),

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FEAT_DISTANCE, FEAT_TORSION, FEAT_TORSION_SINCOS, DcvError, check
+from ._lib import FEAT_DISTANCE, FEAT_TORSION, FEAT_TORSION_SINCOS, INTERP_MAKIMA, INTERP_PCHIP, DcvError, check
 
 
 def _require_gpu(*tensors):
@@ -239,6 +239,63 @@ def superpose(xyz: torch.Tensor, n_atoms: int, fit, fit_ref, sel=None, sel_ref=N
     if "rmsd" in out and sel_ref is None:
         out["rmsd"] = out["rmsd"][:, :1]
     return out
+
+
+INTERP_KINDS = {"pchip": INTERP_PCHIP, "makima": INTERP_MAKIMA}
+
+
+def interpolate(xyz: torch.Tensor, n_atoms: int, t, kind: str = "pchip", sel=None, strides=None, extrapolate: bool = True,
+                noise: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_strides=None) -> torch.Tensor:
+    """The frames of a trajectory interpolated along time at the times ``t`` (dcv_interpolate): PCHIP or modified Akima
+    (``kind`` "pchip" / "makima") through every coordinate column, frame k at time k, float64 arithmetic, equal to
+    scipy's PchipInterpolator / Akima1DInterpolator(method="makima") to rounding.  Returns a float32 [n_out, n_sel, 3]
+    tensor.
+
+    ``xyz``, ``n_atoms`` and ``strides`` as in :func:`featurize`.  ``t``: n_out finite, non-decreasing float64 times, on
+    the host.  ``sel``: the atoms to emit, in output order (None: all).  ``extrapolate``: times outside [0, n - 1] use the
+    end pieces; False makes them NaN.  ``noise``: float64 [n_out, n_sel, 3] on the device, added before the one rounding
+    to float32.  With ``out`` (a 1-D float32 buffer) and ``out_strides = (offset, frame, atom, comp)`` in elements,
+    coordinate c of selected atom s of output frame j is written to ``out[offset + j*frame + s*atom + c*comp]`` -- the
+    planes of DCD frame records, for instance -- nothing else is touched, and ``out`` is returned."""
+    _require_gpu(xyz, noise, out)
+    if kind not in INTERP_KINDS:
+        raise DcvError(f"interpolate: kind must be one of {tuple(INTERP_KINDS)}, got {kind!r}")
+    n_atoms = int(n_atoms)
+    n, base, fs, as_, cs = _coordinates("interpolate", xyz, n_atoms, strides)
+    t = np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1))
+    n_out = int(t.size)
+    if sel is not None:
+        sel = np.ascontiguousarray(np.asarray(sel).reshape(-1), dtype=np.int32)
+        if sel.size == 0:
+            raise DcvError("interpolate: the selection is empty")
+    n_sel = n_atoms if sel is None else int(sel.size)
+    if noise is not None and (noise.dtype != torch.float64 or tuple(noise.shape) != (n_out, n_sel, 3) or not noise.is_contiguous()
+                              or noise.device != xyz.device):
+        raise DcvError(f"interpolate: noise must be a contiguous float64 ({n_out}, {n_sel}, 3) tensor on {xyz.device}, "
+                       f"got {tuple(noise.shape)} {noise.dtype} on {noise.device}")
+    if (out is None) != (out_strides is None):
+        raise DcvError("interpolate: out and out_strides go together")
+    if out is None:
+        out = result = torch.empty(n_out, n_sel, 3, dtype=torch.float32, device=xyz.device)
+        off, ofs, oas, ocs = 0, 3 * n_sel, 3, 1
+    else:
+        result = out
+        off, ofs, oas, ocs = (int(v) for v in out_strides)
+        if out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous() or out.device != xyz.device:
+            raise DcvError("interpolate: out must be a contiguous 1-D float32 buffer on the device of the coordinates")
+        last = off + max(n_out - 1, 0) * ofs + (n_sel - 1) * oas + 2 * ocs
+        if off < 0 or min(ofs, oas, ocs) < 1 or (n_out > 0 and last >= out.numel()):
+            raise DcvError(f"interpolate: output layout {tuple(out_strides)} with {n_sel} atoms and {n_out} frames reaches element "
+                           f"{last} of a buffer of {out.numel()} (strides must be >= 1)")
+    if n_out == 0:
+        return result   # an empty tensor has no data pointer to hand to the library
+    lib = _lib.load()
+    ws = _ws(lib.dcv_interpolate_workspace(n, n_atoms, 0 if sel is None else n_sel, n_out), xyz.device)
+    check(lib.dcv_interpolate(base if n else ws.data_ptr(), n, fs, as_, cs, n_atoms, None if sel is None else sel.ctypes.data,
+                              0 if sel is None else n_sel, INTERP_KINDS[kind], int(bool(extrapolate)), t.ctypes.data, n_out,
+                              _ptr(noise), out.data_ptr() + 4 * off, ofs, oas, ocs, _ptr(ws), ws.numel(), _stream()),
+          "dcv_interpolate")
+    return result
 
 
 def normalize(X: torch.Tensor, mean: torch.Tensor, rng: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

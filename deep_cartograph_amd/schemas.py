@@ -301,3 +301,23 @@ class AnalyzeGeometrySchema(BaseModel):
     # time between frames in ps
     dt_per_frame: float = 1.0
     run: bool = True
+
+
+# ---------------------------------------------------------------- traj_augmentation (yaml_schemas/traj_augmentation.py)
+class TrajAugmentationSchema(BaseModel):
+    # frames of the interpolated trajectory (ignored with interpolation_method: null)
+    num_frames: int = 1000
+    # keep the original frames among the interpolated ones
+    keep_original_frames: bool = False
+    # akima (modified Akima, smoother) or pchip (monotone between frames); null emits the original frames
+    interpolation_method: Optional[Literal["akima", "pchip"]] = "pchip"
+    # standard deviation of the Gaussian noise added to every coordinate (null: none)
+    noise_std: Optional[float] = None
+    random_seed: int = 42
+    # atoms written to the new trajectory and topology (trajectory.select_atoms)
+    atom_selection: str = "all"
+    # "dcd" or "npy" are written; the reference's default "xtc" and its "nc" / "pdb" are accepted here and refused by
+    # augmentation.interpolate_trajectory with an error that names the option (no compressed or NetCDF writer)
+    traj_format: Literal["dcd", "npy", "xtc", "nc", "pdb"] = "dcd"
+    # unwrapping and centring need the box: true is refused by augmentation.interpolate_trajectory
+    prepare_trajectory: bool = False

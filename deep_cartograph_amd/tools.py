@@ -1,5 +1,5 @@
 """The tools of the CV-fit path with the reference's API (argument names, output tree,
-CSV formats): analyze_geometry (tools/analyze_geometry/analyze_geometry.py:13-143), compute_features (tools/compute_features/compute_features.py:25-227), filter_features (tools/filter_features/filter_features.py:22-31), train_colvars (tools/train_colvars/train_colvars.py:20-36), traj_projection
+CSV formats): analyze_geometry (tools/analyze_geometry/analyze_geometry.py:13-143), traj_augmentation (tools/traj_augmentation/traj_augmentation.py:23-131), compute_features (tools/compute_features/compute_features.py:25-227), filter_features (tools/filter_features/filter_features.py:22-31), train_colvars (tools/train_colvars/train_colvars.py:20-36), traj_projection
 (tools/traj_projection/traj_projection.py:19-27), traj_cluster (tools/traj_cluster/traj_cluster.py:
 18-28).  Figures, FES estimation and PDB/XTC extraction (matplotlib / MDAnalysis) are outside the
 accelerated path and are not produced."""
@@ -18,7 +18,7 @@ import pandas as pd
 from . import statistics
 from .common import merge_configurations, save_list, validate_configuration
 from .cv_calculator import CVCalculator, calculator_class
-from .schemas import AnalyzeGeometrySchema, ComputeFeaturesSchema, FilterFeaturesSchema, TrainColvarsSchema, TrajClusterSchema, TrajProjectionSchema
+from .schemas import AnalyzeGeometrySchema, ComputeFeaturesSchema, FilterFeaturesSchema, TrainColvarsSchema, TrajAugmentationSchema, TrajClusterSchema, TrajProjectionSchema
 
 logger = logging.getLogger(__name__)
 
@@ -186,6 +186,43 @@ def analyze_geometry(configuration: Dict, trajectories: List[str], topologies: L
                 np.savetxt(written[stem], np.column_stack((x_data[key], y)), delimiter=",", header=f"{x_label},{y_label}", comments="")
     logger.info("Elapsed time (Analyze geometry): %s", time.strftime("%H h %M min %S s", time.gmtime(time.time() - t0)))
     return written
+
+
+def traj_augmentation(configuration: Dict, trajectories: Union[str, List[str]], topologies: Union[str, List[str]], num_replicas: int = 1,
+                      output_folder: str = "traj_augmentation", memory_budget: Optional[int] = None):
+    """New frames interpolated between the frames of every (seed) trajectory on the device (augmentation.py,
+    hip.interpolate) instead of with scipy on the host, `num_replicas` times each: replica r draws its noise with
+    `random_seed + r` and, with more than one replica, carries the suffix `_rep<r>` (the reference's rule).  Writes
+    <out>/<stem>_augmented_<method><suffix>.<traj_format> and .pdb and returns (trajectories, topologies), as the
+    reference's tool does; existing outputs are skipped.  One topology serves all trajectories, or one per trajectory.
+    `memory_budget` bounds a chunk of output frames on the device.  No CPU fallback."""
+    from . import augmentation
+
+    t0 = time.time()
+    trajectories, topologies = _as_list(trajectories) or [], _as_list(topologies) or []
+    if len(topologies) == 1:
+        topologies = topologies * len(trajectories)
+    if len(trajectories) != len(topologies):
+        raise ValueError(f"Number of trajectories ({len(trajectories)}) and topologies ({len(topologies)}) do not match.")
+    for path in trajectories + topologies:
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"File not found: {path}")
+    os.makedirs(output_folder, exist_ok=True)
+    configuration = validate_configuration(configuration or {}, TrajAugmentationSchema, output_folder)
+    augmented_trajectories, augmented_topologies = [], []
+    for traj_path, top_path in zip(trajectories, topologies):
+        for replica in range(num_replicas):
+            new_traj, new_top = augmentation.interpolate_trajectory(
+                topology_file=top_path, trajectory_file=traj_path, num_frames=configuration["num_frames"],
+                keep_original_frames=configuration["keep_original_frames"], interpolation_method=configuration["interpolation_method"],
+                noise_std=configuration["noise_std"], random_seed=configuration["random_seed"] + replica,
+                atom_selection=configuration["atom_selection"], traj_format=configuration["traj_format"],
+                prepare_trajectory=configuration["prepare_trajectory"], output_path=output_folder,
+                suffix=f"_rep{replica}" if num_replicas > 1 else "", memory_budget=memory_budget)
+            augmented_trajectories.append(new_traj)
+            augmented_topologies.append(new_top)
+    logger.info("Elapsed time (Trajectory Augmentation): %s", time.strftime("%H h %M min %S s", time.gmtime(time.time() - t0)))
+    return augmented_trajectories, augmented_topologies
 
 
 def filter_features(configuration: Dict, colvars_paths: Union[str, List[str]], waypoint_colvars_paths: Optional[List[str]] = None,

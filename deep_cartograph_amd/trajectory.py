@@ -1,5 +1,6 @@
-"""Host side of compute_features: topology, atom selections, trajectory files and the feature definitions the
-device kernel (hip.featurize) evaluates.  NumPy only -- no MDAnalysis, no PLUMED.
+"""Host side of compute_features, analyze_geometry and traj_augmentation: topology, atom selections, trajectory files
+(read and written) and the feature definitions the device kernel (hip.featurize) evaluates.  NumPy only -- no
+MDAnalysis, no PLUMED.
 
 What the reference does with MDAnalysis and a `plumed driver` subprocess (tools/compute_features/compute_features.py,
 modules/md/md.py) is restated for the feature kinds its own test data pins:
@@ -7,6 +8,8 @@ modules/md/md.py) is restated for the feature kinds its own test data pins:
 * ``read_topology``        PDB ATOM / HETATM / CONECT records up to the first ENDMDL;
 * ``select_atoms``         a documented subset of the MDAnalysis selection grammar (below);
 * ``open_trajectory``      little-endian CHARMM / NAMD ``.dcd`` (memory-mapped, never transposed) and ``.npy``;
+* ``write_dcd``, ``write_topology``  the way back out (traj_augmentation): a chunked DCD writer whose record images a
+                           kernel fills in place, and a PDB of a selection with its CONECT records;
 * ``feature_definitions``  names and kernel records of the distance and virtual-dihedral groups, with the
                            reference's labelling rules and order (md.py:26-129, 226-273, 479-545, 580-717).
 
@@ -281,6 +284,112 @@ def open_trajectory(path: str, n_atoms: Optional[int] = None) -> Trajectory:
             raise ValueError(f"{path}: {arr.shape[1]} atoms in the trajectory, {n_atoms} in the topology")
         return Trajectory(arr.reshape(-1), arr.shape[0], arr.shape[1], 0, 3 * arr.shape[1], 3, 1)
     raise ValueError(f"{path}: unsupported trajectory format '{ext}' (supported: .dcd, .npy; XTC is compressed and out of scope)")
+
+
+# ------------------------------------------------------------------------------------------------ writers
+_DCD_TITLE = b"Written by deep_cartograph_amd"
+
+
+class DcdWriter:
+    """Chunked writer of a little-endian CHARMM-style DCD file without unit-cell blocks (what ``open_trajectory`` maps).
+    A chunk of k frames is one float32 *record image* of ``k * frame_words`` words: per frame the planes X[A], Y[A],
+    Z[A], each between two 4-byte record markers.  ``layout()`` is where a kernel writes the coordinates inside such an
+    image (the ``out_strides`` of hip.interpolate); ``append`` stamps the markers on the host and appends the image to
+    the file; ``close`` writes the final frame count into the header.  Until then the header says 0 frames, so an
+    interrupted file is refused by the reader instead of being taken for a shorter trajectory."""
+
+    def __init__(self, path: str, n_atoms: int):
+        if n_atoms < 1:
+            raise ValueError(f"write_dcd: {n_atoms} atoms")
+        self.path, self.n_atoms, self.n_frames = path, int(n_atoms), 0
+        self.frame_words = 3 * (self.n_atoms + 2)
+        self._file = open(path, "wb")
+        self._file.write(self._header(0))
+
+    def _header(self, n_frames: int) -> bytes:
+        icntrl = np.zeros(20, dtype="<i4")
+        icntrl[0], icntrl[1], icntrl[2], icntrl[3] = n_frames, 0, 1, n_frames   # frames, first step, steps between frames, steps
+        icntrl[9] = np.float32(1.0).view(np.int32)                                # time step
+        icntrl[19] = 24                                                           # CHARMM version: CHARMM-style layout, no cell (icntrl[10] = 0)
+        title = _DCD_TITLE.ljust(80)
+        return b"".join([np.int32(84).astype("<i4").tobytes(), b"CORD", icntrl.tobytes(), np.int32(84).astype("<i4").tobytes(),
+                         np.asarray([84, 1], dtype="<i4").tobytes(), title, np.asarray([84], dtype="<i4").tobytes(),
+                         np.asarray([4, self.n_atoms, 4], dtype="<i4").tobytes()])
+
+    def layout(self) -> Tuple[int, int, int, int]:
+        """(offset, frame_stride, atom_stride, comp_stride) of the coordinates inside a record image, in elements."""
+        return 1, self.frame_words, 1, self.n_atoms + 2
+
+    def image(self, n_frames: int) -> np.ndarray:
+        """A zeroed record image of ``n_frames`` frames with the markers in place."""
+        img = np.zeros(n_frames * self.frame_words, dtype=np.float32)
+        self._stamp(img)
+        return img
+
+    def _stamp(self, img: np.ndarray) -> None:
+        planes = img.view(np.int32).reshape(-1, self.n_atoms + 2)
+        planes[:, 0] = planes[:, -1] = 4 * self.n_atoms
+
+    def append(self, image: np.ndarray) -> None:
+        """Append whole frames: a float32 record image (its marker slots may hold anything: they are stamped here)."""
+        image = np.ascontiguousarray(image, dtype=np.float32).reshape(-1)
+        if image.size % self.frame_words:
+            raise ValueError(f"write_dcd: an image of {image.size} words is not a whole number of frames of {self.frame_words}")
+        self._stamp(image)
+        self._file.write(image.astype("<f4", copy=False).tobytes())
+        self.n_frames += image.size // self.frame_words
+
+    def close(self) -> None:
+        if self._file is None:
+            return
+        self._file.seek(0)
+        self._file.write(self._header(self.n_frames))
+        self._file.close()
+        self._file = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        elif self._file is not None:   # leave the header at 0 frames: the reader refuses the file
+            self._file.close()
+            self._file = None
+        return False
+
+
+def write_dcd(path: str, n_atoms: int) -> DcdWriter:
+    """Open ``path`` for chunked DCD output (see :class:`DcdWriter`)."""
+    return DcdWriter(path, n_atoms)
+
+
+def write_topology(path: str, top: Topology, atoms=None) -> None:
+    """A PDB file of the atoms ``atoms`` (indices into ``top``, default all) with the topology's own positions and fields,
+    renumbered from 1, and CONECT records for the bonds whose both ends are kept.  ``read_topology`` reads it back with
+    equal fields; a topology whose bonds are all lost in the selection reads back without bonds (None)."""
+    atoms = np.arange(top.n_atoms) if atoms is None else np.asarray(atoms, dtype=np.int64).reshape(-1)
+    new = {int(a): i for i, a in enumerate(atoms)}
+    lines = []
+    for i, a in enumerate(atoms):
+        a = int(a)
+        name = top.names[a]
+        name = name[:4] if len(name) >= 4 else " " + name.ljust(3)
+        x, y, z = (float(v) for v in top.positions[a])
+        lines.append(f"ATOM  {(i + 1) % 100000:5d} {name}{' '}{top.resnames[a][:4].ljust(4)}{(top.chains[a] or ' ')[:1]}"
+                     f"{int(top.resids[a]):4d}    {x:8.3f}{y:8.3f}{z:8.3f}{1.0:6.2f}{0.0:6.2f}      {top.segids[a][:4].ljust(4)}")
+    if top.bonds and len(atoms) < 100000:
+        partners: Dict[int, List[int]] = {}
+        for i, j in sorted(top.bonds):
+            if i in new and j in new:
+                partners.setdefault(new[i], []).append(new[j])
+                partners.setdefault(new[j], []).append(new[i])
+        for i in sorted(partners):
+            for k in range(0, len(partners[i]), 4):
+                lines.append("CONECT" + f"{i + 1:5d}" + "".join(f"{j + 1:5d}" for j in sorted(partners[i])[k:k + 4]))
+    lines.append("END")
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
 
 
 # ------------------------------------------------------------------------------------------------ feature definitions

@@ -158,6 +158,54 @@ int dcv_superpose(const float* xyz_d, int64_t n_frames, int64_t frame_stride, in
                   const int32_t* sel_h, const double* sel_ref_h, int32_t n_sel, double* transform_d, double* rmsd_d,
                   float* aligned_d, int64_t lda, double* moments_d, void* ws_d, size_t ws_bytes, void* stream);
 
+/* ---- frame interpolation (traj_augmentation) -----------------------------------------------------------------------
+ * Replaces scipy.interpolate.PchipInterpolator / Akima1DInterpolator(method='makima') along the frame axis of the
+ * (frames, atoms, 3) array in interpolate_trajectory, modules/md/md.py:1091-1121.  The n_knots frames of xyz_d are the
+ * knots, addressed as in dcv_featurize (the three strides, n_atoms; dense rows or DCD frame records in place, a frame
+ * stride that is a multiple of the record length); knot k sits at time k.  t_h is a HOST array of n_out query times,
+ * finite and non-decreasing (copied into the workspace).  sel_h is a HOST array of the n_sel atoms to emit, in output
+ * order; NULL = all n_atoms atoms (n_sel is then ignored).  noise_d, optional, holds n_out x n_sel x 3 float64, dense,
+ * in (frame, atom, xyz) order.  Coordinate c of selected atom s of output frame j goes to
+ * out_d[j*out_frame_stride + s*out_atom_stride + c*out_comp_stride] (strides in ELEMENTS, all >= 1): a dense
+ * (n_out, n_sel, 3) array, or the X / Y / Z planes of DCD frame records.  Only those elements are written.
+ * Arithmetic: float64 behind the float32 load, no fused multiply-adds, out = (float)(p(t) + noise), rounded once.
+ * With y a column, m_k = y[k+1] - y[k] (exact in float64), K = clamp(floor(t), 0, n_knots - 2) and s = t - K:
+ *   piece (both kinds: scipy's CubicHermiteSpline -> PPoly with h = 1)  T = d_K + d_{K+1} - 2 m_K,
+ *     p = y_K + d_K s + (m_K - d_K - T) s^2 + T s^3.  t outside [0, n_knots - 1] uses the end piece when
+ *     extrapolate != 0 and is NaN when extrapolate == 0.  A finite result at t == k is y_k exactly.
+ *   DCV_INTERP_PCHIP derivatives (scipy PchipInterpolator._find_derivatives, h = 1)
+ *     interior  d_k = 0 when sign(m_{k-1}) != sign(m_k) or either is 0, otherwise 1 / ((3/m_{k-1} + 3/m_k) / 6);
+ *     ends      with m0 the end slope and m1 its neighbour e = (3 m0 - m1) / 2; e = 0 when sign(e) != sign(m0);
+ *               otherwise e = 3 m0 when sign(m0) != sign(m1) and |e| > 3 |m0|; otherwise e is kept;
+ *     n_knots == 2: both derivatives are m_0.
+ *   DCV_INTERP_MAKIMA derivatives (scipy 1.15 Akima1DInterpolator, method='makima'); n_knots >= 3 (scipy's own result
+ *     for two knots reads an uninitialised slope).  With M the padded slopes: M[2:-2] = m, M[1] = 2M[2] - M[3], then
+ *     M[0] = 2M[1] - M[2], M[-2] = 2M[-3] - M[-4], then M[-1] = 2M[-2] - M[-3]:
+ *       f1_k = |M[k+3] - M[k+2]| + |M[k+3] + M[k+2]| / 2,   f2_k = |M[k+1] - M[k]| + |M[k+1] + M[k]| / 2,
+ *       d_k = (f1_k M[k+1] + f2_k M[k+2]) / (f1_k + f2_k) where f1_k + f2_k > 1e-9 G, (M[k+3] + M[k]) / 2 elsewhere.
+ *     G is the maximum of f1 + f2 over EVERY knot of EVERY selected column (scipy takes one maximum over the whole
+ *     array: one atom of large amplitude switches quiet atoms to the plain average).  A pass over the knots writes one
+ *     partial maximum per wave with plain stores, a one-workgroup launch reduces them, the evaluation reads the
+ *     result: no atomics, and a maximum does not depend on the order, so the output is bit-identical from run to run.
+ *     Non-finite values are left out of G.
+ * A non-finite input coordinate spoils its own column only.
+ * Everything is validated before anything is launched.  DCV_EINVAL: an unknown kind; n_knots < 2 (< 3 for makima); a
+ * selection index outside [0, n_atoms); n_sel < 1 with a selection; bad strides; a decreasing or non-finite time.
+ * DCV_ENOMEM: a workspace that is too small.  n_out = 0 is DCV_OK.
+ * A wave owns 64 adjacent coordinate columns and a run of at least 64 consecutive output frames; a lane walks its run
+ * in ascending t with the six knots around floor(t) and the following one in registers and loads one knot whenever
+ * floor(t) advances.  Nothing is staged in LDS: no limit on the number of atoms.  Algorithmic traffic per output frame:
+ * 12 bytes per selected atom written, plus 24 read with noise_d; reading the knots once costs 12 bytes per knot and
+ * selected atom (once more for makima's G). */
+#define DCV_INTERP_PCHIP 0
+#define DCV_INTERP_MAKIMA 1
+size_t dcv_interpolate_workspace(int64_t n_knots, int32_t n_atoms, int32_t n_sel, int64_t n_out);
+int dcv_interpolate(const float* xyz_d, int64_t n_knots, int64_t frame_stride, int64_t atom_stride, int64_t comp_stride,
+                    int32_t n_atoms, const int32_t* sel_h, int32_t n_sel, int32_t kind, int32_t extrapolate,
+                    const double* t_h, int64_t n_out, const double* noise_d,
+                    float* out_d, int64_t out_frame_stride, int64_t out_atom_stride, int64_t out_comp_stride,
+                    void* ws_d, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- normalisation (a3)
  * Replaces LinearCalculator.normalize_data, cv_calculator.py:833-835
  * (data.sub_(mean).div_(range) in float32).  Y may alias X (in place, as the reference). */
