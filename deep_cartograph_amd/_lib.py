@@ -98,6 +98,7 @@ SIGNATURES = {
     "dcv_mlp_last_path": (_I32, [_P]),
     "dcv_mlp_last_eval_group": (_I32, [_P]),
     "dcv_mlp_last_ride": (_I32, [_P]),
+    "dcv_mlp_last_reduce": (_I32, [_P]),
     "dcv_mlp_opt_state": (_P, [_P, _I32]),
     "dcv_gemm_tn_split": (C.c_int, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P]),
     "dcv_mlp_set_row_sharing": (C.c_int, [_P, _I32]),

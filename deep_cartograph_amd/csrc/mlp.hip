@@ -474,6 +474,7 @@ extern "C" int64_t dcv_mlp_dropout_step(const dcv_mlp* m) { return m ? m->drop_s
 extern "C" int32_t dcv_mlp_last_path(const dcv_mlp* m) { return m ? m->last_path : -1; }
 extern "C" int32_t dcv_mlp_last_eval_group(const dcv_mlp* m) { return m ? m->last_eval_group : -1; }
 extern "C" int32_t dcv_mlp_last_ride(const dcv_mlp* m) { return m ? m->last_ride : -1; }
+extern "C" int32_t dcv_mlp_last_reduce(const dcv_mlp* m) { return m ? m->last_reduce : -1; }
 extern "C" float* dcv_mlp_opt_state(dcv_mlp* m, int32_t which) {
     if (!m) return nullptr;
     return which == 0 ? m->adam_m : which == 1 ? m->adam_v : which == 2 ? m->opt_aux : nullptr;

@@ -199,13 +199,16 @@ static int launch_reduce(dcv_mlp* m, const ReduceArgs& ra_all, int l0, int l1, b
         const int rc = quad_items(rs, 0, &qa, &blocks);
         if (rc) return rc;
         if (blocks <= 0) return DCV_OK;
+        m->last_reduce = 1;
         return launch_quad(m, qa, blocks, fuse_opt, oa, s);
     } else if (rs.max_splits <= 512 && rs.max_bblocks <= 1024) {   // few partials per weight (the few bias elements may see more)
         int64_t bx = cdiv(rs.max_total, 64);
         if (bx > 2048) bx = 2048;
+        m->last_reduce = 2;
         hipLaunchKernelGGL(reduce_grads_small_kernel, dim3((unsigned)bx, ra.L), dim3(256), 0, s, ra, m->grads, 1.f, fuse_opt ? 1 : 0, m->params,
                            m->adam_m, m->adam_v, m->opt_aux, oa);
     } else {
+        m->last_reduce = 3;
         hipLaunchKernelGGL(reduce_grads_kernel, dim3(512, ra.L), dim3(64 * kRedWaves), 0, s, ra, m->grads, 1.f, fuse_opt ? 1 : 0, m->params, m->adam_m,
                            m->adam_v, m->opt_aux, oa);
     }
@@ -391,6 +394,7 @@ int finish_grads(dcv_mlp* m, const ReduceArgs& ra, bool fuse_opt, bool upper_don
         int64_t blocks = 0;
         const int rcq = quad_items(reduce_set(m, ra, 0, m->L), 1, &qa, &blocks);
         if (rcq || blocks <= 0) return rcq;
+        m->last_reduce = 1;
         return launch_quad(m, qa, blocks, true, *ridden, s);
     }
     int rc = reduce_upper(m, ra, fuse_opt, &upper_done, s);

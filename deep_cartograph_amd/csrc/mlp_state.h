@@ -63,6 +63,7 @@ struct dcv_mlp {   // created value-initialised (dcv_mlp_create): every member s
     dcv::EvalGroupWs eval_ws;  // grouped validation pass (dcv_mlp_eval_steps, block engine)
     int last_eval_group;       // members of the first grouped launch of the last dcv_mlp_eval_steps call (0: it stepped batch by batch)
     int last_ride;             // reduction blocks that rode in the layer-0 weight-gradient launch of the last backward (0: none; ride_upper)
+    int last_reduce;           // kernel of the final reduction of the last backward: 0 none yet, 1 flat-grid quad, 2 4-wave, 3 16-wave (launch_reduce)
     void (*upper_cb)(void*);   // data-parallel overlap hook (dcv_mlp_set_upper_grads_callback) or null
     void* upper_cb_user;
     bool head_done;            // the last forward already ran the d x d loss head inside its statistics launch (one-GPU steps)

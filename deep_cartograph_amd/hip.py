@@ -909,6 +909,10 @@ class Mlp:
         """Reduction workgroups that rode in the layer-0 weight-gradient launch of the last training backward (0: none)."""
         return int(self.lib.dcv_mlp_last_ride(self.h))
 
+    def last_reduce(self) -> int:
+        """Kernel of the final gradient reduction of the last training backward: 0 = none yet, 1 = flat-grid quad, 2 = 4-wave, 3 = 16-wave."""
+        return int(self.lib.dcv_mlp_last_reduce(self.h))
+
     def opt_state_view(self, which: int) -> Optional[torch.Tensor]:
         """The optimiser's state tensor `which` (0, 1; 2 = the auxiliary one, None without it) as a view, laid out like params_view()."""
         ptr = self.lib.dcv_mlp_opt_state(self.h, int(which))

@@ -463,6 +463,10 @@ int32_t dcv_mlp_last_eval_group(const dcv_mlp* m);
  * steps of the block engine with the update fused in: every gradient but layer 0's weights is reduced and updated there),
  * 0 when that backward ended on the single reduction launch.  DCV_NO_REDUCE_RIDE=1 in the environment forces 0. */
 int32_t dcv_mlp_last_ride(const dcv_mlp* m);
+/* Test hook: the kernel that ran the final gradient reduction of the last training backward: 0 = none yet, 1 = the flat-grid
+ * ("quad") reduction, 2 = the 4-wave form (DCV_REDUCE_QUAD=0 in the environment), 3 = the 16-wave form (more than 512 weight
+ * partials or 1024 bias partials in some layer). */
+int32_t dcv_mlp_last_reduce(const dcv_mlp* m);
 /* Test hook: the optimiser's state tensors on the device, dcv_mlp_num_params() floats each in the layout of dcv_mlp_params():
  * which = 0 / 1 the two every optimiser owns (Adam: exp_avg / exp_avg_sq), 2 the auxiliary one (amsgrad maximum, centred
  * RMSprop average) or NULL when the optimiser has none. */
