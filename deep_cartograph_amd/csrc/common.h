@@ -31,9 +31,25 @@ void set_error(const char* fmt, ...);
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+__host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 constexpr int kWave = 64;  // gfx950 wavefront
+
+// The rule for 16-byte accesses, decided on the host, in its one place.  aligned16: a vector read from its
+// base; quad_ok: the rows of a matrix with row stride ld; quad_path: and its width F, so that no quad straddles a row's end.
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool quad_ok(const void* p, int64_t ld) { return ld % 4 == 0 && aligned16(p); }
+inline bool quad_path(const void* p, int64_t F, int64_t ld) { return F % 4 == 0 && quad_ok(p, ld); }
+
+// a workgroup's contiguous range [begin, end) of n rows or points: rows_per_block each, or an even share of the grid
+struct Range {
+    int64_t begin, end;
+};
+__device__ __forceinline__ Range block_rows(int64_t n, int64_t rows_per_block) {
+    const int64_t begin = (int64_t)blockIdx.x * rows_per_block;
+    return {begin, begin + rows_per_block < n ? begin + rows_per_block : n};
+}
+__device__ __forceinline__ Range block_range(int64_t n) { return block_rows(n, cdiv(n, gridDim.x)); }
 
 // Kernel-exact timing of ONE launch (dcv_mlp_profile_*): the caller parks a pair of events here, the block engine's launcher
 // hands them to hipExtLaunchKernel, which stamps them with the kernel's own begin / end (the interval rocprofv3 reports:
@@ -47,6 +63,12 @@ extern thread_local LaunchEvents g_launch_ev;
 extern thread_local hipEvent_t g_launch_taken;   // start event of the pair the launcher consumed last
 // Number of CUs of the current device (cached).
 int num_cus();
+// Run-time switches (environment DCV_...).  Callers keep the answer in a `static const`: every switch is read once per
+// process.  env_is: set and starting with `c` (an opt-in tests '1', an opt-out of a default '0'); env_not: its negation
+// (on unless the value starts with `c`); env_int: atoll of the value, `unset` when the variable is not set.
+bool env_is(const char* name, char c);
+bool env_not(const char* name, char c);
+int64_t env_int(const char* name, int64_t unset);
 // arithmetic of the matrix products: false = FP32-input MFMA, true = FP32-accurate split products on the BF16
 // matrix pipe (default; dcv_set_gemm_mode / environment DCV_GEMM_MODE=native|split)
 bool gemm_split();

@@ -23,6 +23,16 @@ int num_cus() {
     return cached;
 }
 
+bool env_is(const char* name, char c) {
+    const char* e = getenv(name);
+    return e && e[0] == c;
+}
+bool env_not(const char* name, char c) { return !env_is(name, c); }
+int64_t env_int(const char* name, int64_t unset) {
+    const char* e = getenv(name);
+    return e ? (int64_t)atoll(e) : unset;
+}
+
 thread_local LaunchEvents g_launch_ev;
 thread_local hipEvent_t g_launch_taken = nullptr;
 static int g_gemm_split = -1;   // -1: not decided yet (environment, else the default)

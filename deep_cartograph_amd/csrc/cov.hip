@@ -5,7 +5,6 @@
 // same matrix `lag` rows further down -- pairing costs no bytes (the reference materialises two
 // copies, cv_calculator.py:2247).
 #include "gemm_kernels.h"
-#include <stdlib.h>
 
 namespace dcv {
 
@@ -25,7 +24,7 @@ struct CovPlan {
 static CovPlan cov_plan(int64_t n_pairs, int F, int lag) {
     CovPlan p;
     p.nb = lag > 0 ? 2 : 1;
-    static const int64_t chunk_env = [] { const char* e = getenv("DCV_COV_CHUNK"); return e ? (int64_t)atoll(e) : (int64_t)0; }();   // diagnostic override
+    static const int64_t chunk_env = env_int("DCV_COV_CHUNK", 0);   // diagnostic override
     p.k_chunk = chunk_env >= 64 ? chunk_env / 32 * 32 : kCovChunkRows;
     const size_t per_split = (size_t)p.nb * F * F * sizeof(float);
     while (cdiv(n_pairs, p.k_chunk) * per_split > kCovMaxSlabBytes) p.k_chunk *= 2;
@@ -130,7 +129,7 @@ extern "C" int dcv_lagged_cov(const float* X_d, int64_t n_pairs, int32_t F, int6
     float* asum = reinterpret_cast<float*>(ws + p.stats_ws + p.sums + p.slab);
     // With a shift (the standardised / centred case) the column sums of z_t fall out of the covariance kernel itself;
     // without one the values are not centred and a float32 chunk sum would cost digits: the float64 statistics pass stays.
-    static const bool fuse_off = [] { const char* e = getenv("DCV_COV_FUSED_SUMS"); return e && e[0] == '0'; }();
+    static const bool fuse_off = env_is("DCV_COV_FUSED_SUMS", '0');
     const bool fused_sums = shift_d != nullptr && !fuse_off;
     int rc = DCV_OK;
     if (!fused_sums) {

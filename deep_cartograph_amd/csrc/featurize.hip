@@ -92,8 +92,7 @@ extern "C" int dcv_featurize(const float* xyz_d, int64_t n_frames, int64_t frame
     DCV_REQUIRE(xyz_d && defs_h && out_d && n_frames >= 0 && n_atoms > 0 && n_defs > 0 && ldo > 0,
                 "dcv_featurize: bad arguments (n_frames=%lld n_atoms=%d n_defs=%d ldo=%lld)", (long long)n_frames, n_atoms, n_defs,
                 (long long)ldo);
-    DCV_REQUIRE(frame_stride >= 0 && atom_stride >= 1 && comp_stride >= 1, "dcv_featurize: strides (%lld, %lld, %lld): the frame stride must be >= 0, the atom and component strides >= 1",
-                (long long)frame_stride, (long long)atom_stride, (long long)comp_stride);
+    DCV_REQUIRE_COORD_STRIDES("dcv_featurize", frame_stride, atom_stride, comp_stride);
     // ---- validate every record before anything is launched
     std::vector<char> is_used((size_t)n_atoms, 0);
     for (int32_t d = 0; d < n_defs; ++d) {
@@ -121,9 +120,7 @@ extern "C" int dcv_featurize(const float* xyz_d, int64_t n_frames, int64_t frame
     stage_plan(is_used, n_atoms, atom_stride, comp_stride, a.st, plan);
     const std::vector<int32_t>&used = plan.used, &slot = plan.slot;
     const int64_t per_frame = plan.per_frame;
-    DCV_REQUIRE(per_frame * (int64_t)sizeof(float) <= kStageLdsMax,
-                "dcv_featurize: one frame of the %lld atoms to stage exceeds %d bytes of LDS (at most %d atoms)", (long long)(per_frame / 3),
-                kStageLdsMax, kStageLdsMax / 12);
+    DCV_REQUIRE_STAGE_FITS("dcv_featurize", per_frame);
     a.st.tile = stage_tile_frames(per_frame, 0, 0);
     const int64_t blocks = cdiv(n_frames, a.st.tile);
     DCV_REQUIRE(blocks <= 0x7fffffffLL, "dcv_featurize: %lld frames need more than 2^31 - 1 workgroups", (long long)n_frames);
@@ -144,10 +141,7 @@ extern "C" int dcv_featurize(const float* xyz_d, int64_t n_frames, int64_t frame
     DCV_CHECK_HIP(hipMemcpyAsync(defs_d, rec.data(), rec.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     DCV_CHECK_HIP(hipMemcpyAsync(used_d, used.data(), used.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
 
-    a.st.xyz = xyz_d;
-    a.st.frame_stride = frame_stride; a.st.atom_stride = atom_stride; a.st.comp_stride = comp_stride;
-    a.st.n_frames = n_frames;
-    a.st.used = used_d;
+    stage_source(a.st, xyz_d, frame_stride, atom_stride, comp_stride, n_frames, used_d);
     a.defs = defs_d;
     a.n_defs = n_defs;
     a.unit = unit;

@@ -9,15 +9,10 @@
 // Dip: one lane per column, columns adjacent in memory (n x C row-major), float64 arithmetic on the float32
 // values, no fused multiply-adds, so the statistic is the one a float64 host implementation of AS 217 gives.
 // The hull scans keep the top of each lane's vertex stack in LDS.
-#include "common.h"
+// The histogram's loads, its walk over a block's rows and the rule for 16-byte accesses are stream.h's.
+#include "stream.h"
 
 namespace dcv {
-
-__device__ __forceinline__ float4 hist_nt_load4(const float* p) {
-    typedef float nv4 __attribute__((ext_vector_type(4)));
-    const nv4 v = __builtin_nontemporal_load(reinterpret_cast<const nv4*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
 
 constexpr int kHistThreads = 256;
 constexpr int kHistCols = 64;      // columns per workgroup: 64 x (bins + 1) counters and edges in LDS (51.7 KB at 100 bins)
@@ -49,8 +44,7 @@ __global__ __launch_bounds__(kHistThreads) void col_histogram_kernel(const float
     constexpr int RL = kHistThreads / G;     // row lanes
     const int cg = t % G, rl = t / G;
     const int col = cg * VEC;
-    const int64_t r_begin = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r_end = r_begin + rows_per_block < n ? r_begin + rows_per_block : n;
+    const Range rows = block_rows(n, rows_per_block);
     if (col < nc) {
         float first[VEC], last[VEC], scale[VEC];
 #pragma unroll
@@ -68,34 +62,7 @@ __global__ __launch_bounds__(kHistThreads) void col_histogram_kernel(const float
             while (i < bins - 1 && x >= e[i + 1]) ++i;        // the last bin is closed on the right
             atomicAdd(&s_cnt[(col + v) * stride + i], 1u);
         };
-        const float* base = X + c0 + col;
-        int64_t r = r_begin + rl;
-        for (; r + 3 * (int64_t)RL < r_end; r += 4 * (int64_t)RL) {   // 4 independent row loads in flight
-            float x[4][VEC];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float* p = base + (r + (int64_t)u * RL) * ld;
-                if constexpr (VEC == 4) {
-                    const float4 q = hist_nt_load4(p);
-                    x[u][0] = q.x; x[u][1] = q.y; x[u][2] = q.z; x[u][3] = q.w;
-                } else {
-                    x[u][0] = *p;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) count(x[u][v], v);
-        }
-        for (; r < r_end; r += RL) {
-            const float* p = base + r * ld;
-            if constexpr (VEC == 4) {
-                const float4 q = hist_nt_load4(p);
-                count(q.x, 0); count(q.y, 1); count(q.z, 2); count(q.w, 3);
-            } else {
-                count(*p, 0);
-            }
-        }
+        stream_rows<VEC, 4>(X + c0 + col, ld, rows.begin + rl, rows.end, RL, count);   // 4 independent row loads in flight
     }
     __syncthreads();
     for (int i = t; i < nc * bins; i += kHistThreads) {
@@ -354,8 +321,7 @@ extern "C" int dcv_col_histogram(const float* X_d, int64_t n, int32_t F, int64_t
     nb = cdiv(n, rpb);
     const size_t lds = (size_t)kHistCols * hist_stride(bins) * (sizeof(unsigned int) + sizeof(float));
     unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts_d);
-    const bool v4 = (F % 4 == 0) && (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(X_d) & 15) == 0);
-    if (v4)
+    if (quad_path(X_d, F, ld))
         hipLaunchKernelGGL(col_histogram_kernel<4>, dim3((unsigned)nb, ncb), dim3(kHistThreads), lds, s, X_d, n, F, ld, edges_d, bins, cnt, rpb);
     else
         hipLaunchKernelGGL(col_histogram_kernel<1>, dim3((unsigned)nb, ncb), dim3(kHistThreads), lds, s, X_d, n, F, ld, edges_d, bins, cnt, rpb);

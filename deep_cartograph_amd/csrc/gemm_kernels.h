@@ -320,8 +320,6 @@ struct EpiSlabSum : EpiSlab {
     float* asum = nullptr;
 };
 
-inline bool quad_ok(const void* p, int64_t ld) { return (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(p) & 15) == 0); }
-
 // ------------------------------------------------------------------ kernels
 // XCD-aware block -> (tile, split) map.  Blocks b and b + 8 are observed to share an XCD (and its
 // L2); the workgroups that read the same rows -- the column tiles of one row tile (NT / NN), the
@@ -515,11 +513,11 @@ inline bool alloc_tail_ws(TailWs* tw, int max_tiles_n) {
 #define DCV_TAIL_MINSTAGES 2   // stages per tail chunk
 #endif
 inline int xcd_remap_enabled() {   // DCV_XCD_REMAP=0: plain block -> tile order
-    static const int env = [] { const char* e = getenv("DCV_XCD_REMAP"); return e ? atoi(e) : 1; }();
+    static const int env = (int)env_int("DCV_XCD_REMAP", 1);
     return env;
 }
 inline bool tail_split_enabled() {
-    static const bool on = [] { const char* e = getenv("DCV_TAIL_KSPLIT"); return !(e && e[0] == '0'); }();
+    static const bool on = env_not("DCV_TAIL_KSPLIT", '0');
     return on;
 }
 
@@ -549,7 +547,7 @@ static int prepare_gemm(const Operand& A, const Operand& B, int64_t M, int64_t N
         // from memory either way, and a launch that ends without dirty lines skips the L2 write-back in front of its
         // successor (contract batch: 105.0 -> 101.9 us per step; neutral at the large batch and on the covariance slabs,
         // which stay write-back).  DCV_WT=0 restores plain stores.
-        static const int wt_env = [] { const char* e = getenv("DCV_WT"); return e ? atoi(e) : 1; }();
+        static const int wt_env = (int)env_int("DCV_WT", 1);
         const int64_t out_bytes = nsplit * M * N * (int64_t)sizeof(float) * NB;
         d.wt = (wt_env != 0 && out_bytes <= (256ll << 20)) ? 1 : 0;
         // bijective only when the remapped index is a multiple of 8
@@ -624,7 +622,7 @@ static CfgPick pick_cfg(int64_t M, int64_t N, int64_t K, int64_t k_chunk) {
             // between one and two 64 x 128 workgroups per CU (8202 rows x 256 columns: 258): 64 x 64 tiles put two waves on
             // every SIMD, which overlap each other's split and MFMA phases (measured 22.8 -> 20.8 us at 8192 x 256 x 512)
             if constexpr (!HEAD) {
-                static const bool quarter_off = [] { const char* e = getenv("DCV_NO_QUARTER_NT"); return e && e[0] == '1'; }();
+                static const bool quarter_off = env_is("DCV_NO_QUARTER_NT", '1');
                 if (!quarter_off && N % 64 == 0) return kPickQuarter;
             }
             return kPickHalfM;
@@ -679,7 +677,7 @@ static int launch_gemm(const Operand& A, const Operand& B, int64_t M, int64_t N,
 // ---- grouped NT products (gemm_group_kernel)
 // (diagnostic) DCV_EVAL_GROUP_TILES=0: every member keeps the tile family of the single-batch launch
 inline bool group_retile_enabled() {
-    static const bool on = [] { const char* e = getenv("DCV_EVAL_GROUP_TILES"); return !(e && e[0] == '0'); }();
+    static const bool on = env_not("DCV_EVAL_GROUP_TILES", '0');
     return on;
 }
 // `members` products of M rows each.  Every member must come out bit for bit as launch_gemm<kNT, Epi>(A, B, M, N, K) leaves
@@ -786,8 +784,7 @@ inline Operand make_operand(const float* p, int64_t ld, int64_t inner_extent, co
     o.rows = rows;
     o.shift = shift;
     (void)inner_extent;
-    o.vec_ok = (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(p) & 15) == 0) &&
-               (shift == nullptr || (reinterpret_cast<uintptr_t>(shift) & 15) == 0);
+    o.vec_ok = quad_ok(p, ld) && aligned16(shift);   // no shift: a null pointer is aligned
     return o;
 }
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "common.h"
+#include "stage.h"   // DCV_REQUIRE_COORD_STRIDES
 
 namespace dcv {
 
@@ -325,9 +326,7 @@ extern "C" int dcv_interpolate(const float* xyz_d, int64_t n_knots, int64_t fram
     DCV_REQUIRE(n_knots >= (kind == DCV_INTERP_MAKIMA ? 3 : 2), "dcv_interpolate: %lld knots, %s needs at least %d", (long long)n_knots,
                 kind == DCV_INTERP_MAKIMA ? "makima" : "pchip", kind == DCV_INTERP_MAKIMA ? 3 : 2);
     DCV_REQUIRE(!sel_h || n_sel >= 1, "dcv_interpolate: a selection of %d atoms", n_sel);
-    DCV_REQUIRE(frame_stride >= 0 && atom_stride >= 1 && comp_stride >= 1,
-                "dcv_interpolate: strides (%lld, %lld, %lld): the frame stride must be >= 0, the atom and component strides >= 1",
-                (long long)frame_stride, (long long)atom_stride, (long long)comp_stride);
+    DCV_REQUIRE_COORD_STRIDES("dcv_interpolate", frame_stride, atom_stride, comp_stride);
     DCV_REQUIRE(out_frame_stride >= 1 && out_atom_stride >= 1 && out_comp_stride >= 1,
                 "dcv_interpolate: output strides (%lld, %lld, %lld) must all be >= 1", (long long)out_frame_stride,
                 (long long)out_atom_stride, (long long)out_comp_stride);

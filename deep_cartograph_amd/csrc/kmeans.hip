@@ -6,7 +6,7 @@
 // blocks in block order, and each thread walks its points in increasing index order.
 //
 // Layout.  What the other float64 point kernels use as well lives in points.h: point_blocks (the grid), block_range (a
-// block's points), load_point (runtime d and <D>), block_sum (the 256-value LDS tree), sum_blocks (the final sum over the
+// block's points; common.h), load_point (runtime d and <D>), block_sum (the 256-value LDS tree), sum_blocks (the final sum over the
 // blocks, defined here) and take_min / wave_min (the (distance, row) minimum).  The shared device pieces of this file come
 // first, ONE copy each: glds_stream (LDS-DMA) and the two point streams reg_stream (registers: two alternating batches, the
 // D == 4 pair path) and ring_stream (per-wave LDS-DMA ring), which both call a per-point f(x, i, old).  The kernels pass what differs between them as template parameters and
@@ -14,7 +14,6 @@
 // "choose kernel, blocks and LDS; launch; final".
 #include "gemm_kernels.h"   // butterfly_sum
 #include "points.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace dcv {
@@ -767,12 +766,8 @@ struct Pick {   // a kernel and the dynamic LDS it is launched with; fn == nullp
     Fn fn;
     size_t lds;
 };
-static bool env_starts_with(const char* name, char c) {   // callers keep the answer in a static: every flag is read once
-    const char* e = getenv(name);
-    return e && e[0] == c;
-}
 static bool km_ring_enabled() {
-    static const bool on = !env_starts_with("DCV_KM_RING", '0');
+    static const bool on = env_not("DCV_KM_RING", '0');
     return on;
 }
 
@@ -825,7 +820,7 @@ extern "C" int dcv_kmeans_step(const double* P_d, int64_t n, int32_t d, const do
     int nb = point_blocks(n);
     const int W = k * d + k;
     double* part = static_cast<double*>(ws_d);
-    static const bool no_reg = env_starts_with("DCV_KMEANS_ATOMIC", '1');   // diagnostic: general kernel
+    static const bool no_reg = env_is("DCV_KMEANS_ATOMIC", '1');   // diagnostic: general kernel
     const KmRegPick reg = no_reg ? KmRegPick{} : km_reg_pick(d, k, km_ring_enabled() && mindist_d == nullptr);
     if (reg.fn) {
         // One round of the chip: the register kernel holds ~150 VGPRs (3 blocks per CU), and 1024 equal blocks on 768
@@ -864,7 +859,7 @@ extern "C" int dcv_nearest_rows(const double* P_d, int64_t n, int32_t d, const d
     const int nb = point_blocks(n);
     double* pdist = static_cast<double*>(ws_d);
     int64_t* prow = reinterpret_cast<int64_t*>(pdist + (size_t)kKmMaxBlocks * k);
-    static const bool multi_off = env_starts_with("DCV_NEAREST_PER_CENTROID", '1');
+    static const bool multi_off = env_is("DCV_NEAREST_PER_CENTROID", '1');
     const NearPick multi = multi_off ? NearPick{} : near_multi_pick(d, k, km_ring_enabled());
     if (multi.fn)   // one pass over the points per chunk of kNearKC centroids
         hipLaunchKernelGGL(multi.fn, dim3(nb, (unsigned)cdiv(k, kNearKC)), dim3(kKmThreads), multi.lds, s, P_d, n, centers_d, (int)k, pdist, prow);

@@ -135,7 +135,7 @@ static void wgrad_plan(int out, int in, int64_t rows, int64_t* k_chunk, int64_t*
     // slabs of 512 KB per step -- 32 MB written and re-read by the reduction, 11.4 us -- where 16 chunks of 64 x 64 tiles leave
     // 8 MB): the reduction fell to 7.0 us, but the GATHERED weight gradient went from 38.7 to 60.0 us (per-thread 64-bit row
     // pointers: four times the stage loads per flop of the 128 x 128 tile) -- kept behind DCV_WGRAD_Q=1, off by default.
-    static const bool q_wide = [] { const char* e = getenv("DCV_WGRAD_Q"); return e && e[0] == '1'; }();   // opt-in: see below
+    static const bool q_wide = env_is("DCV_WGRAD_Q", '1');   // opt-in: see below
     const int64_t tiles_q = cdiv(out, 64) * cdiv(in, 64);
     const int64_t want_q = cdiv(cdiv(2 * (int64_t)num_cus(), tiles_q), 8) * 8;
     if (out > 32 && in > 32 && want_q <= max_by_rows) {
@@ -360,7 +360,7 @@ extern "C" int dcv_mlp_create(const dcv_mlp_desc* desc, dcv_mlp** out) {
     for (int l = 0; l < m->L; ++l) m->any_drop = m->any_drop || desc->dropout[l] > 0.f;
     m->vae_d = desc->model == DCV_MODEL_VAE ? desc->dims[desc->latent_layer] / 2 : 0;
     m->ld_z = align_up((size_t)(m->vae_d > 0 ? m->vae_d : 1), 4);
-    static const bool graph_env = [] { const char* e = getenv("DCV_GRAPH"); return e && e[0] == '1'; }();
+    static const bool graph_env = env_is("DCV_GRAPH", '1');
     m->graph_on = graph_env;
     plan_layers(m);
     rc = alloc_buffers(m);
@@ -569,7 +569,7 @@ extern "C" int dcv_mlp_read_log(dcv_mlp* m, double* out_h, int32_t max_records, 
 namespace dcv {
 
 static bool act_mask_enabled() {
-    static const bool off = [] { const char* e = getenv("DCV_NO_ACT_MASK"); return e && e[0] == '1'; }();
+    static const bool off = env_is("DCV_NO_ACT_MASK", '1');
     return !off;
 }
 

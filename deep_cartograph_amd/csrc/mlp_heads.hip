@@ -731,8 +731,7 @@ static size_t head_lds_bytes(int D, int K) {
     return (size_t)(2 * D + 2 * D * D) * sizeof(double) + ((size_t)groups * 4 * D + (size_t)groups * ((size_t)(D + 1) * K + D)) * sizeof(float);
 }
 bool head_fusable(const dcv_mlp* m) {
-    static const bool off = [] { const char* e = getenv("DCV_NO_HEAD_FUSION"); return e && e[0] == '1'; }();
-    if (off || m->L < 2 || m->any_bn) return false;
+    if (head_fusion_off() || m->L < 2 || m->any_bn) return false;
     if (m->desc.dropout[m->L - 1] > 0.f) return false;   // dropout on the network output: general kernels
     const LayerPlan& p = m->layers[m->L - 1];
     const LayerPlan& q = m->layers[m->L - 2];

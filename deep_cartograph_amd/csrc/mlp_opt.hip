@@ -154,7 +154,7 @@ static ReduceSet reduce_set(const dcv_mlp* m, const ReduceArgs& ra_all, int l0, 
     return rs;
 }
 static bool quad_takes(const ReduceSet& rs) {
-    static const bool quad_off = [] { const char* e = getenv("DCV_REDUCE_QUAD"); return e && e[0] == '0'; }();
+    static const bool quad_off = env_is("DCV_REDUCE_QUAD", '0');
     return rs.max_splits <= 512 && rs.max_bblocks <= 1024 && !quad_off;
 }
 // The items of the flat-grid reduction in the set's order (weights, then biases, of every entry).  part: 0 = all of them,
@@ -368,7 +368,7 @@ int reduce_upper(dcv_mlp* m, const ReduceArgs& ra, bool fuse_opt, bool* done, hi
 // Returns 1 when it does not apply (nothing was launched, no state was touched: the caller launches the product alone).
 int ride_upper(dcv_mlp* m, const ReduceArgs& ra, const Operand& A, const Operand& B, int64_t M, int64_t N, int64_t K, int64_t k_chunk,
                const EpiSlab& epi, OptArgs* oa, hipStream_t s) {
-    static const bool off = [] { const char* e = getenv("DCV_NO_REDUCE_RIDE"); return e && e[0] == '1'; }();
+    static const bool off = env_is("DCV_NO_REDUCE_RIDE", '1');
     if (off || m->upper_cb || m->L < 2) return 1;
     const ReduceSet rs = reduce_set(m, ra, 0, m->L);
     if (!quad_takes(rs) || !wgrad_reduce_applies(A, B, M, N, K, k_chunk)) return 1;

@@ -274,9 +274,12 @@ int dmalloc(T** p, size_t count) {
 }
 
 // layer l + 1 can ride in the epilogue of layer l: it is narrow and layer l's output fits one column tile
+inline bool head_fusion_off() {   // DCV_NO_HEAD_FUSION=1: neither the forward nor the backward fusion of a narrow layer
+    static const bool off = env_is("DCV_NO_HEAD_FUSION", '1');
+    return off;
+}
 inline bool next_layer_fusable(const dcv_mlp* m, int l) {
-    static const bool off = [] { const char* e = getenv("DCV_NO_HEAD_FUSION"); return e && e[0] == '1'; }();
-    if (off || l + 1 >= m->L || m->any_bn) return false;
+    if (head_fusion_off() || l + 1 >= m->L || m->any_bn) return false;
     if (m->desc.dropout[l + 1] > 0.f) return false;
     if (m->vae_d > 0 && l + 1 == m->desc.latent_layer) return false;   // the first decoder Linear reads z, sampled in between
     return m->layers[l + 1].out <= 8 && m->layers[l].out <= 128;

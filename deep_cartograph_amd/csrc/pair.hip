@@ -57,7 +57,7 @@ static int launch_pair_mode(const Operand& A1, const Operand& B1, int64_t M1, in
 int launch_wgrad_dgrad(const Operand& A1, const Operand& B1, int64_t M1, int64_t N1, int64_t K1, int64_t k_chunk1, const EpiSlab& e1,
                        const Operand& A2, const Operand& B2, int64_t M2, int64_t N2, int64_t K2, const EpiActGrad& e2, int* tiles_m_out2,
                        const TailWs* tw, hipStream_t s) {
-    static const bool off = [] { const char* e = getenv("DCV_NO_PAIR"); return e && e[0] == '1'; }();
+    static const bool off = env_is("DCV_NO_PAIR", '1');
     if (off) return 1;
     if (gemm_split()) return launch_pair_mode<true>(A1, B1, M1, N1, K1, k_chunk1, e1, A2, B2, M2, N2, K2, e2, tiles_m_out2, tw, s);
     return launch_pair_mode<false>(A1, B1, M1, N1, K1, k_chunk1, e1, A2, B2, M2, N2, K2, e2, tiles_m_out2, tw, s);

@@ -60,16 +60,6 @@ __device__ __forceinline__ void load_point(const double* __restrict__ P, int64_t
     }
 }
 
-// the block's contiguous range of points [begin, end)
-struct Range {
-    int64_t begin, end;
-};
-__device__ __forceinline__ Range block_range(int64_t n) {
-    const int64_t per_block = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t begin = (int64_t)blockIdx.x * per_block;
-    return {begin, begin + per_block < n ? begin + per_block : n};
-}
-
 // s_red[0] = the sum of the block's 256 values v by a fixed LDS tree (pairs 128 apart, then 64, ...), valid after the call
 __device__ __forceinline__ void block_sum(double v, double (&s_red)[kPtThreads], int t) {
     s_red[t] = v;

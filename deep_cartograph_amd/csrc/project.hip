@@ -3,8 +3,8 @@
 // 16 lanes share a row (16-byte loads, 256 contiguous bytes per row segment), each lane keeps
 // 4 rows in flight so that the LDS-resident weights are read once per 4 rows; the 16 partial
 // dot products are combined with wave shuffles.  Per-column extrema of the output are reduced
-// per block and combined in a fixed order.
-#include "common.h"
+// per block and combined in a fixed order.  The 16-byte load and the host's rule for it are stream.h's.
+#include "stream.h"
 
 namespace dcv {
 
@@ -89,10 +89,7 @@ __global__ __launch_bounds__(kProjThreads) void project_kernel(ProjArgs a) {
             for (int u = 0; u < kRowsInFlight; ++u) {
                 if constexpr (VEC == 4) {
                     // unconditional (rows past the end re-read row 0 and are never stored) and non-temporal: the matrix is streamed once
-                    typedef float nv4 __attribute__((ext_vector_type(4)));
-                    const nv4 qv = __builtin_nontemporal_load(reinterpret_cast<const nv4*>(rowp[u] + col));
-                    const float4 q = make_float4(qv.x, qv.y, qv.z, qv.w);
-                    x[u][0] = q.x; x[u][1] = q.y; x[u][2] = q.z; x[u][3] = q.w;
+                    load_group<4>(rowp[u] + col, x[u]);
                 } else {
                     x[u][0] = rok[u] ? rowp[u][col] : 0.f;
                 }
@@ -256,7 +253,7 @@ extern "C" int dcv_project_linear(const float* X_d, int64_t n, int32_t F, int64_
     ProjArgs a{X_d, n, F, ld, fmean_d, frange_d, W_d, d, bias_d, cvmean_d, cvrange_d, out_d,
                minmax_d ? static_cast<float*>(ws_d) : nullptr};
     const int nb = proj_blocks(n);
-    const bool vec4 = (F % 4 == 0) && (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(X_d) & 15) == 0);
+    const bool vec4 = quad_path(X_d, F, ld);
     if (d <= 2) return launch_project<2>(a, nb, vec4, minmax_d, s);
     if (d <= 4) return launch_project<4>(a, nb, vec4, minmax_d, s);
     if (d <= 8) return launch_project<8>(a, nb, vec4, minmax_d, s);

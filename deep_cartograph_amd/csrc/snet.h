@@ -495,7 +495,7 @@ inline int snet_launch(K kern, int& attr_state, size_t lds_max, size_t lds_bytes
 }
 
 inline bool snet_disabled() {
-    static const bool off = [] { const char* e = getenv("DCV_NO_SNET"); return e && e[0] == '1'; }();
+    static const bool off = env_is("DCV_NO_SNET", '1');
     return off;
 }
 

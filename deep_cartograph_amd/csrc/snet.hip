@@ -361,7 +361,7 @@ static size_t snet_ae_map(SnetArgs& a, int L, int fl, int TR) {
 // workgroups), the larger tile beyond.  The choice depends on the rows of ONE batch only: a batched validation pass tiles its
 // batches as the single steps would, so its records stay bit-equal to theirs.
 static int snet_ae_pick_tr(const SnetPlan* pl, int64_t R) {
-    static const int tr_env = [] { const char* e = getenv("DCV_SNET_TR"); return e ? atoi(e) : 0; }();   // 16 | 32: force the rows per workgroup
+    static const int tr_env = (int)env_int("DCV_SNET_TR", 0);   // 16 | 32: force the rows per workgroup
     if ((tr_env == 16 || tr_env == 32) && tr_env <= pl->tr_max) return tr_env;
     if (pl->tr_max == 32) {
         if (cdiv(R, 16) <= 128) return 16;
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(256) void snet_pack_kernel(const float* __restrict_
     }
 }
 bool snet_image_build(dcv_mlp* m) {
-    static const bool off = [] { const char* e = getenv("DCV_SNET_IMG"); return e && e[0] == '0'; }();
+    static const bool off = env_is("DCV_SNET_IMG", '0');
     if (off) return false;
     if (m->snet_img != nullptr) return true;
     SnetLayer ly[DCV_MAX_LAYERS];

@@ -437,13 +437,13 @@ static int snet_dt_map(SnetDtArgs& a, int fl, int TR) {
 // input units per thread (pin <= 64 * 32 / TR ... i.e. always for pin <= 256 at TR = 32, pin <= 256 at 64 and 128 too since
 // the unit count per thread grows with TR) and the activation map fits in LDS
 static int snet_dt_pick_tr(const SnetDtPlan* pl, int64_t B) {
-    static const int tr_env = [] { const char* e = getenv("DCV_SNET_TR"); return e ? atoi(e) : 0; }();
+    static const int tr_env = (int)env_int("DCV_SNET_TR", 0);
     int best = 0;
     // 16-row tiles (8 pairs per workgroup) up to 1024 pairs: a shorter latency chain per workgroup while the twice-as-many
     // partials stay cheap.  A/B on one box, 54-16-8-2, contiguous batches (tools/dbg/dt_tr_probe.py): 24.2 -> 23.2 us per step
     // at 64 pairs, 24.7 -> 23.7 at 128, 25.5 -> 23.9 at 256, 25.4 -> 24.6 at 512, 26.1 -> 24.7 at 1024, and 26.1 -> 26.8
     // (slower) at 2048; the gathered batch of 128 of bench.py's ref_small block: 29.1 -> 27.2.  DCV_SNET_DT16=0 turns them off.
-    static const bool dt16 = [] { const char* e = getenv("DCV_SNET_DT16"); return !(e && e[0] == '0'); }();
+    static const bool dt16 = env_not("DCV_SNET_DT16", '0');
     // (128-64-32-4 on the same box, 16 | 32 rows: 25.8 | 28.0 at 128 pairs, 27.9 | 29.3 at 1024 -- 5.4 MB of partials and still ahead --
     // 32.4 | 30.4 at 2048, 53 | 35 at 4096: two rounds of the chip)
     if (tr_env == 16 || (tr_env == 0 && dt16 && cdiv(B, 8) <= 128)) {

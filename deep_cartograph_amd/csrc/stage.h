@@ -10,10 +10,12 @@
 //   GATHER  everything else (any strides, a sparse subset of an all-atom trajectory): one 4-byte load per coordinate
 //           of a used atom, lanes along the sorted list of used atoms, nothing else is read.
 // In LDS, coordinate c of the atom in slot s of frame f of the tile is lds[f * lfs + s * las + c * lcs].
+// The 16-byte load is stream.h's.  The host preamble the coordinate entries share is at the end: the stride requirement
+// (dcv_interpolate's too), the refusal of a frame that LDS cannot hold, and the source fields of StageArgs.
 #pragma once
 #include <vector>
 
-#include "common.h"
+#include "stream.h"
 
 namespace dcv {
 
@@ -36,12 +38,6 @@ struct StageArgs {
     int32_t lfs, las, lcs; // LDS strides of frame, atom slot, component
     int32_t tile;          // frames per workgroup
 };
-
-__device__ __forceinline__ float4 stage_nt_load4(const float* p) {
-    typedef float nv4 __attribute__((ext_vector_type(4)));
-    const nv4 v = __builtin_nontemporal_load(reinterpret_cast<const nv4*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
 
 // Contiguous rows -> LDS.  A slot is one 16-byte-aligned group of four floats of the address space; slot k of a row
 // that starts m floats past such a boundary holds row elements 4k - m .. 4k - m + 3.  Four slots per thread are in
@@ -69,7 +65,7 @@ __device__ __forceinline__ void stage_rows(const StageArgs& a, int64_t f0, int n
             const int j = 4 * k - m;
             if (j >= a.L) continue;   // this row has fewer slots than nsmax
             j0[u] = j;
-            if (j >= 0 && j + 4 <= a.L) v[u] = stage_nt_load4(g[u] + j);
+            if (j >= 0 && j + 4 <= a.L) v[u] = nt_load4(g[u] + j);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -148,5 +144,26 @@ inline int stage_tile_frames(int64_t per_frame, int64_t bytes_per_frame_extra, i
     const int64_t tile = (kStageLdsBudget - fixed_bytes) / per;
     return tile < 1 ? 1 : (tile > kStageTile ? kStageTile : (int)tile);
 }
+
+// where the coordinates come from: everything of `a` that stage_plan and the choice of the tile leave open
+inline void stage_source(StageArgs& a, const float* xyz, int64_t frame_stride, int64_t atom_stride, int64_t comp_stride, int64_t n_frames,
+                         const int32_t* used_d) {
+    a.xyz = xyz;
+    a.frame_stride = frame_stride; a.atom_stride = atom_stride; a.comp_stride = comp_stride;
+    a.n_frames = n_frames;
+    a.used = used_d;
+}
+
+// the strides every coordinate entry accepts; `entry` is the entry's name, a string literal
+#define DCV_REQUIRE_COORD_STRIDES(entry, frame_stride, atom_stride, comp_stride)                                                  \
+    DCV_REQUIRE((frame_stride) >= 0 && (atom_stride) >= 1 && (comp_stride) >= 1,                                                  \
+                entry ": strides (%lld, %lld, %lld): the frame stride must be >= 0, the atom and component strides >= 1",         \
+                (long long)(frame_stride), (long long)(atom_stride), (long long)(comp_stride))
+
+// one frame of the staged atoms (StagePlan::per_frame floats) must fit the LDS of a workgroup
+#define DCV_REQUIRE_STAGE_FITS(entry, per_frame)                                                                                  \
+    DCV_REQUIRE((per_frame) * (int64_t)sizeof(float) <= dcv::kStageLdsMax,                                                        \
+                entry ": one frame of the %lld atoms to stage exceeds %d bytes of LDS (at most %d atoms)", (long long)((per_frame) / 3), \
+                dcv::kStageLdsMax, dcv::kStageLdsMax / 12)
 
 }  // namespace dcv

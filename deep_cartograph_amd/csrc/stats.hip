@@ -1,21 +1,10 @@
 // Column statistics and normalisation: HBM-bound streaming passes over the frames x features
 // matrix.  Lanes run along the feature axis (16-byte loads, whole rows per wave), rows are
 // strided over the block; partial results per block are combined in a fixed order, so the
-// result is deterministic.
-#include "common.h"
-#include <stdlib.h>
+// result is deterministic.  The loads, the walk over a block's rows and the rule for 16-byte accesses are stream.h's.
+#include "stream.h"
 
 namespace dcv {
-
-// 16-byte non-temporal load: the feature matrix is streamed once per pass (round 4: the same policy took the k-means point
-// stream from 4.6 to 5.7 TB/s, the normalisation +2.7 %); DCV_STREAM_NT=0 at run time restores plain loads where a kernel
-// offers the switch
-__device__ __forceinline__ float4 nt_load4(const float* p) {
-    typedef float nv4 __attribute__((ext_vector_type(4)));
-    const nv4 v = __builtin_nontemporal_load(reinterpret_cast<const nv4*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-
 
 constexpr int kStatsThreads = 256;
 constexpr int kStatsMaxBlocks = 2048;
@@ -51,10 +40,7 @@ __global__ __launch_bounds__(kStatsThreads) void col_stats_kernel(const float* _
     float* s_mn = reinterpret_cast<float*>(s_sq + kStatsThreads * VEC);
     float* s_mx = s_mn + kStatsThreads * VEC;
 
-    // contiguous block of rows per workgroup
-    const int64_t rows_per_block = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t r_begin = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r_end = r_begin + rows_per_block < n ? r_begin + rows_per_block : n;
+    const Range rows = block_range(n);
     double* my_part = part + (int64_t)blockIdx.x * 4 * F;
 
     for (int cb = 0; cb < g.ncb; ++cb) {
@@ -69,52 +55,14 @@ __global__ __launch_bounds__(kStatsThreads) void col_stats_kernel(const float* _
             mn[v] = INFINITY;
             mx[v] = -INFINITY;
         }
-        if (col_ok) {
-            const float* base = X + col;
-            int64_t r = r_begin + rl;
-            // 4 independent row loads in flight
-            for (; r + 3 * (int64_t)g.rpp < r_end; r += 4 * (int64_t)g.rpp) {
-                float x[4][VEC];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float* p = base + (r + (int64_t)u * g.rpp) * ld;
-                    if constexpr (VEC == 4) {
-                        const float4 q = nt_load4(p);
-                        x[u][0] = q.x; x[u][1] = q.y; x[u][2] = q.z; x[u][3] = q.w;
-                    } else {
-                        x[u][0] = *p;
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) {
-                        const double d = (double)x[u][v];
-                        sum[v] += d;
-                        sq[v] = fma(d, d, sq[v]);
-                        mn[v] = fminf(mn[v], x[u][v]);
-                        mx[v] = fmaxf(mx[v], x[u][v]);
-                    }
-            }
-            for (; r < r_end; r += g.rpp) {
-                const float* p = base + r * ld;
-                float x[VEC];
-                if constexpr (VEC == 4) {
-                    const float4 q = nt_load4(p);
-                    x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
-                } else {
-                    x[0] = *p;
-                }
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) {
-                    const double d = (double)x[v];
-                    sum[v] += d;
-                    sq[v] = fma(d, d, sq[v]);
-                    mn[v] = fminf(mn[v], x[v]);
-                    mx[v] = fmaxf(mx[v], x[v]);
-                }
-            }
-        }
+        if (col_ok)   // 4 independent row loads in flight
+            stream_rows<VEC, 4>(X + col, ld, rows.begin + rl, rows.end, g.rpp, [&](float x, int v) {
+                const double d = (double)x;
+                sum[v] += d;
+                sq[v] = fma(d, d, sq[v]);
+                mn[v] = fminf(mn[v], x);
+                mx[v] = fmaxf(mx[v], x);
+            });
         __syncthreads();
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
@@ -229,8 +177,8 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __rest
     const int t = threadIdx.x, tx = t % ng, ty = t / ng, lanes = 256 / ng;
     const float4 m = *reinterpret_cast<const float4*>(mean + 4 * tx);
     const float4 s = *reinterpret_cast<const float4*>(range + 4 * tx);
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
+    const Range rows = block_rows(n, rows_per_block);
+    const int64_t r0 = rows.begin, r1 = rows.end;
     // Two alternating batches of U rows per thread: the loads of the next batch are issued before this one is divided and
     // stored (a batch at a time left every wave with nothing in flight during its 50 division instructions per float4), and
     // they are UNCONDITIONAL loads from clamped rows -- a load inside a branch makes hipcc put s_waitcnt vmcnt(0) behind
@@ -255,12 +203,8 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __rest
                 y.y = __fdiv_rn(__fsub_rn(x[u].y, m.y), s.y);
                 y.z = __fdiv_rn(__fsub_rn(x[u].z, m.z), s.z);
                 y.w = __fdiv_rn(__fsub_rn(x[u].w, m.w), s.w);
-                if constexpr (NT) {
-                    typedef float nv4 __attribute__((ext_vector_type(4)));
-                    __builtin_nontemporal_store(nv4{y.x, y.y, y.z, y.w}, reinterpret_cast<nv4*>(Y + rr * ldy + 4 * tx));
-                } else {
-                    *reinterpret_cast<float4*>(Y + rr * ldy + 4 * tx) = y;
-                }
+                if constexpr (NT) nt_store4(Y + rr * ldy + 4 * tx, y);
+                else *reinterpret_cast<float4*>(Y + rr * ldy + 4 * tx) = y;
             }
         }
     };
@@ -281,10 +225,6 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __rest
 
 using namespace dcv;
 
-static bool vec4_ok(const void* p, int F, int64_t ld) {
-    return (F % 4 == 0) && (ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(p) & 15) == 0);
-}
-
 extern "C" size_t dcv_col_stats_workspace(int64_t n, int32_t F) {
     if (n <= 0 || F <= 0) return 0;
     return (size_t)stats_blocks(n, F) * 4 * (size_t)F * sizeof(double);
@@ -298,7 +238,7 @@ extern "C" int dcv_col_stats(const float* X_d, int64_t n, int32_t F, int64_t ld,
     hipStream_t s = as_stream(stream);
     const int nb = stats_blocks(n, F);
     double* part = static_cast<double*>(ws_d);
-    if (vec4_ok(X_d, F, ld)) {
+    if (quad_path(X_d, F, ld)) {
         const size_t lds = kStatsThreads * 4 * (2 * sizeof(double) + 2 * sizeof(float));
         hipLaunchKernelGGL(col_stats_kernel<4>, dim3(nb), dim3(kStatsThreads), lds, s, X_d, n, F, ld, part);
     } else {
@@ -316,22 +256,21 @@ extern "C" int dcv_normalize(const float* X_d, float* Y_d, int64_t n, int32_t F,
     DCV_REQUIRE(X_d && Y_d && mean_d && range_d && n > 0 && F > 0 && ldx >= F && ldy >= F,
                 "dcv_normalize: bad arguments");
     hipStream_t s = as_stream(stream);
-    const bool v4 = vec4_ok(X_d, F, ldx) && vec4_ok(Y_d, F, ldy) && ((reinterpret_cast<uintptr_t>(mean_d) & 15) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(range_d) & 15) == 0);
+    const bool v4 = quad_path(X_d, F, ldx) && quad_path(Y_d, F, ldy) && aligned16(mean_d) && aligned16(range_d);
     const int64_t total = n * (v4 ? F / 4 : F);
     int64_t blocks = cdiv(total, 256);
     const int64_t cap = (int64_t)num_cus() * 16;
     if (blocks > cap) blocks = cap;
     const int ng = F / 4;
-    static const bool rows_off = [] { const char* e = getenv("DCV_NORMALIZE_FLAT"); return e && e[0] == '1'; }();
-    if (v4 && !rows_off && ng <= 256 && 256 % ng == 0 && (reinterpret_cast<uintptr_t>(mean_d) & 15) == 0 && (reinterpret_cast<uintptr_t>(range_d) & 15) == 0) {
+    static const bool rows_off = env_is("DCV_NORMALIZE_FLAT", '1');
+    if (v4 && !rows_off && ng <= 256 && 256 % ng == 0) {
         const int lanes = 256 / ng;
         int rpb = lanes * 8 * 4;   // four rounds of eight loads per thread
         while ((int64_t)cdiv(n, rpb) > (int64_t)num_cus() * 64) rpb *= 2;
         // non-temporal loads / stores: the matrix is streamed exactly once.  A/B on one box, 5M x 256, three runs each (round 4):
         // 5.11 / 5.12 / 5.14 TB/s plain, 5.31 / 5.21 / 5.25 TB/s non-temporal (+2.7 %); DCV_NORMALIZE_NT=0 restores plain accesses
-        static const int nt_env = [] { const char* e = getenv("DCV_NORMALIZE_NT"); return e ? atoi(e) : 1; }();
-        static const int rpb_env = [] { const char* e = getenv("DCV_NORMALIZE_RPB"); return e ? atoi(e) : 0; }();
+        static const int nt_env = (int)env_int("DCV_NORMALIZE_NT", 1);
+        static const int rpb_env = (int)env_int("DCV_NORMALIZE_RPB", 0);
         if (rpb_env > 0) rpb = rpb_env;
         if (nt_env) hipLaunchKernelGGL((normalize_rows_kernel<8, true>), dim3((unsigned)cdiv(n, rpb)), dim3(256), 0, s, X_d, Y_d, n, ng, ldx, ldy, mean_d, range_d, rpb);
         else hipLaunchKernelGGL((normalize_rows_kernel<8, false>), dim3((unsigned)cdiv(n, rpb)), dim3(256), 0, s, X_d, Y_d, n, ng, ldx, ldy, mean_d, range_d, rpb);

@@ -225,9 +225,7 @@ extern "C" int dcv_superpose(const float* xyz_d, int64_t n_frames, int64_t frame
     // ---- validate everything before anything is launched
     DCV_REQUIRE(xyz_d && fit_h && fit_ref_h && n_frames >= 0 && n_atoms > 0 && n_fit >= 1 && n_sel >= 0,
                 "dcv_superpose: bad arguments (n_frames=%lld n_atoms=%d n_fit=%d n_sel=%d)", (long long)n_frames, n_atoms, n_fit, n_sel);
-    DCV_REQUIRE(frame_stride >= 0 && atom_stride >= 1 && comp_stride >= 1,
-                "dcv_superpose: strides (%lld, %lld, %lld): the frame stride must be >= 0, the atom and component strides >= 1",
-                (long long)frame_stride, (long long)atom_stride, (long long)comp_stride);
+    DCV_REQUIRE_COORD_STRIDES("dcv_superpose", frame_stride, atom_stride, comp_stride);
     DCV_REQUIRE(sel_h || n_sel == 0, "dcv_superpose: n_sel = %d without a selection", n_sel);
     DCV_REQUIRE(!sel_ref_h || n_sel > 0, "dcv_superpose: a selection reference without a selection");
     DCV_REQUIRE(!moments_d || (sel_ref_h && n_sel > 0), "dcv_superpose: moments need a selection and its reference (sel_ref)");
@@ -253,9 +251,7 @@ extern "C" int dcv_superpose(const float* xyz_d, int64_t n_frames, int64_t frame
     StagePlan plan;
     stage_plan(is_used, n_atoms, atom_stride, comp_stride, a.st, plan);
     const int64_t per_frame = plan.per_frame;
-    DCV_REQUIRE(per_frame * (int64_t)sizeof(float) <= kStageLdsMax,
-                "dcv_superpose: one frame of the %lld atoms to stage exceeds %d bytes of LDS (at most %d atoms)", (long long)(per_frame / 3),
-                kStageLdsMax, kStageLdsMax / 12);
+    DCV_REQUIRE_STAGE_FITS("dcv_superpose", per_frame);
     const bool phase_b = aligned_d || moments_d;
     const int64_t xf_bytes = phase_b ? 12 * (int64_t)sizeof(double) : 0;                       // per frame
     const int64_t mom_bytes = moments_d ? (int64_t)n_sel * 6 * (int64_t)sizeof(double) : 0;    // per workgroup
@@ -295,10 +291,7 @@ extern "C" int dcv_superpose(const float* xyz_d, int64_t n_frames, int64_t frame
     if (sel_ref_h) DCV_CHECK_HIP(hipMemcpyAsync(ws + lay.sel_ref, sel_ref_h, (size_t)n_sel * 3 * sizeof(double), hipMemcpyHostToDevice, s));
     DCV_CHECK_HIP(hipMemcpyAsync(ws + lay.used, plan.used.data(), plan.used.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
 
-    a.st.xyz = xyz_d;
-    a.st.frame_stride = frame_stride; a.st.atom_stride = atom_stride; a.st.comp_stride = comp_stride;
-    a.st.n_frames = n_frames;
-    a.st.used = reinterpret_cast<const int32_t*>(ws + lay.used);
+    stage_source(a.st, xyz_d, frame_stride, atom_stride, comp_stride, n_frames, reinterpret_cast<const int32_t*>(ws + lay.used));
     a.fit_slot = reinterpret_cast<const int32_t*>(ws + lay.fit_slot);
     a.fit_rec = reinterpret_cast<const double*>(ws + lay.fit_rec);
     a.sel_slot = reinterpret_cast<const int32_t*>(ws + lay.sel_slot);
