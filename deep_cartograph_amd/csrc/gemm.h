@@ -1071,6 +1071,8 @@ __device__ __forceinline__ void gemm_block(const Operand& A, const Operand& B, i
     DCV_STAMP_AT(2);
     DCV_STAMP_RT(6);
     static_assert(!Epi::kHead || kStaged, "the fused narrow layer needs the staged epilogue");
+    static_assert(!Epi::kDrop || kStaged, "dropout is applied in the staged epilogue only (Epi::one drops nothing)");
+    static_assert(!Epi::kMaskOut || kStaged, "the sign mask is written by the staged epilogue only");
     if constexpr (kStaged) {
         float* tile = lds;  // [RP][TN]
         const int c4 = t % C4, r0 = t / C4;

@@ -743,6 +743,9 @@ int forward_impl(dcv_mlp* m, const float* Xn_d, int64_t ld, const int64_t* idx_d
     DCV_REQUIRE(batch >= 1 && batch <= m->desc.max_batch, "dcv_mlp_forward: batch=%d exceeds max_batch=%d", batch, m->desc.max_batch);
     DCV_REQUIRE(ld >= m->desc.dims[0], "dcv_mlp_forward: ld=%lld < F=%d", (long long)ld, m->desc.dims[0]);
     if (fuse_head) DCV_REQUIRE(m->log && m->log_cap > 0, "dcv_mlp step: call dcv_mlp_reset_log first");
+    // torch.nn.BatchNorm1d raises on a training forward call of one row ("Expected more than 1 value per channel when training");
+    // every forward call of a step -- the batch, or each half of a Deep-TICA batch -- has `batch` rows
+    DCV_REQUIRE(!(train && m->any_bn && batch == 1), "dcv_mlp_forward: a training forward of one row per call through a batch normalisation");
     if (m->vae_d > 0) {   // after every argument check, before any state changes: a refused step leaves the engine as it was
         const int rcn = take_noise(m, batch);
         if (rcn) return rcn;

@@ -316,7 +316,13 @@ typedef struct dcv_mlp_desc {
     double lr_decay, initial_accumulator_value; /* Adagrad */
     double opt_p[4];                    /* further constants of the optimiser, see DCV_OPT_* */
     /* torch.nn.Dropout(p) behind the activation of each Linear (mlcolvar FeedForward order: Linear, activation,
-     * dropout), active in training steps only; 0 = none.  Masks come from a counter-based generator keyed by `seed`. */
+     * dropout), active in training steps only; 0 = none.  Masks come from a counter-based generator keyed by `seed`.
+     * p must lie in [0, 1): dcv_mlp_create refuses p >= 1 (and a negative or non-finite p) with DCV_EINVAL -- the kept
+     * values are scaled by 1 / (1 - p).
+     * The keep bit of element (row, col) of Linear `layer` in training step `step` is Philox-4x32 with 7 rounds on the counter
+     * (row, col >> 2, layer, step) (each mod 2^32) under the key (seed & 0xffffffff, (seed >> 32) + 0x9E3779B9 * rank) (rank:
+     * dcv_mlp_set_rank): the four output words cover columns 4 (col >> 2) .. + 3, an element is kept iff its word >= thr,
+     * thr = p * 2^32 clamped to [1, 2^32 - 1].  tests/dropout_oracle.py restates it independently. */
     float dropout[DCV_MAX_LAYERS];
     uint64_t seed;
     /* torch.nn.BatchNorm1d(dims[l + 1]) behind Linear l (mlcolvar FeedForward order: Linear, activation, dropout, batchnorm);
@@ -375,6 +381,10 @@ int dcv_mlp_latent_sample(dcv_mlp* m, int64_t rows, float* out_d, void* stream);
  * `global_batch` is the number of samples over ALL ranks (= batch on one GPU).
  *
  *   dcv_mlp_forward   forward pass (train != 0: dropout active, as in model.train(); 0: model.eval());
+ *                     train != 0 with batch == 1 while any layer is batch-normalised is REFUSED (DCV_EINVAL, nothing
+ *                     launched, no state changed; also through dcv_mlp_train_step / _steps / _dp_step): every forward call
+ *                     of the step -- the batch, or each half of a Deep-TICA batch -- would have one row, on which
+ *                     torch.nn.BatchNorm1d raises in training mode;
  *                     Deep-TICA: leaves the batch statistics
  *                     [sum f_t (d) | sum f_lag (d) | sum f_t f_t^T (d*d) | sum f_t f_lag^T (d*d)]
  *                     as float64 in dcv_mlp_stats() (all-reduce SUM across ranks);
