@@ -2,7 +2,7 @@
 // d x d loss head, the loss gradient and the fused backward of a narrow last layer; the autoencoder's squared error and its
 // gradient.  The other units reach the kernels through the host launchers at the end of the file.
 #include "mlp_state.h"
-#include "tica_head.h"
+#include "loss_head.h"
 #include <math.h>
 
 namespace dcv {
@@ -29,21 +29,8 @@ __global__ __launch_bounds__(256) void tica_stats_kernel(const float* __restrict
     }
     __syncthreads();
     double* my = part + (int64_t)blockIdx.x * W;
-    for (int o = t; o < W; o += 256) {
-        double s = 0.0;
-        if (o < d) {
-            for (int r = 0; r < nr; ++r) s += s_t[r * d + o];
-        } else if (o < 2 * d) {
-            for (int r = 0; r < nr; ++r) s += s_l[r * d + o - d];
-        } else if (o < 2 * d + d * d) {
-            const int q = o - 2 * d, i = q / d, j = q % d;
-            for (int r = 0; r < nr; ++r) s += s_t[r * d + i] * s_t[r * d + j];
-        } else {
-            const int q = o - 2 * d - d * d, i = q / d, j = q % d;
-            for (int r = 0; r < nr; ++r) s += s_t[r * d + i] * s_l[r * d + j];
-        }
-        my[o] = s;
-    }
+    for (int o = t; o < W; o += 256)
+        my[o] = tica_stat_entry(o, d, nr, [&](int r, int i) { return s_t[r * d + i]; }, [&](int r, int i) { return s_l[r * d + i]; });
 }
 
 // out[i] = sum_b part[b][i], one wave per output, fixed combination tree
@@ -52,9 +39,7 @@ __global__ __launch_bounds__(64) void sum_partials_kernel(const double* __restri
     const int i = blockIdx.x;
     if (i >= width) return;
     const int lane = threadIdx.x;
-    double s = 0.0;
-    for (int b = lane; b < nblocks; b += 64) s += part[(int64_t)b * width + i];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    const double s = wave_sum_in_order([&](int b) { return part[(int64_t)b * width + i]; }, nblocks, lane);
     if (lane == 0) out[i] = s;
 }
 
@@ -219,12 +204,8 @@ __global__ void tica_grad_kernel(const double* __restrict__ stats, int d_rt, dou
 }
 
 typedef void (*TicaGradFn)(const double*, int, double, double, double*, double*, int*, int, int);
-static TicaGradFn tica_grad_fn(int d) {
-    static const TicaGradFn fn[] = {   // by dimension; [0]: every other one
-        tica_grad_kernel<0>, tica_grad_kernel<1>, tica_grad_kernel<2>, tica_grad_kernel<3>, tica_grad_kernel<4>, tica_grad_kernel<5>,
-        tica_grad_kernel<6>};
-    return fn[d >= 1 && d <= 6 ? d : 0];
-}
+// (d <= 4 takes the wave form below; <0>: every other dimension)
+static TicaGradFn tica_grad_fn(int d) { return d == 5 ? tica_grad_kernel<5> : d == 6 ? tica_grad_kernel<6> : tica_grad_kernel<0>; }
 
 // the wave-parallel loss head as a launch of its own: the data-parallel path, where the batch statistics are all-reduced
 // between the statistics kernel and the head (the single-thread form above is a chain of ~2000 dependent float64
@@ -250,9 +231,10 @@ static TicaGradWaveFn tica_grad_wave_fn(int d) {
 // LDS.  rows_per_block pairs per block (a multiple of 256; stats_plan): enough blocks to spread a small batch over
 // the chip, few enough partials for the last block's ordered sum.  One launch: the block that finishes last adds the
 // partials up in block order and -- on one GPU, where nothing is all-reduced in between (fused.on) -- goes straight
-// on to the d x d loss head (tica_grad_body), saving the launch of tica_grad_kernel.
+// on to the d x d loss head (tica_grad_wave, on its wave 0), saving the launch of tica_grad_wave_kernel.
 // GROUP: member `member` of `members` batches evaluated side by side (tica_stats_rows_group_kernel): the caller hands in the
-// member's own rows, partials and ticket; its record goes to slot (counter + member), the counter itself stays put.
+// member's own rows, partials and ticket; its record goes to slot (counter + member) (loss_head.h: log_member), the counter
+// stays put until launch_log_advance behind the launch.
 template <int D, bool GROUP>
 __device__ __forceinline__ void tica_stats_rows_body(const float* __restrict__ F, int64_t ld, int B, int lag_off, int rows_per_block,
                                                      double* __restrict__ part, unsigned* __restrict__ ticket, double* __restrict__ out,
@@ -304,31 +286,10 @@ __device__ __forceinline__ void tica_stats_rows_body(const float* __restrict__ F
     // block it is).  Hand-off between the blocks: handoff.h (write-through partials, drained by every wave before the
     // barrier and the agent-scope ticket; the last arriver acquires at agent scope and reads with sc1 loads).
     if (handoff_arrive_last(ticket, gridDim.x, &s_last)) {
-        // partials of the other blocks come from memory (1-2 us each): G thread groups take the blocks b = g, g + G, ...
-        // with several loads in flight, then W threads add the G group sums in group order (fixed order: deterministic)
         constexpr int G = 256 / W;
-        __shared__ double s_grp[G][W];
-        const int g = t / W, o = t - g * W;
-        if (g < G) {
-            double s = 0.0;
-            for (unsigned b0 = g; b0 < gridDim.x; b0 += 8 * G) {   // eight loads in flight, added in block order
-                double v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const unsigned b = b0 + (unsigned)u * G;
-                    v[u] = handoff_load(part + (int64_t)(b < gridDim.x ? b : b0) * W + o);
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-                    if (b0 + (unsigned)u * G < gridDim.x) s += v[u];
-            }
-            s_grp[g][o] = s;
-        }
-        __syncthreads();
+        __shared__ double s_grp[G * W];
+        const double s = block_sum_partials_in_order(part, gridDim.x, W, G, t, s_grp);
         if (t < W) {
-            double s = 0.0;
-#pragma unroll
-            for (int q = 0; q < G; ++q) s += s_grp[q][t];
             if (!GROUP || member == members - 1) out[t] = s;   // (a group leaves the statistics of its last batch, as stepping does)
             red[0][t] = s;
         }
@@ -338,12 +299,11 @@ __device__ __forceinline__ void tica_stats_rows_body(const float* __restrict__ F
                 if constexpr (!GROUP) {
                     tica_grad_wave<D>(s_head, &red[0][0], fused.Bg, fused.reg, fused.gradp, fused.log, fused.log_count, fused.log_cap, fused.log_width, lane);
                 } else {
-                    // records in batch order: this head is handed a log base moved by `member` records and a private copy of the
-                    // counter, which nobody moves inside the launch (log_advance_kernel does, behind it, by the group size)
+                    // records in batch order (loss_head.h: log_member): the head moves a private copy of the counter only
                     if (lane == 0) s_slot = *fused.log_count;
                     wave_sync_lds();
-                    tica_grad_wave<D>(s_head, &red[0][0], fused.Bg, fused.reg, fused.gradp, fused.log + (int64_t)member * fused.log_width, &s_slot,
-                                      fused.log_cap - member, fused.log_width, lane);
+                    const MemberLog ml = log_member(fused.log, fused.log_width, fused.log_cap, member);
+                    tica_grad_wave<D>(s_head, &red[0][0], fused.Bg, fused.reg, fused.gradp, ml.log, &s_slot, ml.cap, fused.log_width, lane);
                 }
             }
         }
@@ -365,7 +325,7 @@ __global__ __launch_bounds__(256) void tica_stats_rows_group_kernel(const float*
     const int j = blockIdx.y, n = gridDim.y;
     tica_stats_rows_body<D, true>(F + (int64_t)j * f_stride, ld, B, lag_off, rows_per_block, part + (int64_t)j * gridDim.x * W, ticket + j, out, fused, j, n);
 }
-// the log counter behind a grouped launch: every head of the group read it, none moved it
+// the log counter behind a batched launch whose members only read it (loss_head.h: log_member): + n records
 __global__ void log_advance_kernel(int* __restrict__ log_count, int n) { *log_count += n; }
 typedef void (*tica_stats_fn_t)(const float*, int64_t, int, int, int, double*, unsigned*, double*, FusedHead);
 static tica_stats_fn_t tica_stats_rows_fn(int d) {
@@ -383,17 +343,11 @@ static tica_stats_group_fn_t tica_stats_rows_group_fn(int d) {
 // rows per block of the kernels above: at most 512 blocks, whole multiples of 256 rows
 int stats_rows_per_block(int64_t batch) { return (int)(cdiv(cdiv(batch, 256), 256) * 256); }   // <= 256 blocks: each ends on one ticket (~70 ns apiece, serialised)
 
-// Gradient of the loss w.r.t. the network outputs.  Sample i (0 <= i < B) has f_t in row i and f_lag in
-// row i + lag_off:  dL/df_t[i] = Gu u_i + Gv v_i + c,  dL/df_lag[i] = Gv u_i  (u = f_t - mu, v = f_lag - mu).
-// Row j of dZ collects whatever lands on it: its own t-gradient (j < B) plus the lag-gradient of sample
-// j - lag_off (j >= lag_off).  With lag_off = B the halves are disjoint; with lag_off = lag (contiguous
-// batch, shared rows) an interior row receives both.  Multiplied by act'(F) of the last layer.
-// Evaluated in float64 from the float64 batch statistics, rounded once: the loss does not change when a constant is
-// added to the outputs, so the exact gradient rows sum to zero over the batch, and every parameter whose gradient is a
-// multiple of that sum (the last bias; the bias of any hidden unit that stays on one side of its ReLU kink over the
-// batch) has an exactly zero gradient.  Adam divides by |g| + 1e-8: a common-mode residue of 1e-5 -- what mu and the
-// matrices rounded to float32 leave -- moves those parameters by a full +-lr per step, where autograd's
-// (g - mean g) leaves 1e-10.  In float64 the rows sum to zero up to their own final rounding, as there.
+// Gradient of the loss w.r.t. the network outputs (loss_head.h: tica_grad_t / tica_grad_l, and why float64).  Sample i
+// (0 <= i < B) has f_t in row i and f_lag in row i + lag_off.  Row j of dZ collects whatever lands on it: its own
+// t-gradient (j < B) plus the lag-gradient of sample j - lag_off (j >= lag_off).  With lag_off = B the halves are
+// disjoint; with lag_off = lag (contiguous batch, shared rows) an interior row receives both.  Multiplied by act'(F) of
+// the last layer.
 __global__ __launch_bounds__(256) void tica_dF_kernel(const float* __restrict__ F, int64_t ldf, int B, int d, int lag_off,
                                                       const double* __restrict__ gradp, int act, float* __restrict__ dZ,
                                                       int64_t ldz, DropCfg drop, float hscale) {
@@ -401,38 +355,21 @@ __global__ __launch_bounds__(256) void tica_dF_kernel(const float* __restrict__ 
     const int np = d + 2 * d * d + d;
     for (int i = threadIdx.x; i < np; i += 256) s_g[i] = gradp[i];
     __syncthreads();
-    const double* mu = s_g;
-    const double* Gu = s_g + d;
-    const double* Gv = Gu + d * d;
-    const double* cv = Gv + d * d;
+    const TicaGradMats G = tica_grad_mats(s_g, d);
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t rows = (int64_t)B + lag_off;
     if (j >= rows) return;
     const bool has_t = j < B;            // row j is the f_t row of sample j
     const bool has_l = j >= lag_off;     // row j is the f_lag row of sample j - lag_off
-    double u[kMaxTicaDim], v[kMaxTicaDim], w[kMaxTicaDim];
-    float fj[kMaxTicaDim];
-    const float* frow = F + j * ldf;
+    float fj[kMaxTicaDim], fv[kMaxTicaDim], fw[kMaxTicaDim];
     for (int i = 0; i < d; ++i) {
-        fj[i] = frow[i];
-        u[i] = (double)fj[i] - mu[i];                                               // u_j
-        v[i] = has_t ? (double)F[(j + lag_off) * ldf + i] - mu[i] : 0.0;           // v_j
-        w[i] = has_l ? (double)F[(j - lag_off) * ldf + i] - mu[i] : 0.0;           // u_{j - lag_off}
+        fj[i] = F[j * ldf + i];
+        fv[i] = has_t ? F[(j + lag_off) * ldf + i] : 0.f;   // f_lag of sample j
+        fw[i] = has_l ? F[(j - lag_off) * ldf + i] : 0.f;   // f_t of sample j - lag_off
     }
     for (int i = 0; i < d; ++i) {
-        double g = 0.0;
-        if (has_t) {
-            g = cv[i];
-            for (int q = 0; q < d; ++q) {
-                g = fma(Gu[i * d + q], u[q], g);
-                g = fma(Gv[i * d + q], v[q], g);
-            }
-        }
-        if (has_l) {
-            double gl = 0.0;
-            for (int q = 0; q < d; ++q) gl = fma(Gv[i * d + q], w[q], gl);
-            g += gl;
-        }
+        double g = has_t ? tica_grad_t<0>(i, d, G.mu, G.Gu, G.Gv, G.c, fj, fv) : 0.0;
+        if (has_l) g += tica_grad_l<0>(i, d, G.mu, G.Gv, fw);
         float gf = (float)g;
         if (drop.thr != 0u) gf *= f4c(drop.mult(j, i & ~3), i & 3);   // F holds act(z) * keep / (1 - p)
         dZ[j * ldz + i] = gf * act_grad_from_out(act, fj[i] * hscale);
@@ -443,7 +380,7 @@ __global__ __launch_bounds__(256) void tica_dF_kernel(const float* __restrict__ 
 // Deep-TICA's last Linear maps K hidden units to D <= 8 outputs: as separate products its wgrad, dgrad and the
 // two bias-gradient passes each stream the K-wide activations H (or write the K-wide dZ) for a handful of
 // flops per byte.  One pass does all of it: per row r
-//   g      = dL/dz_last[r]  (D values; the tica_dF formula above, evaluated in place)
+//   g      = dL/dz_last[r]  (D values; the gradient row of tica_dF_kernel, evaluated in place)
 //   dW    += g (x) H[r]          -> slab[block][D][K]          (wgrad partial of the last layer)
 //   db    += g                   -> bpart_last[block][D]
 //   dZ[r]  = (g W) * act'(H[r])  -> written once, 16-byte stores (dgrad of the last layer)
@@ -461,17 +398,14 @@ __global__ __launch_bounds__(256) void head_backward_kernel(const float* __restr
                                                             DropCfg drop_prev, float hscale_prev) {
     constexpr int U = 4;                        // rows in flight per thread
     extern __shared__ __attribute__((aligned(16))) double s_memd[];
-    double* s_g = s_memd;                       // mu | Gu | Gv | c   (float64: see tica_dF_kernel)
+    double* s_g = s_memd;                       // mu | Gu | Gv | c   (float64: loss_head.h)
     float* s_gf = reinterpret_cast<float*>(s_memd + (2 * D + 2 * D * D));  // [groups][U][D] loss gradients of the rows in flight
     const int t = threadIdx.x;
     const int C4 = K / 4, groups = 256 / C4;    // a row group (C4 <= 64 lanes) lies inside one wave
     float* s_red = s_gf + groups * U * D;       // [groups][(D + 1) * K + D]
     for (int i = t; i < 2 * D + 2 * D * D; i += 256) s_g[i] = gradp[i];
     __syncthreads();
-    const double* mu = s_g;
-    const double* Gu = s_g + D;
-    const double* Gv = Gu + D * D;
-    const double* cv = Gv + D * D;
+    const TicaGradMats G = tica_grad_mats(s_g, D);
     const int c4 = t % C4, rl = t / C4;
     const int64_t rows = (int64_t)B + lag_off;
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
@@ -532,25 +466,9 @@ __global__ __launch_bounds__(256) void head_backward_kernel(const float* __restr
                 float gi = 0.f;
                 if (r < r1) {
                     const bool has_t = r < B, has_l = r >= lag_off;
-                    double gd = 0.0;
-                    if (has_t) {
-                        gd = cv[i];
-#pragma unroll
-                        for (int k = 0; k < D; ++k) {
-                            gd = fma(Gu[i * D + k], (double)fro[q][k] - mu[k], gd);
-                            gd = fma(Gv[i * D + k], (double)fvo[q][k] - mu[k], gd);
-                        }
-                    }
-                    if (has_l) {
-                        double gl = 0.0;
-#pragma unroll
-                        for (int k = 0; k < D; ++k) gl = fma(Gv[i * D + k], (double)fwo[q][k] - mu[k], gl);
-                        gd += gl;
-                    }
-                    float fri = fro[q][0];   // fro[q][i] without a dynamically indexed register array
-#pragma unroll
-                    for (int k = 1; k < D; ++k) fri = i == k ? fro[q][k] : fri;
-                    gi = (float)gd * act_grad_from_out(act_last, fri);
+                    double gd = has_t ? tica_grad_t<D>(i, D, G.mu, G.Gu, G.Gv, G.c, fro[q], fvo[q]) : 0.0;
+                    if (has_l) gd += tica_grad_l<D>(i, D, G.mu, G.Gv, fwo[q]);
+                    gi = (float)gd * act_grad_from_out(act_last, pick(i, fro[q]));
                 }
                 gmine[q * D + i] = gi;
             }
@@ -660,29 +578,16 @@ __global__ __launch_bounds__(256) void ae_sse_kernel(const float* __restrict__ Y
     if (t == 0) handoff_store(part + blockIdx.x, red[0]);
     __shared__ unsigned is_last;
     if (!handoff_arrive_last(ticket, gridDim.x, &is_last)) return;   // handoff.h; see tica_stats_rows_kernel
-    if (t < 64) {   // one wave, the arithmetic of sum_partials_kernel: lanes over the blocks, shuffle tree
-        double tot = 0.0;
-        for (int b = t; b < (int)gridDim.x; b += 64) tot += handoff_load(part + b);
-        for (int off = 32; off > 0; off >>= 1) tot += __shfl_down(tot, off, 64);
-        double kl = 0.0;   // VAE: the KL partials of the sampling launch (vae_sample_kernel), the same lane / shuffle order
-        if (kpart != nullptr) {
-            for (int b = t; b < kblocks; b += 64) kl += kpart[b];
-            for (int off = 32; off > 0; off >>= 1) kl += __shfl_down(kl, off, 64);
-        }
+    if (t < 64) {   // one wave, the sum sum_partials_kernel would produce
+        const double tot = wave_sum_in_order([&](int b) { return handoff_load(part + b); }, (int)gridDim.x, t);
+        double kl = 0.0;   // VAE: the KL partials of the sampling launch (vae_sample_kernel: an earlier launch, plain loads)
+        if (kpart != nullptr) kl = wave_sum_in_order([&](int b) { return kpart[b]; }, kblocks, t);
         if (t == 0) {
             out[0] = tot;
             if (kpart != nullptr) out[1] = kl;
             if (log != nullptr) {
                 const int slot = *log_count;
-                if (slot < log_cap) {
-                    const double rec = tot / (Bg * (double)F);
-                    log[(int64_t)slot * log_width + 0] = kpart != nullptr ? rec + beta * (kl / Bg) : rec;
-                    log[(int64_t)slot * log_width + 1] = Bg;
-                    if (kpart != nullptr) {
-                        log[(int64_t)slot * log_width + 2] = rec;
-                        log[(int64_t)slot * log_width + 3] = kl / Bg;
-                    }
-                }
+                if (slot < log_cap) ae_loss_record(log + (int64_t)slot * log_width, tot, kl, Bg, F, beta, kpart != nullptr);
                 *log_count = slot + 1;
             }
         }
@@ -712,15 +617,7 @@ __global__ void ae_log_kernel(const double* __restrict__ stats, double Bg, int F
                               int* __restrict__ log_count, int log_cap, int log_width, int vae = 0, double beta = 0.0) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const int slot = *log_count;
-    if (slot < log_cap) {
-        const double rec = stats[0] / (Bg * (double)F);
-        log[(int64_t)slot * log_width + 0] = vae ? rec + beta * (stats[1] / Bg) : rec;
-        log[(int64_t)slot * log_width + 1] = Bg;
-        if (vae) {
-            log[(int64_t)slot * log_width + 2] = rec;
-            log[(int64_t)slot * log_width + 3] = stats[1] / Bg;
-        }
-    }
+    if (slot < log_cap) ae_loss_record(log + (int64_t)slot * log_width, stats[0], vae ? stats[1] : 0.0, Bg, F, beta, vae != 0);
     *log_count = slot + 1;
 }
 
@@ -757,6 +654,10 @@ static int launched() {
     DCV_CHECK_LAUNCH();
     return DCV_OK;
 }
+int launch_log_advance(int* log_count, int n, hipStream_t s) {
+    hipLaunchKernelGGL(log_advance_kernel, dim3(1), dim3(1), 0, s, log_count, n);
+    return launched();
+}
 int launch_sum_partials(const double* part, int nblocks, int width, double* out, hipStream_t s) {
     hipLaunchKernelGGL(sum_partials_kernel, dim3(width), dim3(64), 0, s, part, nblocks, width, out);
     return launched();
@@ -787,8 +688,7 @@ int tica_stats_group(dcv_mlp* m, const float* F, int64_t ldf, int64_t f_stride, 
     hipLaunchKernelGGL(tica_stats_rows_group_fn(m->d_out), dim3((unsigned)blocks, (unsigned)members), dim3(256), 0, s, F, ldf, f_stride, batch, lag_off,
                        stats_rows_per_block(batch), part, tickets, m->stats, fh);
     DCV_CHECK_LAUNCH();
-    hipLaunchKernelGGL(log_advance_kernel, dim3(1), dim3(1), 0, s, m->log_count, members);
-    return launched();
+    return launch_log_advance(m->log_count, members, s);
 }
 // The step's loss record from m->stats, unless the forward's launch wrote it (head_done) or the fused backward will
 // (head_in_bwd).  Deep-TICA: the loss head as a launch of its own, which for a training step also leaves the matrices m->gradp.

@@ -316,6 +316,7 @@ int finish_grads(dcv_mlp* m, const ReduceArgs& ra, bool fuse_opt, bool upper_don
 int apply_impl(dcv_mlp* m, void* stream);
 // mlp_heads.hip: launchers of the loss-head kernels
 int launch_sum_partials(const double* part, int nblocks, int width, double* out, hipStream_t s);
+int launch_log_advance(int* log_count, int n, hipStream_t s);   // the log counter + n behind a batched launch (loss_head.h: log_member)
 int stats_rows_per_block(int64_t batch);
 int tica_stats(dcv_mlp* m, const float* F, int64_t ldf, int batch, int lag_off, int fuse_head, bool* head_ran, hipStream_t s);
 bool tica_stats_groupable(int d);

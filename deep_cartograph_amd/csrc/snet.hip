@@ -16,6 +16,7 @@
 // A wave owns 16-row groups: TR = 32 -> waves (row group, column-tile parity); the k-slot permutation of gemm.h lets
 // one ds_read_b128 feed four MFMA steps (lane (n, q) holds k = k0 + 4q + s in step s, identically for A and B).
 #include "snet.h"
+#include "loss_head.h"
 #include <new>
 
 namespace dcv {
@@ -273,52 +274,31 @@ __global__ __launch_bounds__(kSnetThreads) void snet_ae_kernel(SnetArgs a) {
     if (!handoff_arrive_last(a.ticket + bj, wgpb, flag)) return;
     SNET_STAMP(61);
     if (t < 64) {
-        double tot = 0.0;
         const double* sp = a.sse_part + (int64_t)bj * wgpb;
-        for (int b0 = t; b0 < (int)wgpb; b0 += 64) tot += handoff_load(sp + b0);
-        for (int off = 32; off > 0; off >>= 1) tot += __shfl_down(tot, off, 64);
-        const bool vae = VAE;
+        const double tot = wave_sum_in_order([&](int b) { return handoff_load(sp + b); }, (int)wgpb, t);
         double kl = 0.0;   // VAE: the KL partials, the same lane / shuffle order
-        if (vae) {
+        if (VAE) {
             const double* kp = a.kl_part + (int64_t)bj * wgpb;
-            for (int b0 = t; b0 < (int)wgpb; b0 += 64) kl += handoff_load(kp + b0);
-            for (int off = 32; off > 0; off >>= 1) kl += __shfl_down(kl, off, 64);
+            kl = wave_sum_in_order([&](int b) { return handoff_load(kp + b); }, (int)wgpb, t);
         }
         if (t == 0) {
             if (a.nb <= 1) a.stats[0] = tot;
-            if (a.nb <= 1 && vae) a.stats[1] = kl;
+            if (a.nb <= 1 && VAE) a.stats[1] = kl;
             if (a.log != nullptr) {   // (a data-parallel step logs after the all-reduce of the sum: ae_log_kernel)
-                // a batched evaluation appends its records in batch order: every batch's last arriver reads the counter, the last
-                // of those (a second ticket, taken behind the read) moves it
+                // a batched evaluation appends its records in batch order (loss_head.h: log_member): every batch's last arriver
+                // reads the counter; the last of those moves it -- the VAE's batched pass leaves that to launch_log_advance
                 const int slot0 = *a.log_count;
-                const int slot = slot0 + bj;
-                if (slot < a.log_cap) {
-                    const double rec = tot / (a.Bg * (double)a.l[0].in);
-                    a.log[(int64_t)slot * a.log_width + 0] = vae ? rec + a.beta * (kl / a.Bg) : rec;
-                    a.log[(int64_t)slot * a.log_width + 1] = a.Bg;
-                    if (vae) {
-                        a.log[(int64_t)slot * a.log_width + 2] = rec;
-                        a.log[(int64_t)slot * a.log_width + 3] = kl / a.Bg;
-                    }
-                }
+                const MemberLog ml = log_member(a.log, a.log_width, a.log_cap, bj);
+                if (slot0 < ml.cap) ae_loss_record(ml.log + (int64_t)slot0 * a.log_width, tot, kl, a.Bg, a.l[0].in, a.beta, VAE);
                 if (a.nb <= 1) {
-                    *a.log_count = slot + 1;
-                } else if (!VAE) {   // (the VAE's batched pass leaves the counter to snet_log_advance_kernel, launched behind it)
+                    *a.log_count = slot0 + 1;
+                } else if (!VAE) {
                     asm volatile("s_waitcnt vmcnt(0) ; the counter has been read" ::: "memory");
-                    const unsigned prev = __hip_atomic_fetch_add(a.ticket + a.nb, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (prev == (unsigned)a.nb - 1u) {
-                        __hip_atomic_store(a.ticket + a.nb, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        *a.log_count = slot0 + a.nb;
-                    }
+                    log_advance_by_ticket(a.ticket + a.nb, a.nb, a.log_count, slot0);
                 }
             }
         }
     }
-}
-
-// the log counter behind a batched VAE evaluation launch (whose batches only read it): + nb records
-__global__ void snet_log_advance_kernel(int* __restrict__ log_count, int n) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) *log_count += n;
 }
 
 struct SnetPlan {
@@ -552,10 +532,7 @@ int snet_ae_step(dcv_mlp* m, const float* Xn_d, int64_t ld, const RowMap& rm, in
     };
     if (a.vae_l >= 0) {
         const int rc = TR == 32 ? launch(snet_ae_kernel<32, true>) : launch(snet_ae_kernel<16, true>);
-        if (rc == DCV_OK && nb > 1 && a.log != nullptr) {
-            hipLaunchKernelGGL(snet_log_advance_kernel, dim3(1), dim3(64), 0, s, m->log_count, nb);
-            DCV_CHECK_LAUNCH();
-        }
+        if (rc == DCV_OK && nb > 1 && a.log != nullptr) return launch_log_advance(m->log_count, nb, s);
         return rc;
     }
     return TR == 32 ? launch(snet_ae_kernel<32, false>) : launch(snet_ae_kernel<16, false>);

@@ -10,10 +10,10 @@
 //                        pairs are formed from LDS.  Forward chain with the activations kept in LDS; statistics partial
 //                        (float64, pair order); the tile's activations leave as one contiguous blob (write-through); the
 //                        ticketed last arriver (handoff.h) adds the partials in block order and -- one-GPU steps -- runs
-//                        the wave-parallel d x d loss head (tica_head.h).  An evaluation step ends here.
+//                        the wave-parallel d x d loss head (loss_head.h).  An evaluation step ends here.
 //   snet_dt_bwd_kernel   stages the weights of layers >= 1 (the input gradients need them) and its blob back into LDS,
-//                        evaluates the loss gradient of its pairs in float64 from the head's matrices (the arithmetic of
-//                        tica_dF_kernel / head_backward_kernel), walks back through the layers as snet_ae_kernel does and
+//                        evaluates the loss gradient of its pairs in float64 from the head's matrices (loss_head.h:
+//                        tica_grad_t / tica_grad_l), walks back through the layers as snet_ae_kernel does and
 //                        leaves one gradient partial per workgroup and layer for reduce_grads_quad_kernel + the optimiser.
 //
 // Three launches instead of eight for a 3-layer network, none of them a matrix product over a few thousand rows on 516
@@ -22,7 +22,7 @@
 // tica_grad_wave_kernel behind the statistics all-reduce.  Not taken (the layer-by-layer path runs): d > 4, dropout, batch
 // normalisation, a width above 256, a network that does not fit in LDS, more than 512 tiles (DCV_NO_SNET=1 forces it off).
 #include "snet.h"
-#include "tica_head.h"
+#include "loss_head.h"
 #include <new>
 
 namespace dcv {
@@ -63,7 +63,7 @@ union TicaWaveLdsAny {
     TicaWaveLds<3> h3;
     TicaWaveLds<4> h4;
 };
-// the wave-parallel d x d loss head (tica_head.h) for the run-time d of the plan
+// the wave-parallel d x d loss head (loss_head.h) for the run-time d of the plan
 __device__ __forceinline__ void snet_dt_head(int D, TicaWaveLdsAny& w, const double* stats, const FusedHead& f, double* gradp, double* log,
                                              int* log_count, int log_cap, int lane) {
     switch (D) {
@@ -178,18 +178,8 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_fwd_kernel(SnetDtArgs a)
         const int64_t left = (int64_t)a.B - p0;
         const int nvalid = left >= HP ? HP : (left > 0 ? (int)left : 0);
         if (t < W) {
-            double s = 0.0;
-            if (t < D) {
-                for (int pl = 0; pl < nvalid; ++pl) s += (double)FL[pl * psL + t];
-            } else if (t < 2 * D) {
-                for (int pl = 0; pl < nvalid; ++pl) s += (double)FL[(HP + pl) * psL + t - D];
-            } else if (t < 2 * D + D * D) {
-                const int e = t - 2 * D, i = e / D, j = e - i * D;
-                for (int pl = 0; pl < nvalid; ++pl) s += (double)FL[pl * psL + i] * (double)FL[pl * psL + j];
-            } else {
-                const int e = t - 2 * D - D * D, i = e / D, j = e - i * D;
-                for (int pl = 0; pl < nvalid; ++pl) s += (double)FL[pl * psL + i] * (double)FL[(HP + pl) * psL + j];
-            }
+            const double s = tica_stat_entry(t, D, nvalid, [&](int pl, int i) { return (double)FL[pl * psL + i]; },
+                                             [&](int pl, int i) { return (double)FL[(HP + pl) * psL + i]; });
             handoff_store(a.spart + (int64_t)blockIdx.x * W + t, s);
         }
     }
@@ -205,29 +195,9 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_fwd_kernel(SnetDtArgs a)
     // ---- last workgroup: the partials in block order, then the d x d loss head
     if (!handoff_arrive_last(a.ticket + bj, wgpb, &s_flag)) return;
     {
-        const int G = NT / W;
-        double* s_grp = reinterpret_cast<double*>(sl);   // [G][W]: the weight images are dead
-        const int g = t / W, o = t - g * W;
-        if (g < G) {
-            double s = 0.0;
-            const double* sp = a.spart + (int64_t)wg0 * W;
-            for (unsigned b0 = g; b0 < wgpb; b0 += 8 * G) {   // eight loads in flight, added in block order
-                double v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const unsigned b = b0 + (unsigned)u * G;
-                    v[u] = handoff_load(sp + (int64_t)(b < wgpb ? b : b0) * W + o);
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-                    if (b0 + (unsigned)u * G < wgpb) s += v[u];
-            }
-            s_grp[g * W + o] = s;
-        }
-        __syncthreads();
+        // (the group sums go where the weight images were: they are dead)
+        const double s = block_sum_partials_in_order(a.spart + (int64_t)wg0 * W, wgpb, W, NT / W, t, reinterpret_cast<double*>(sl));
         if (t < W) {
-            double s = 0.0;
-            for (int g2 = 0; g2 < G; ++g2) s += s_grp[g2 * W + t];
             if (a.nb <= 1) a.stats[t] = s;
             s_stat[t] = s;
         }
@@ -235,29 +205,21 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_fwd_kernel(SnetDtArgs a)
             __syncthreads();
             if (wave == 0) {
                 const FusedHead& f = a.fused;
-                // a batched evaluation appends its records in batch order: the head of batch j writes record (counter + j) -- it is
-                // handed a log base moved by j records and a private copy of the counter -- and the last head to finish (a second
-                // ticket, taken behind its read of the counter) moves the counter by nb
-                double* logp = f.log;
+                // a batched evaluation appends its records in batch order (loss_head.h: log_member): the head of batch j moves a
+                // private copy of the counter, the last head to finish moves the counter itself by nb
+                MemberLog ml{f.log, f.log_cap};
                 int* lc = f.log_count;
-                int cap = f.log_cap, slot0 = 0;
+                int slot0 = 0;
                 if (a.nb > 1) {
                     slot0 = *f.log_count;
                     asm volatile("s_waitcnt vmcnt(0) ; the counter has been read" ::: "memory");
                     if (lane == 0) s_slot = slot0;
                     wave_sync_lds();
-                    logp = f.log + (int64_t)bj * f.log_width;
+                    ml = log_member(f.log, f.log_width, f.log_cap, bj);
                     lc = &s_slot;
-                    cap = f.log_cap - bj;
                 }
-                snet_dt_head(D, s_head, s_stat, f, f.gradp, logp, lc, cap, lane);
-                if (a.nb > 1 && lane == 0) {
-                    const unsigned prev = __hip_atomic_fetch_add(a.ticket + a.nb, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (prev == (unsigned)a.nb - 1u) {
-                        __hip_atomic_store(a.ticket + a.nb, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        *f.log_count = slot0 + a.nb;
-                    }
-                }
+                snet_dt_head(D, s_head, s_stat, f, f.gradp, ml.log, lc, ml.cap, lane);
+                if (a.nb > 1 && lane == 0) log_advance_by_ticket(a.ticket + a.nb, a.nb, f.log_count, slot0);
             }
         }
     }
@@ -341,9 +303,9 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_bwd_kernel(SnetDtArgs a)
     }
     asm volatile("" ::"s"(ka_touch));
     __syncthreads();
-    // ---- loss gradient of the tile's pairs, float64, rounded once (tica_dF_kernel: the rows of the exact gradient sum to
-    //      zero over the batch; see DESIGN.md section 2, noise-driven parameters): dL/df_t = Gu u + Gv v + c, dL/df_lag = Gv u
-    //      with u = f_t - mu, v = f_lag - mu; times act'(f) of the last layer; written over f (H_L becomes dZ_L)
+    // ---- loss gradient of the tile's pairs, float64, rounded once (loss_head.h: tica_grad_t / tica_grad_l; the rows of the
+    //      exact gradient sum to zero over the batch, see DESIGN.md section 2, noise-driven parameters); times act'(f) of the
+    //      last layer; written over f (H_L becomes dZ_L)
     {
         float* FL = sl + a.lh[L];
         const int psL = a.ps[L];
@@ -361,6 +323,8 @@ __global__ __launch_bounds__(kSnetThreads) void snet_dt_bwd_kernel(SnetDtArgs a)
         if (mine) {
             float gt = 0.f, gl = 0.f;
             if (valid) {
+                // the two chains of loss_head.h (tica_grad_t, tica_grad_l) side by side, sharing u and the loads of Gv: composed from
+                // the two functions the kernel was 43 instructions longer and measured slower (profiles/loss_head_resource_usage.md)
                 const double* mu = s_g;
                 const double* Gu = s_g + D;
                 const double* Gv = Gu + D * D;
