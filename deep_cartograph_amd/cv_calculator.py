@@ -32,6 +32,7 @@ import torch
 from . import export, hip, linalg
 from .colvars import load_feature_matrix
 from .common import closest_power_of_two, remove_files, unzip_files, zip_files
+from .fit import FitPlan, Try, _Batches, _HostLRScheduler, _torch_threads  # noqa: F401  (the training driver; names importable from here)
 from .parallel import Comm, append_halo, reduce_col_stats, reduce_minmax
 
 logger = logging.getLogger(__name__)
@@ -617,121 +618,6 @@ _OPTIMIZERS_REFUSED = {"LBFGS": "needs a closure that re-evaluates the model sev
 _IMPLEMENTATION_SWITCHES = ("foreach", "fused", "capturable", "differentiable")   # no effect on the arithmetic
 
 
-class _torch_threads:
-    """with _torch_threads(k): torch's intra-op thread count capped at k for the block (restored afterwards)."""
-
-    def __init__(self, k: int):
-        self.k = k
-
-    def __enter__(self):
-        self.prev = torch.get_num_threads()
-        if self.prev > self.k:
-            torch.set_num_threads(self.k)
-        return self
-
-    def __exit__(self, *exc):
-        if torch.get_num_threads() != self.prev:
-            torch.set_num_threads(self.prev)
-        return False
-
-
-class _Batches:
-    """The batches of one pass over a DictLoader, without the per-batch objects: kind 'idx' (base = the device index list of
-    the pass, batch i = base[i * bs:(i + 1) * bs]) or 'range' (base = first row, batch i = rows base + i * bs ...)."""
-
-    def __init__(self, kind: str, base, n: int, bs: int):
-        self.kind, self.base, self.n, self.bs = kind, base, int(n), int(bs)
-        self.count = (self.n + self.bs - 1) // self.bs if self.n > 0 else 0
-
-    def __len__(self):
-        return self.count
-
-    def size(self, i: int) -> int:
-        return min(self.bs, self.n - i * self.bs)
-
-    def full(self) -> int:
-        """Number of leading batches of the full size bs."""
-        return self.n // self.bs
-
-    def __getitem__(self, i):
-        if isinstance(i, slice):
-            return [self[j] for j in range(*i.indices(self.count))]
-        if i < 0:
-            i += self.count
-        if not 0 <= i < self.count:
-            raise IndexError(i)
-        if self.kind == "idx":
-            return ("idx", self.base[i * self.bs:i * self.bs + self.size(i)], self.base)
-        return ("range", self.base + i * self.bs, self.size(i))
-
-    def __iter__(self):
-        return (self[i] for i in range(self.count))
-
-
-class _HostLRScheduler:
-    """torch.optim.lr_scheduler.<name> (reference :1382-1394, adjusted by :1228-1273) evaluated on the host: the very
-    torch class runs over a one-parameter optimiser of the configured type, and after each of its steps the
-    learning rate -- and beta1 / momentum, which OneCycleLR and CyclicLR cycle too -- are handed to the HIP engine.
-    Stepping follows lightning's lr_scheduler_config: interval 'step' (after every optimiser step) or 'epoch'
-    (at the end of every epoch), every `frequency`-th time; ReduceLROnPlateau receives the monitored valid_loss."""
-
-    def __init__(self, name: str, kwargs: Dict, config: Dict, opt_name: str, opt_kwargs: Dict, engine):
-        cls = getattr(torch.optim.lr_scheduler, name, None)
-        if cls is None:
-            logger.error(f"Learning rate scheduler {name} not recognized. Exiting...")
-            raise ValueError(f"Learning rate scheduler {name} not recognized.")
-        self.opt = getattr(torch.optim, opt_name)([torch.nn.Parameter(torch.zeros(1))], **opt_kwargs)
-        self.sched = cls(self.opt, **kwargs)
-        self.plateau = isinstance(self.sched, torch.optim.lr_scheduler.ReduceLROnPlateau)
-        self.interval = config.get("interval", "epoch")
-        self.frequency = max(1, int(config.get("frequency", 1)))
-        self.monitor = config.get("monitor", "valid_loss")
-        self.engine = engine
-        self.count = 0
-        self.plateau_from: Optional[int] = None   # VAE: LROnPlateauManager's extra step from this epoch on (set by the calculator)
-        self.push()
-
-    def push(self):
-        g = self.opt.param_groups[0]
-        self.engine.set_lr(float(g["lr"]))
-        if "betas" in g:
-            self.engine.set_momentum(float(g["betas"][0]))
-        elif "momentum" in g:
-            self.engine.set_momentum(float(g["momentum"]))
-
-    def lr(self) -> float:
-        return float(self.opt.param_groups[0]["lr"])
-
-    def _advance(self, metric=None):
-        self.count += 1
-        if self.count % self.frequency:
-            return
-        self.opt.step()   # no gradients: a no-op that keeps torch's call-order check quiet
-        if self.plateau:
-            if metric is None:   # lightning raises MisconfigurationException here
-                raise ValueError(f"ReduceLROnPlateau conditioned on metric {self.monitor} which is not available yet "
-                                 "(set check_val_every_n_epoch to 1)")
-            self.sched.step(metric)
-        else:
-            self.sched.step()
-        self.push()
-
-    def after_step(self):
-        if self.interval == "step":
-            self._advance()
-
-    def after_epoch(self, last_valid_loss):
-        if self.interval == "epoch":
-            self._advance(last_valid_loss)
-
-    def on_validation_end(self, epoch: int, valid_loss: float):
-        """The reference's LROnPlateauManager (VAE, modules/ml/ml.py): at the end of every validation from epoch `plateau_from`
-        on, ReduceLROnPlateau is stepped once more with the validation loss, outside lightning's interval / frequency."""
-        if self.plateau and self.plateau_from is not None and epoch >= self.plateau_from:
-            self.sched.step(valid_loss)
-            self.push()
-
-
 class NonLinear(CVCalculator):
     """Neural CVs trained by the HIP MLP engine (reference :1049-1921)."""
 
@@ -883,15 +769,30 @@ class NonLinear(CVCalculator):
             self.validation_normalized = hip.normalize(self.validation_data, *self._norm_tensors(self.validation_data.device))
 
     # ---- model description, implemented by the subclasses
-    def layer_plan(self) -> Tuple[List[int], List[Optional[str]], List[float], int]:
-        """(dims, activation per Linear, dropout per Linear, index of the latent layer)."""
+    def layer_plan(self) -> Tuple[List[int], List[Optional[str]], List[float], List[bool], int]:
+        """(dims, activation / dropout / batch-norm flag per Linear, index of the latent layer)."""
         raise NotImplementedError
 
     def n_samples_local(self) -> int:
-        raise NotImplementedError
+        return self.training_data.shape[0]
 
     def n_val_samples_local(self) -> int:
-        raise NotImplementedError
+        return self.validation_data.shape[0]
+
+    def _decoder_options(self):
+        """_layer_options of the decoder, its last activation made to cover the range of the normalised features
+        (reference :1188-1207)."""
+        dec_cfg = self.decoder_config if self.decoder_config is not None else self.encoder_config
+        dec_act, dec_drop, dec_bn = self._layer_options(dec_cfg, len(self.decoder_hidden_layers))
+        for mode, act, text in (("min_max_range1", "custom_sigmoid", "[0, 1]. Changing the activation function to 'sigmoid'."),
+                                ("min_max_range2", "tanh", "[-1, 1]. Changing the activation function to 'tanh'.")):
+            if self.feats_norm_mode == mode and dec_act[-1] != act:
+                logger.warning(f"The last layer activation function of the decoder is set to {dec_act[-1]}, but the features are "
+                               f"normalized using min max with range {text}")
+                dec_act[-1] = act
+        if dec_drop[-1]:
+            logger.warning("Dropout in the last layer of the decoder is not recommended.")
+        return dec_act, dec_drop, dec_bn
 
     def lag(self) -> int:
         return 0
@@ -915,74 +816,11 @@ class NonLinear(CVCalculator):
                            f"Setting the batch size to the closest power of two: {self.batch_size}")
         return self.batch_size
 
-    @staticmethod
-    def _split(n: int, lengths, random_split: bool, generator):
-        """DictModule split: fractional lengths = floor + round-robin remainder; random_split uses
-        ONE randperm of the given generator, else consecutive blocks."""
-        sizes = [int(np.floor(n * f)) for f in lengths]
-        for i in range(n - sum(sizes)):
-            sizes[i % len(sizes)] += 1
-        perm = torch.randperm(n, generator=generator) if random_split else None
-        out, off = [], 0
-        for s in sizes:
-            out.append((perm[off:off + s].clone() if perm is not None else (off, s)))
-            off += s
-        return out
-
-    def _batches(self, part, batch_size: int, dev):
-        """DictLoader: consecutive slices of batch_size, last partial batch kept, fresh randperm per
-        epoch when shuffling.  A sequence of ('idx', tensor, whole list) or ('range', row0, count) entries, materialised on
-        access (an epoch of 10 000 batches issued by ONE dcv_mlp_train_steps call never builds 10 000 views)."""
-        if isinstance(part, tuple):
-            off, n = part
-            if self.shuffle:
-                part = torch.arange(off, off + n)
-            else:
-                return _Batches("range", off, n, batch_size if batch_size > 0 else n)
-        idx = part
-        if self.shuffle:
-            idx = idx[torch.randperm(len(idx))]   # the reference's permutation (global CPU generator)
-        bs = batch_size if batch_size > 0 else len(idx)
-        idx_d = idx.to(dev).contiguous()   # one copy per epoch; the batches are consecutive views of it (third field: the whole list)
-        return _Batches("idx", idx_d, len(idx), bs)
-
-    @staticmethod
-    def _part_len(part) -> int:
-        return part[1] if isinstance(part, tuple) else len(part)
-
     def _init_linears(self, dims):
         """torch.nn.Linear default initialisation in construction order, consuming the global
         RNG exactly as create_model() does."""
         lins = [torch.nn.Linear(dims[i], dims[i + 1]) for i in range(len(dims) - 1)]
         return [(l.weight.detach().numpy().copy(), l.bias.detach().numpy().copy()) for l in lins]
-
-    def _step(self, Xn, batch, train: bool, global_batch_of):
-        kw = dict(idx=batch[1]) if batch[0] == "idx" else dict(row0=batch[1], batch=batch[2])
-        n = int(batch[1].numel()) if batch[0] == "idx" else int(batch[2])
-        if not self.comm.active:
-            (self.engine.train_step if train else self.engine.eval_step)(Xn, **kw)
-            return
-        self.engine.data_parallel_step(Xn, self.comm._dist, global_batch_of(n), train=train, group=self.comm.group, **kw)
-
-    def _run_batches(self, Xn, batches, train: bool, global_batch_of, per_step=None):
-        """One pass over the loader's batches: a training step (train) or an evaluation step per batch.  On one GPU and with
-        nothing to do between steps (`per_step` None: no learning-rate scheduler) the full-sized batches go down in ONE call --
-        dcv_mlp_train_steps / dcv_mlp_eval_steps: the epoch loop runs behind the C-ABI, and small networks are evaluated many
-        batches per launch -- and the ragged last batch follows; launches, parameters and loss records are those of the
-        step-by-step loop, bit for bit."""
-        k = 0
-        if not self.comm.active and per_step is None and len(batches) > 1:
-            k = batches.full()
-            if k > 0:
-                many = self.engine.train_steps if train else self.engine.eval_steps
-                if batches.kind == "idx":
-                    many(Xn, batches.bs, k, idx=batches.base)
-                else:
-                    many(Xn, batches.bs, k, row0=batches.base)
-        for b in batches[k:]:
-            self._step(Xn, b, train, global_batch_of)
-            if per_step is not None:
-                per_step()
 
     def _records_to_metrics(self, rec: np.ndarray, need_eig: bool = True):
         """(weighted mean loss, weighted mean eigenvalues or None, TICA buffers of the last record)."""
@@ -997,8 +835,7 @@ class NonLinear(CVCalculator):
         logger.info(f"Training {cv_names_map[self.cv_name]} ...")
         dev = self.training_data.device
         try:
-            dims, acts, drops, latent = self.layer_plan()
-            opt_name, opt_kw = self._optimizer_options()
+            model, optimizer = self.layer_plan(), self._optimizer_options()
         except Exception as e:
             logger.error(f"{cv_names_map[self.cv_name]} cannot be set up: {e}")
             return False
@@ -1015,8 +852,7 @@ class NonLinear(CVCalculator):
             return False
         self.check_num_samples()
         self.check_batch_size()
-        world = self.comm.world
-        local_bs = max(1, self.batch_size // world) if self.batch_size > 0 else 0
+        plan = FitPlan(*model, *optimizer, n_local, n_val_local, max(1, self.batch_size // self.comm.world) if self.batch_size > 0 else 0)
         best = None
         for try_num in range(1, self.num_tries + 1):
             self.tries = try_num
@@ -1026,7 +862,7 @@ class NonLinear(CVCalculator):
                 # 1.3 ms with 8 (its result does not depend on the count: tests/test_host_cpu.py).  Capped once per try --
                 # growing the pool back costs ~12 ms, so not per epoch.
                 with _torch_threads(8):
-                    result = self._train_once(try_num, dims, acts, drops, latent, opt_name, opt_kw, n_local, n_val_local, local_bs, dev)
+                    result = Try(self, plan, try_num).run()
             except Exception as e:
                 logger.error(f"Training try {try_num} failed with an exception: {e}")
                 continue
@@ -1042,133 +878,10 @@ class NonLinear(CVCalculator):
         self.cv = best["state"]
         self.cv_score = best["score"]
         self.metrics = best["metrics"]
+        self.cv["norm_in"] = (self.features_norm_mean, self.features_norm_range)
         self.engine.set_linears(self.cv["linears"], bn=self.cv.get("bn"))
         logger.info(f"Best model score across {self.num_tries} tries: {best['score']:.5f}")
         return True
-
-    def _train_once(self, try_num, dims, acts, drops, latent, opt_name, opt_kw, n_local, n_val_local, local_bs, dev):
-        seed = self.seed + try_num
-        import random
-
-        random.seed(seed)
-        np.random.seed(seed % (2 ** 32))
-        gen = torch.manual_seed(seed)           # seed_everything + DictModule(generator=manual_seed(seed))
-        separate_val = self.validation_data is not None
-        # RNG order (SURVEY.md Appendix A.6 i): create_model() first, the split inside trainer.fit second --
-        # unless a scheduler is configured, whose _adjust_lr_scheduler_from_datamodule splits before the model exists
-        split_first = self.lr_scheduler is not None and not separate_val
-        parts = None
-        if split_first:
-            parts = self._split(n_local, self.training_validation_lengths, self.random_split, gen)
-        linears = self._init_linears(dims)
-        if separate_val:       # DictLoader over the whole training set and over the validation set (:1485-1492)
-            train_part, val_part = (0, n_local), (0, n_val_local)
-        else:
-            if parts is None:
-                parts = self._split(n_local, self.training_validation_lengths, self.random_split, gen)
-            parts = [p if isinstance(p, tuple) or self.shuffle else p.to(dev) for p in parts]  # index plans live on the GPU
-            train_part, val_part = parts[0], parts[1]
-        Xn_train = self.training_normalized
-        Xn_val = self.validation_normalized if separate_val else self.training_normalized
-        n_tr, n_va = self._part_len(train_part), self._part_len(val_part)
-        bs = local_bs if local_bs > 0 else max(n_tr, n_va, 1)
-        if self.engine is not None:
-            self.engine.close()
-        nmax = max(1, min(bs, max(n_tr, n_va)))
-        self.engine = hip.Mlp(self.model_kind, dims, acts, max_batch=nmax, lag=self.lag(), latent_layer=latent,
-                              tica_reg=float(self.configuration.get("tica_regularization", 1e-6)), dropout=drops, seed=seed, device=dev,
-                              batchnorm=getattr(self, "_bn_plan", None),
-                              **self._engine_optimizer_kwargs(opt_name, opt_kw))
-        self.engine.set_linears(linears)
-        self.engine.set_rank(self.comm.rank)   # data-parallel ranks hold the same seed: independent dropout masks per rank
-        if self.comm.world > 1 and any(getattr(self, "_bn_plan", None) or []):
-            # each rank would normalise with its local rows and keep its own running statistics: no longer the reference's
-            # single-process fit (dcv_mlp_dp_step refuses it too) -- say so before the first step
-            raise ValueError("batchnorm / last_layer_batchnorm are not supported in a frame-sharded (multi-GPU) fit: run this CV on one GPU "
-                             "or drop the option")
-        if self.model_kind == "ae":
-            self.engine.set_feature_range(self.features_norm_range)
-        self._stats_view = self.engine.stats_view()
-        self._grads_view = self.engine.grads_view()
-        world = self.comm.world
-        gb = lambda n: n * world  # equal shards: every rank runs the same batch sizes
-        steps_per_epoch = (n_tr + bs - 1) // bs   # len(train_loader)
-        sched = None
-        so = self._scheduler_options(steps_per_epoch)
-        if so is not None:
-            sched = _HostLRScheduler(so[0], so[1], so[2], opt_name, {k: v for k, v in opt_kw.items()}, self.engine)
-        metrics: Dict[str, list] = {"train_loss": [], "valid_loss": [], "epoch": []}
-        if sched is not None:
-            metrics["lr"] = []
-        self._fit_begin(sched, n_va, bs)
-        best_score, best_state, last_state = float("inf"), None, None
-        es_best, wait = float("inf"), 0
-        last_valid = None
-        next_tb = None
-        for epoch in range(self.max_epochs):
-            tb = next_tb if next_tb is not None else self._batches(train_part, bs, dev)
-            do_val = (epoch + 1) % self.check_val_every_n_epoch == 0
-            vb = self._epoch_begin(epoch, tb, lambda: self._batches(val_part, bs, dev) if do_val else [])
-            self.engine.reset_log(len(tb) + len(vb))
-            # (a scheduler stepped per EPOCH -- lightning's default interval -- has nothing to do between the steps of an epoch)
-            self._run_batches(Xn_train, tb, True, gb, per_step=sched.after_step if sched is not None and sched.interval == "step" else None)
-            self._run_batches(Xn_val, vb, False, gb)
-            # While the device works through the epoch just enqueued: the NEXT epoch's permutation and index upload (a CPU
-            # randperm of 10 M indices is ~0.1 s -- as long as the epoch itself).  The draws keep the reference's order (train
-            # loader, validation loader, next train loader ...); if this epoch turns out to be the last one, the generator is put
-            # back where the reference's would be.
-            rng_before_prefetch = torch.get_rng_state() if self.shuffle else None
-            next_tb = self._batches(train_part, bs, dev) if self.shuffle and epoch + 1 < self.max_epochs else None
-            rec = self.engine.read_log()   # the only host sync of the epoch
-            if not np.all(np.isfinite(rec[:, 0])):
-                raise FloatingPointError("non-finite loss (ill-conditioned batch covariance?)")
-            train_loss, _, _ = self._records_to_metrics(rec[:len(tb)], need_eig=False)   # (only validation logs eigenvalues)
-            stop = False
-            if do_val:
-                valid_loss, eig, buffers = self._records_to_metrics(rec[len(tb):])
-                last_valid = valid_loss
-                metrics["train_loss"].append(train_loss)
-                metrics["valid_loss"].append(valid_loss)
-                metrics["epoch"].append(epoch)
-                if sched is not None:
-                    metrics["lr"].append(sched.lr())
-                self._on_validation(epoch, rec[:len(tb)], rec[len(tb):], valid_loss, metrics,
-                                    lambda: {"linears": self.engine.get_linears(), "tica": buffers, "dims": dims, "acts": acts, "drops": drops,
-                                             "latent": latent, "bn": self.engine.get_bn() if any(getattr(self, "_bn_plan", None) or []) else None})
-                if sched is not None:
-                    sched.on_validation_end(epoch, valid_loss)
-                if eig is not None:
-                    for i, v in enumerate(eig):
-                        metrics.setdefault(f"valid_eigval_{i + 1}", []).append(float(v))
-                if (epoch + 1) % self.save_check_every_n_epoch == 0:  # ModelCheckpoint(save_top_k=1, save_last=True)
-                    state = {"linears": self.engine.get_linears(), "tica": buffers, "dims": dims, "acts": acts, "drops": drops, "latent": latent,
-                             "bn": self.engine.get_bn() if any(getattr(self, "_bn_plan", None) or []) else None}
-                    last_state = state
-                    if valid_loss < best_score:
-                        best_score, best_state = valid_loss, state
-                if valid_loss < es_best - self.early_stop_delta:  # EarlyStopping(monitor=valid_loss, mode=min)
-                    es_best, wait = valid_loss, 0
-                else:
-                    wait += 1
-                    stop = wait >= self.early_stop_patience
-            if sched is not None:
-                sched.after_epoch(last_valid)
-            if stop:
-                if next_tb is not None:
-                    torch.set_rng_state(rng_before_prefetch)
-                break
-        if metrics["valid_loss"] and min(metrics["valid_loss"]) > metrics["valid_loss"][0]:
-            logger.warning(f"Try {try_num}: validation loss did not decrease during training.")
-        chosen = self._choose_model(best_state, best_score, last_state, metrics)
-        if chosen is None:
-            logger.error("Training finished, but no valid model checkpoint was found.")
-            return None
-        state, score = chosen
-        if self.cv_name == "deep_tica" and score < -float(self.cv_dimension):
-            logger.warning(f"Deep TICA validation loss ({score:.5f}) is below the theoretical minimum "
-                           f"({-float(self.cv_dimension):.5f}). Try reducing the learning rate or increasing 'tica_regularization'.")
-            return None
-        return {"state": state, "score": score, "metrics": metrics}
 
     # ---- per-model hooks of the epoch loop (the VAE's noise, beta and post-annealing checkpoint; no-ops here)
     def _fit_begin(self, sched, n_val: int, bs: int):
@@ -1178,8 +891,8 @@ class NonLinear(CVCalculator):
         """Start of an epoch: the training batches exist; returns the validation batches (make_val_batches())."""
         return make_val_batches()
 
-    def _on_validation(self, epoch: int, rec_train: np.ndarray, rec_val: np.ndarray, valid_loss: float, metrics: Dict, snapshot):
-        """After every validation pass; snapshot() returns the current model state."""
+    def _on_validation(self, epoch: int, rec_train: np.ndarray, rec_val: np.ndarray, metrics: Dict, snapshot):
+        """After every validation pass (its losses are the last entries of `metrics`); snapshot() returns the current model state."""
 
     def _choose_model(self, best_state, best_score, last_state, metrics):
         """_finalize_training (reference :1555-1642): "best" = the checkpoint with the lowest monitored loss and that loss;
@@ -1195,13 +908,19 @@ class NonLinear(CVCalculator):
             if self.comm.rank == 0:
                 self.plot_training_metrics()
 
+    metric_files: Tuple[str, ...] = ("train_loss", "valid_loss", "epoch")
+
     def plot_training_metrics(self):
-        """train_loss / valid_loss / epoch .npy -> training_metrics.zip, model_score.txt,
-        eigenvalues.txt (reference :1658-1733, 2592-2627; no figures)."""
+        """The metrics named by metric_files as .npy -> training_metrics.zip, model_score.txt, eigenvalues.txt (Deep-TICA)
+        (reference :1658-1733, 2592-2627; the VAE's: :2880-2893; no figures)."""
         if not self.training_config.get("save_loss", True) or self.metrics is None:
             return
         paths = []
-        for key in ("train_loss", "valid_loss", "epoch"):
+        for key in self.metric_files:
+            if key not in self.metrics:   # (only the VAE names metrics that a fit may not have)
+                if key == "lr":
+                    logger.warning(f"Metric {key} not found in metrics. It will not be saved.")
+                continue
             p = os.path.join(self.training_output_folder, f"{key}.npy")
             np.save(p, np.array(self.metrics[key]))
             paths.append(p)
@@ -1306,6 +1025,13 @@ class NonLinear(CVCalculator):
         given = self._fit_list((cfg or {}).get("dropout", [None] * (n - 1)), n - 1, "dropout") + [(cfg or {}).get("last_layer_dropout", None)]
         return [None if g is None else float(d) for g, d in zip(given, drops)]
 
+    def _export_parts(self):
+        """What every exported module tree starts from: (norm_in, postprocessing, dropout / batch-norm entry per Linear)."""
+        st, n = self.cv, len(self.cv["linears"])
+        norm = export.Normalization(self.features_norm_mean, self.features_norm_range) if self.feats_norm_mode is not None else None
+        post = export.Normalization(*st["post"]) if st.get("post") is not None else None
+        return norm, post, st.get("drops") or [0.0] * n, st.get("bn") or [None] * n
+
     def to_torch_module(self) -> torch.nn.Module:
         raise NotImplementedError
 
@@ -1369,52 +1095,19 @@ class AECalculator(NonLinear):
 
     def layer_plan(self):
         enc_act, enc_drop, enc_bn = self._layer_options(self.encoder_config, len(self.encoder_hidden_layers))
-        dec_cfg = self.decoder_config if self.decoder_config is not None else self.encoder_config
-        dec_act, dec_drop, dec_bn = self._layer_options(dec_cfg, len(self.decoder_hidden_layers))
-        self._bn_plan = enc_bn + dec_bn
-        # the decoder output must cover the range of the normalised features (reference :1188-1207)
-        if self.feats_norm_mode == "min_max_range1" and dec_act[-1] != "custom_sigmoid":
-            logger.warning(f"The last layer activation function of the decoder is set to {dec_act[-1]}, but the features are "
-                           "normalized using min max with range [0, 1]. Changing the activation function to 'sigmoid'.")
-            dec_act[-1] = "custom_sigmoid"
-        elif self.feats_norm_mode == "min_max_range2" and dec_act[-1] != "tanh":
-            logger.warning(f"The last layer activation function of the decoder is set to {dec_act[-1]}, but the features are "
-                           "normalized using min max with range [-1, 1]. Changing the activation function to 'tanh'.")
-            dec_act[-1] = "tanh"
-        if dec_drop[-1]:
-            logger.warning("Dropout in the last layer of the decoder is not recommended.")
+        dec_act, dec_drop, dec_bn = self._decoder_options()
         enc = [self.num_features] + self.encoder_hidden_layers + [self.cv_dimension]
         dec = [self.cv_dimension] + self.decoder_hidden_layers + [self.num_features]
-        return enc + dec[1:], enc_act + dec_act, enc_drop + dec_drop, len(enc) - 1
-
-    def n_samples_local(self) -> int:
-        return self.training_data.shape[0]
-
-    def n_val_samples_local(self) -> int:
-        return self.validation_data.shape[0]
-
-    def _records_to_metrics(self, rec, need_eig: bool = True):
-        w = rec[:, 1]
-        return float((rec[:, 0] * w).sum() / w.sum()), None, None
+        return enc + dec[1:], enc_act + dec_act, enc_drop + dec_drop, enc_bn + dec_bn, len(enc) - 1
 
     def to_torch_module(self):
         st = self.cv
         L = st["latent"]
-        ne = len(self.encoder_hidden_layers) + 1
-        drops = st.get("drops") or [0.0] * len(st["linears"])
-        bn = st.get("bn") or [None] * len(st["linears"])
+        norm, post, drops, bn = self._export_parts()
         enc = export.FeedForward(st["linears"][:L], st["acts"][:L], self._export_dropout(self.encoder_config, drops[:L]), bn[:L])
         dec_cfg = self.decoder_config if self.decoder_config is not None else self.encoder_config
         dec = export.FeedForward(st["linears"][L:], st["acts"][L:], self._export_dropout(dec_cfg, drops[L:]), bn[L:])
-        norm = export.Normalization(self.features_norm_mean, self.features_norm_range) if self.feats_norm_mode is not None else None
-        post = export.Normalization(*st["post"]) if st.get("post") is not None else None
         return export.AutoEncoderCV(norm, enc, dec, post)
-
-    def train(self) -> bool:
-        ok = super().train()
-        if ok:
-            self.cv["norm_in"] = (self.features_norm_mean, self.features_norm_range)
-        return ok
 
 
 class DeepTICACalculator(NonLinear):
@@ -1432,9 +1125,8 @@ class DeepTICACalculator(NonLinear):
 
     def layer_plan(self):
         act, drop, bn = self._layer_options(self.encoder_config, len(self.encoder_hidden_layers))
-        self._bn_plan = bn
         dims = [self.num_features] + self.encoder_hidden_layers + [self.cv_dimension]
-        return dims, act, drop, len(dims) - 1
+        return dims, act, drop, bn, len(dims) - 1
 
     def n_samples_local(self) -> int:
         return self.training_data.shape[0] - self.lag()   # pairs (i, i+lag) inside this rank's block
@@ -1457,18 +1149,9 @@ class DeepTICACalculator(NonLinear):
 
     def to_torch_module(self):
         st = self.cv
-        nl = len(st["linears"])
-        nn_ = export.FeedForward(st["linears"], st["acts"], self._export_dropout(self.encoder_config, st.get("drops") or [0.0] * nl), st.get("bn"))
-        norm = export.Normalization(self.features_norm_mean, self.features_norm_range) if self.feats_norm_mode is not None else None
-        tica = export.TICA(st["tica"][1], st["tica"][0])
-        post = export.Normalization(*st["post"]) if st.get("post") is not None else None
-        return export.DeepTICA(norm, nn_, tica, post)
-
-    def train(self) -> bool:
-        ok = super().train()
-        if ok:
-            self.cv["norm_in"] = (self.features_norm_mean, self.features_norm_range)
-        return ok
+        norm, post, drops, bn = self._export_parts()
+        nn_ = export.FeedForward(st["linears"], st["acts"], self._export_dropout(self.encoder_config, drops), bn)
+        return export.DeepTICA(norm, nn_, export.TICA(st["tica"][1], st["tica"][0]), post)
 
 
 def kl_annealing_settings(section: Optional[Dict], max_epochs: int) -> Dict:
@@ -1551,22 +1234,10 @@ class VAECalculator(NonLinear):
         if self.comm.world > 1:
             raise ValueError("the VAE is not supported in a frame-sharded (multi-GPU) fit: run this CV on one GPU")
         enc_act, enc_drop, enc_bn = self._encoder_options()
-        dec_cfg = self.decoder_config if self.decoder_config is not None else self.encoder_config
-        dec_act, dec_drop, dec_bn = self._layer_options(dec_cfg, len(self.decoder_hidden_layers))
-        if self.feats_norm_mode == "min_max_range1" and dec_act[-1] != "custom_sigmoid":
-            logger.warning(f"The last layer activation function of the decoder is set to {dec_act[-1]}, but the features are "
-                           "normalized using min max with range [0, 1]. Changing the activation function to 'sigmoid'.")
-            dec_act[-1] = "custom_sigmoid"
-        elif self.feats_norm_mode == "min_max_range2" and dec_act[-1] != "tanh":
-            logger.warning(f"The last layer activation function of the decoder is set to {dec_act[-1]}, but the features are "
-                           "normalized using min max with range [-1, 1]. Changing the activation function to 'tanh'.")
-            dec_act[-1] = "tanh"
-        if dec_drop[-1]:
-            logger.warning("Dropout in the last layer of the decoder is not recommended.")
-        self._bn_plan = enc_bn + [False] + dec_bn
+        dec_act, dec_drop, dec_bn = self._decoder_options()
         enc = [self.num_features] + self.encoder_hidden_layers + [2 * self.cv_dimension]
         dec = [self.cv_dimension] + self.decoder_hidden_layers + [self.num_features]
-        return enc + dec[1:], enc_act + [None] + dec_act, enc_drop + [0.0] + dec_drop, len(enc) - 1
+        return enc + dec[1:], enc_act + [None] + dec_act, enc_drop + [0.0] + dec_drop, enc_bn + [False] + dec_bn, len(enc) - 1
 
     def _init_linears(self, dims):
         """Construction order of VariationalAutoEncoderCV: encoder Linears, mean_nn, log_var_nn, decoder Linears (global RNG);
@@ -1579,16 +1250,6 @@ class VAECalculator(NonLinear):
         out = [(l.weight.detach().numpy().copy(), l.bias.detach().numpy().copy()) for l in lins]
         out.append((torch.cat([mean.weight, log_var.weight]).detach().numpy().copy(), torch.cat([mean.bias, log_var.bias]).detach().numpy().copy()))
         return out + [(l.weight.detach().numpy().copy(), l.bias.detach().numpy().copy()) for l in dec]
-
-    def n_samples_local(self) -> int:
-        return self.training_data.shape[0]
-
-    def n_val_samples_local(self) -> int:
-        return self.validation_data.shape[0]
-
-    def _records_to_metrics(self, rec, need_eig: bool = True):
-        w = rec[:, 1]
-        return float((rec[:, 0] * w).sum() / w.sum()), None, None
 
     # ---- the epoch loop's hooks
     def _noise_for(self, batches) -> List[torch.Tensor]:
@@ -1611,7 +1272,8 @@ class VAECalculator(NonLinear):
         self.engine.set_noise(torch.cat(eps).to(dev) if eps else torch.zeros(0, self.cv_dimension, device=dev))   # one copy per epoch
         return vb
 
-    def _on_validation(self, epoch, rec_train, rec_val, valid_loss, metrics, snapshot):
+    def _on_validation(self, epoch, rec_train, rec_val, metrics, snapshot):
+        valid_loss = metrics["valid_loss"][-1]
         for tag, rec in (("train", rec_train), ("valid", rec_val)):
             w = rec[:, 1]
             metrics.setdefault(f"{tag}_reconstruction_loss", []).append(float((rec[:, 2] * w).sum() / w.sum()))
@@ -1632,29 +1294,7 @@ class VAECalculator(NonLinear):
             return last_state, metrics["valid_loss"][-1]
         return None
 
-    def train(self) -> bool:
-        ok = super().train()
-        if ok:
-            self.cv["norm_in"] = (self.features_norm_mean, self.features_norm_range)
-        return ok
-
-    def plot_training_metrics(self):
-        """training_metrics.zip with the VAE's metrics beside the common ones (reference :2880-2893; no figures)."""
-        if not self.training_config.get("save_loss", True) or self.metrics is None:
-            return
-        paths = []
-        for key in ("train_loss", "valid_loss", "epoch", "train_kl_loss", "valid_kl_loss", "train_reconstruction_loss",
-                    "valid_reconstruction_loss", "beta", "lr"):
-            if key not in self.metrics:
-                if key == "lr":
-                    logger.warning(f"Metric {key} not found in metrics. It will not be saved.")
-                continue
-            p = os.path.join(self.training_output_folder, f"{key}.npy")
-            np.save(p, np.array(self.metrics[key]))
-            paths.append(p)
-        np.savetxt(os.path.join(self.training_output_folder, "model_score.txt"), np.array([self.cv_score]), fmt="%.7g")
-        zip_files(os.path.join(self.training_output_folder, "training_metrics.zip"), *paths)
-        remove_files(*paths)
+    metric_files = NonLinear.metric_files + ("train_kl_loss", "valid_kl_loss", "train_reconstruction_loss", "valid_reconstruction_loss", "beta", "lr")
 
     # ---- projection / sensitivity / export
     def summed_cv_gradient(self) -> np.ndarray:
@@ -1669,16 +1309,13 @@ class VAECalculator(NonLinear):
         L = st["latent"]   # the first decoder Linear; L - 1 = the heads
         d = self.cv_dimension
         n_enc = L - 1
-        drops = st.get("drops") or [0.0] * len(st["linears"])
-        bn = st.get("bn") or [None] * len(st["linears"])
+        norm, post, drops, bn = self._export_parts()
         given = self._fit_list(self.encoder_config.get("dropout", [None] * n_enc), n_enc, "dropout") if n_enc else []
         enc = export.FeedForward(st["linears"][:n_enc], st["acts"][:n_enc], [None if g is None else float(p) for g, p in zip(given, drops[:n_enc])],
                                  bn[:n_enc])
         hw, hb = st["linears"][n_enc]
         dec_cfg = self.decoder_config if self.decoder_config is not None else self.encoder_config
         dec = export.FeedForward(st["linears"][L:], st["acts"][L:], self._export_dropout(dec_cfg, drops[L:]), bn[L:])
-        norm = export.Normalization(self.features_norm_mean, self.features_norm_range) if self.feats_norm_mode is not None else None
-        post = export.Normalization(*st["post"]) if st.get("post") is not None else None
         return export.VariationalAutoEncoderCV(norm, enc, (hw[:d], hb[:d]), (hw[d:], hb[d:]), dec, post)
 
 
