@@ -78,6 +78,7 @@ SIGNATURES = {
     "dcv_superpose": (C.c_int, [_P, _I64, _I64, _I64, _I64, _I32, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P, _I64, _P, _P, _SZ, _P]),
     "dcv_interpolate_workspace": (_SZ, [_I64, _I32, _I32, _I64]),
     "dcv_interpolate": (C.c_int, [_P, _I64, _I64, _I64, _I64, _I32, _P, _I32, _I32, _I32, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
+    "dcv_transform_frames": (C.c_int, [_P, _I64, _I64, _I64, _I64, _I32, _P, _I64, _P, _I64, _I64, _I64, _P]),
     "dcv_normalize": (C.c_int, [_P, _P, _I64, _I32, _I64, _I64, _P, _P, _P]),
     "dcv_lagged_cov_workspace": (_SZ, [_I64, _I32, _I32]),
     "dcv_lagged_cov": (C.c_int, [_P, _I64, _I32, _I64, _I32, _P, _P, _P, _SZ, _P]),

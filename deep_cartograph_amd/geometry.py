@@ -7,12 +7,13 @@ to the device as they are in the file, results come back per chunk.  No CPU fall
 raises DcvError.
 
 Not reproduced: MDAnalysis rounds the aligned positions to float32 before the group RMSD and the RMSF, here they stay
-float64; residues are not mapped between different topologies (the reference uses Biopython for that): selections are
-applied to each topology as it is and must select equally many atoms; mass weights are not supported (the reference
+float64; the analyses do not map residues between different topologies (align_trajectory's caller does, sequence.py):
+selections are applied to each topology as it is and must select equally many atoms; mass weights are not supported (the reference
 fits unweighted too)."""
 from __future__ import annotations
 
 import logging
+import os
 from typing import Optional, Tuple
 
 import numpy as np
@@ -149,6 +150,69 @@ def rmsf(traj, top, selection: str, fit_selection: str, memory_budget: Optional[
     resids = top.resids[sel]
     residues = np.unique(resids)
     return np.asarray([per_atom[resids == r].mean() for r in residues], dtype=np.float64), residues
+
+
+def align_frame_bytes(traj: trajectory.Trajectory, dcd: bool) -> int:
+    """Device bytes one frame of an `align_trajectory` chunk takes: its input record, its output record (DCD image or
+    dense row) and its transform row."""
+    words_out = 3 * (traj.n_atoms + 2) if dcd else 3 * traj.n_atoms
+    return 4 * traj.frame_stride + 4 * words_out + 128
+
+
+def align_trajectory(traj, top, fit, fit_ref, output_path: str, memory_budget: Optional[int] = None) -> np.ndarray:
+    """Fits every frame onto `fit_ref` (n_fit x 3, Angstrom) on the atoms `fit` (unweighted, hip.superpose) and writes
+    ALL atoms of every frame, moved by the frame's transform (hip.transform_frames), to `output_path`: a `.dcd` without
+    unit-cell blocks or a `.npy` of (n, A, 3) float32.  Returns the aligned first frame, float32 [A, 3].  Frames go
+    through the device in chunks that hold their input records and their output image at once, at most `memory_budget`
+    bytes (default: a quarter of free device memory, at most 4 GiB); they land under `<output_path>.partial` and are
+    renamed at the end.  The fit set is bounded by dcv_superpose's staging limit of 5 461 atoms; the number of atoms
+    written is not bounded.  float64 arithmetic with one rounding (MDAnalysis translates, rotates and translates in
+    float32)."""
+    from . import hip
+
+    torch = _require_device("align_trajectory")
+    top = _as_topology(top)
+    traj = _as_trajectory(traj, top.n_atoms)
+    ext = os.path.splitext(output_path)[1].lower()
+    if ext not in (".dcd", ".npy"):
+        raise ValueError(f"{output_path}: the aligned trajectory is written as .dcd or .npy")
+    fit = np.asarray(fit, dtype=np.int64).reshape(-1)
+    fit_ref = np.asarray(fit_ref, dtype=np.float64)
+    n, A = traj.n_frames, traj.n_atoms
+    if n == 0:
+        raise ValueError("the trajectory has no frames")
+    if memory_budget is None:
+        memory_budget = min(torch.cuda.mem_get_info()[0] // 4, DEFAULT_CHUNK_BYTES)
+    chunk = int(max(1, min(n, memory_budget // align_frame_bytes(traj, ext == ".dcd"))))
+    logger.info(f"Aligning {n} frames of {A} atoms on {len(fit)} atoms in chunks of {chunk} frames")
+    tmp_path = output_path + ".partial"
+    writer = trajectory.write_dcd(tmp_path, A) if ext == ".dcd" else None
+    rows = None if writer else np.lib.format.open_memmap(tmp_path, mode="w+", dtype=np.float32, shape=(n, A, 3))
+    first = None
+    for lo in range(0, n, chunk):
+        hi = min(n, lo + chunk)
+        span, layout = traj.span(lo, hi)
+        buf = torch.from_numpy(np.array(span, dtype=np.float32)).cuda()
+        transform = hip.superpose(buf, A, fit, fit_ref, strides=layout, want=("transform",))["transform"]
+        if writer:
+            image = torch.empty((hi - lo) * writer.frame_words, dtype=torch.float32, device="cuda")
+            hip.transform_frames(buf, A, transform, strides=layout, out=image, out_strides=writer.layout())
+            image = image.cpu().numpy()   # the kernel writes the planes, the host the record markers
+            if lo == 0:
+                first = np.ascontiguousarray(image[:writer.frame_words].reshape(3, A + 2)[:, 1:-1].T)
+            writer.append(image)
+        else:
+            rows[lo:hi] = hip.transform_frames(buf, A, transform, strides=layout).cpu().numpy()
+            if lo == 0:
+                first = np.array(rows[0], dtype=np.float32)
+        del buf
+    if writer:
+        writer.close()
+    else:
+        rows.flush()
+        del rows
+    os.replace(tmp_path, output_path)
+    return first
 
 
 def drmsd(traj, top, selection: str, selection_stride: int, ref_top, memory_budget: Optional[int] = None) -> np.ndarray:

@@ -298,6 +298,45 @@ def interpolate(xyz: torch.Tensor, n_atoms: int, t, kind: str = "pchip", sel=Non
     return result
 
 
+def transform_frames(xyz: torch.Tensor, n_atoms: int, transform: torch.Tensor, strides=None, out: Optional[torch.Tensor] = None,
+                     out_strides=None) -> torch.Tensor:
+    """Every atom of every frame moved by the frame's rigid transform (dcv_transform_frames):
+    ``out = (x - c_mob) . R + c_ref`` in float64, rounded once to float32; Angstrom in, Angstrom out.  Returns a float32
+    [n, n_atoms, 3] tensor.  No limit on the number of atoms.
+
+    ``xyz``, ``n_atoms`` and ``strides`` as in :func:`featurize`.  ``transform``: float64 [n, >= 15] on the device with
+    row stride >= 15, R row-major, c_mob, c_ref -- the ``transform`` output of :func:`superpose` as it is.  ``out`` /
+    ``out_strides = (offset, frame, atom, comp)`` as in :func:`interpolate`: a 1-D float32 buffer in which only the
+    coordinate slots are written (the planes of DCD frame records, for instance); it must not overlap ``xyz``."""
+    _require_gpu(xyz, transform, out)
+    n_atoms = int(n_atoms)
+    n, base, fs, as_, cs = _coordinates("transform_frames", xyz, n_atoms, strides)
+    if (transform.dim() != 2 or transform.dtype != torch.float64 or transform.shape[0] != n or transform.shape[1] < 15
+            or transform.stride(1) != 1 or transform.device != xyz.device):
+        raise DcvError(f"transform_frames: transform must be a float64 ({n}, >= 15) tensor with unit column stride on {xyz.device}, "
+                       f"got {tuple(transform.shape)} {transform.dtype} strides {transform.stride()} on {transform.device}")
+    ldt = max(int(transform.stride(0)), int(transform.shape[1])) if n <= 1 else int(transform.stride(0))   # a one-row stride is arbitrary
+    if (out is None) != (out_strides is None):
+        raise DcvError("transform_frames: out and out_strides go together")
+    if out is None:
+        out = result = torch.empty(n, n_atoms, 3, dtype=torch.float32, device=xyz.device)
+        off, ofs, oas, ocs = 0, 3 * n_atoms, 3, 1
+    else:
+        result = out
+        off, ofs, oas, ocs = (int(v) for v in out_strides)
+        if out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous() or out.device != xyz.device:
+            raise DcvError("transform_frames: out must be a contiguous 1-D float32 buffer on the device of the coordinates")
+        last = off + max(n - 1, 0) * ofs + (n_atoms - 1) * oas + 2 * ocs
+        if off < 0 or min(ofs, oas, ocs) < 1 or (n > 0 and last >= out.numel()):
+            raise DcvError(f"transform_frames: output layout {tuple(out_strides)} with {n_atoms} atoms and {n} frames reaches element "
+                           f"{last} of a buffer of {out.numel()} (strides must be >= 1)")
+    if n == 0:
+        return result   # an empty tensor has no data pointer to hand to the library
+    check(_lib.load().dcv_transform_frames(base, n, fs, as_, cs, n_atoms, _ptr(transform), ldt, out.data_ptr() + 4 * off, ofs, oas, ocs,
+                                           _stream()), "dcv_transform_frames")
+    return result
+
+
 def normalize(X: torch.Tensor, mean: torch.Tensor, rng: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(x - mean) / range in float32; ``out`` may be X itself (in place)."""
     _require_gpu(X, mean, rng, out)

@@ -1,5 +1,5 @@
 """The tools of the CV-fit path with the reference's API (argument names, output tree,
-CSV formats): analyze_geometry (tools/analyze_geometry/analyze_geometry.py:13-143), traj_augmentation (tools/traj_augmentation/traj_augmentation.py:23-131), compute_features (tools/compute_features/compute_features.py:25-227), filter_features (tools/filter_features/filter_features.py:22-31), train_colvars (tools/train_colvars/train_colvars.py:20-36), traj_projection
+CSV formats): align_trajectories (tools/align_trajectories/align_trajectories.py:70-189), analyze_geometry (tools/analyze_geometry/analyze_geometry.py:13-143), traj_augmentation (tools/traj_augmentation/traj_augmentation.py:23-131), compute_features (tools/compute_features/compute_features.py:25-227), filter_features (tools/filter_features/filter_features.py:22-31), train_colvars (tools/train_colvars/train_colvars.py:20-36), traj_projection
 (tools/traj_projection/traj_projection.py:19-27), traj_cluster (tools/traj_cluster/traj_cluster.py:
 18-28).  Figures, FES estimation and PDB/XTC extraction (matplotlib / MDAnalysis) are outside the
 accelerated path and are not produced."""
@@ -223,6 +223,71 @@ def traj_augmentation(configuration: Dict, trajectories: Union[str, List[str]], 
             augmented_topologies.append(new_top)
     logger.info("Elapsed time (Trajectory Augmentation): %s", time.strftime("%H h %M min %S s", time.gmtime(time.time() - t0)))
     return augmented_trajectories, augmented_topologies
+
+
+def align_trajectories(trajectory_data: Union[str, List[str]], topology_data: Union[str, List[str]], ref_topology: Optional[str] = None,
+                       output_folder: str = "align_trajectories", memory_budget: Optional[int] = None):
+    """Every trajectory superposed frame by frame onto the reference topology (default: the first topology) and written
+    with ALL its atoms, on the device (geometry.align_trajectory: hip.superpose for the fit, hip.transform_frames for
+    the atoms) instead of with MDAnalysis' AlignTraj.  The fit atoms are the C-alpha atoms of the residues that a local
+    sequence alignment (sequence.py, in place of Biopython) maps from the reference into every topology; they pair up
+    in topology order on both sides (MDAnalysis with match_atoms=False), and unequal counts raise ValueError.  Writes
+    <out>/<trajectory file name> in the input's format (.dcd or .npy) and <out>/<topology stem>.pdb with all atoms at
+    the positions of the first aligned frame, and returns (aligned trajectories, aligned topologies) -- the reference
+    returns None.  One topology serves all trajectories, or one per trajectory.  Without common residues an error is
+    logged and nothing is written, as in the reference.  Limits: at most 5 461 fit atoms (dcv_superpose's staging), so
+    5 461 common residues; any number of atoms is written.  The unit-cell block of an input DCD is not carried over and
+    the header times are the writer's.  `memory_budget` bounds a chunk of frames (input and output) on the device.  No
+    CPU fallback."""
+    import dataclasses
+
+    import torch
+
+    from . import geometry, sequence, trajectory
+    from ._lib import DcvError
+
+    t0 = time.time()
+    trajectories, topologies = _as_list(trajectory_data) or [], _as_list(topology_data) or []
+    if not trajectories:
+        logger.warning("No trajectories provided. Nothing to align.")
+        return [], []
+    if len(topologies) == 1:
+        topologies = topologies * len(trajectories)
+    if len(trajectories) != len(topologies):
+        raise ValueError(f"Number of trajectories ({len(trajectories)}) and topologies ({len(topologies)}) do not match.")
+    if ref_topology is None:
+        ref_topology = topologies[0]
+        logger.info(f"No reference topology provided. Using first topology as reference: {Path(ref_topology).name}")
+    for path in trajectories + topologies + [ref_topology]:
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"File not found: {path}")
+    out_trajs = [os.path.join(output_folder, Path(t).name) for t in trajectories]
+    out_tops = [os.path.join(output_folder, Path(t).stem + ".pdb") for t in topologies]
+    for src, dst in zip(trajectories, out_trajs):
+        if os.path.splitext(src)[1].lower() not in (".dcd", ".npy"):
+            raise ValueError(f"{src}: unsupported trajectory format (supported: .dcd, .npy)")
+        if os.path.realpath(src) == os.path.realpath(dst):
+            raise ValueError(f"The aligned trajectory would be written over its input {src}, which is memory-mapped while it is read: "
+                             "choose another output folder")
+    ref = trajectory.read_topology(ref_topology)
+    tops = {p: trajectory.read_topology(p) for p in dict.fromkeys(topologies)}
+    common = sequence.common_resids(ref, [tops[p] for p in tops])
+    logger.info(f"Found {len(common)} common residues across all topologies.")
+    if not common:
+        logger.error("No common residues found across topologies. Cannot align trajectories.")
+        return [], []
+    if not torch.cuda.is_available():
+        raise DcvError("align_trajectories needs an MI355X (cuda) device: the frames are fitted and moved by libdcv.so, there is no CPU fallback")
+    os.makedirs(output_folder, exist_ok=True)
+    for traj_path, top_path, out_traj, out_top in zip(trajectories, topologies, out_trajs, out_tops):
+        top = tops[top_path]
+        ref_fit, fit = sequence.fit_atoms(ref, top, common, what=top_path)
+        fit_ref = ref.positions[ref_fit].astype(np.float64)
+        logger.info(f"Aligning trajectory '{Path(traj_path).name}' with topology '{Path(top_path).name}' on {len(fit)} C-alpha atoms")
+        first = geometry.align_trajectory(traj_path, top, fit, fit_ref, out_traj, memory_budget)
+        trajectory.write_topology(out_top, dataclasses.replace(top, positions=first))
+    logger.info("Elapsed time (Align trajectories): %s", time.strftime("%H h %M min %S s", time.gmtime(time.time() - t0)))
+    return out_trajs, out_tops
 
 
 def filter_features(configuration: Dict, colvars_paths: Union[str, List[str]], waypoint_colvars_paths: Optional[List[str]] = None,

@@ -206,6 +206,31 @@ int dcv_interpolate(const float* xyz_d, int64_t n_knots, int64_t frame_stride, i
                     float* out_d, int64_t out_frame_stride, int64_t out_atom_stride, int64_t out_comp_stride,
                     void* ws_d, size_t ws_bytes, void* stream);
 
+/* ---- rigid transform of whole frames (align_trajectories) ----------------------------------------------------------
+ * Applies to EVERY atom of frame f the transform in row f of transform_d: the first 15 doubles of a row of
+ * dcv_superpose's transform output -- R row-major (row-vector convention), c_mob, c_ref --, rows ldt >= 15 doubles
+ * apart, so the n x 16 tensor is passed as it is.  For every frame f, atom a and component c = 0, 1, 2:
+ *     p   = (double)x[f, a, :] - c_mob[f]
+ *     out = (float)(p0 R[f][0][c] + p1 R[f][1][c] + p2 R[f][2][c] + c_ref[f][c])
+ * summed left to right in float64 without fused multiply-adds; the store is the one rounding.  No unit conversion.
+ * The input is addressed as in dcv_featurize (xyz_d, the three strides in elements: dense rows, DCD frame records in
+ * place with or without the unit-cell block, a frame stride that skips frames); coordinate c of atom a of frame f goes
+ * to out_d[f*out_frame_stride + a*out_atom_stride + c*out_comp_stride] (strides >= 1) as in dcv_interpolate: a dense
+ * (n, A, 3) array or the planes of a DCD record image.  Only those elements are written.  Nothing is staged in LDS:
+ * there is no limit on the number of atoms (dcv_superpose's `aligned` output stops at 5461).  A non-finite transform
+ * row gives non-finite coordinates in its own frame only.
+ * Everything is validated before anything is launched.  DCV_EINVAL: a NULL pointer or one off the 4-byte (transform:
+ * 8-byte) grid; n_atoms <= 0; n_frames < 0; bad strides (input: frame < 0, atom or component < 1; output: any < 1);
+ * ldt < 15; an input element range [xyz_d, xyz_d + last] that overlaps the output's, both computed from the strides
+ * (the map is not in place), or transform rows that overlap the output.  n_frames = 0 is DCV_OK and launches nothing.  No workspace.
+ * One launch; a thread owns four consecutive atoms of one frame (16-byte accesses where the atom stride is 1 or the
+ * rows are dense; the first and the last group of a row are moved inside the row and overlap their neighbours, whose
+ * atoms are then stored twice with the same bits), several frames share a workgroup when there are few atoms, at most
+ * 2048 workgroups stride over the rest.  Algorithmic traffic: 12 bytes read and 12 written per atom and frame, 120 per frame for the transform. */
+int dcv_transform_frames(const float* xyz_d, int64_t n_frames, int64_t frame_stride, int64_t atom_stride, int64_t comp_stride,
+                         int32_t n_atoms, const double* transform_d, int64_t ldt,
+                         float* out_d, int64_t out_frame_stride, int64_t out_atom_stride, int64_t out_comp_stride, void* stream);
+
 /* ---------------------------------------------------------------- normalisation (a3)
  * Replaces LinearCalculator.normalize_data, cv_calculator.py:833-835
  * (data.sub_(mean).div_(range) in float32).  Y may alias X (in place, as the reference). */
