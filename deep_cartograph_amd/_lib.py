@@ -74,6 +74,9 @@ SIGNATURES = {
     "dcv_dip_sorted": (C.c_int, [_P, _I64, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
     "dcv_featurize_workspace": (_SZ, [_I64, _I32, _I32]),
     "dcv_featurize": (C.c_int, [_P, _I64, _I64, _I64, _I64, _I32, _P, _I32, C.c_double, _P, _I64, _P, _SZ, _P]),
+    "dcv_featurize_project_workspace": (_SZ, [_I64, _I32, _I32, _I32, _I32]),
+    "dcv_featurize_project": (C.c_int, [_P, _I64, _I64, _I64, _I64, _I32, _P, _I32, _I32, C.c_double, _P, _P, _P, _I32, _P, _P, _P, _P, _I64,
+                                        _P, _P, _SZ, _P]),
     "dcv_superpose_workspace": (_SZ, [_I64, _I32, _I32, _I32]),
     "dcv_superpose": (C.c_int, [_P, _I64, _I64, _I64, _I64, _I32, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P, _I64, _P, _P, _SZ, _P]),
     "dcv_interpolate_workspace": (_SZ, [_I64, _I32, _I32, _I64]),

@@ -3,8 +3,8 @@
 //
 // A workgroup owns a tile of kStageTile frames (fewer when the atoms it needs do not fit the LDS budget).  It stages
 // the coordinates of the atoms the features use into LDS with coalesced loads, computes every feature of its frames
-// in float64 from LDS (PLUMED computes in double: p = (double)x * unit, one rounding to float32 on store) and writes
-// the output rows with consecutive lanes on consecutive columns.  No atomics, no state between workgroups.
+// in float64 from LDS (feat_math.h: PLUMED computes in double, p = (double)x * unit; one rounding to float32 on store)
+// and writes the output rows with consecutive lanes on consecutive columns.  No atomics, no state between workgroups.
 //
 // The two staging forms (ROWS and GATHER), their host-side choice and the LDS budget live in stage.h, which
 // superpose.hip shares.
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.h"
+#include "feat_math.h"
 #include "stage.h"
 
 namespace dcv {
@@ -28,7 +29,6 @@ struct FeatArgs {
 };
 
 __global__ __launch_bounds__(kFeatThreads) void featurize_kernel(const FeatArgs a, const int dlanes) {
-#pragma clang fp contract(off)   // a*b - c*d of identical products must be exactly 0 (collinear atoms), as in NumPy / PLUMED
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* lds = reinterpret_cast<float*>(smem);
     const int64_t f0 = (int64_t)blockIdx.x * a.st.tile;
@@ -48,31 +48,9 @@ __global__ __launch_bounds__(kFeatThreads) void featurize_kernel(const FeatArgs 
         for (int f = fg; f < nf; f += fgroups) {
             const float* lf = lds + f * a.st.lfs;
             float* of = o + (f0 + f) * a.ldo;
-            const double p0x = (double)lf[s0] * unit, p0y = (double)lf[s0 + lcs] * unit, p0z = (double)lf[s0 + 2 * lcs] * unit;
-            const double p1x = (double)lf[s1] * unit, p1y = (double)lf[s1 + lcs] * unit, p1z = (double)lf[s1 + 2 * lcs] * unit;
-            const double b0x = p1x - p0x, b0y = p1y - p0y, b0z = p1z - p0z;
-            if (kind == DCV_FEAT_DISTANCE) {
-                of[0] = (float)sqrt(b0x * b0x + b0y * b0y + b0z * b0z);
-                continue;
-            }
-            const double p2x = (double)lf[s2] * unit, p2y = (double)lf[s2 + lcs] * unit, p2z = (double)lf[s2 + 2 * lcs] * unit;
-            const double p3x = (double)lf[s3] * unit, p3y = (double)lf[s3 + lcs] * unit, p3z = (double)lf[s3 + 2 * lcs] * unit;
-            const double b1x = p2x - p1x, b1y = p2y - p1y, b1z = p2z - p1z;
-            const double b2x = p3x - p2x, b2y = p3y - p2y, b2z = p3z - p2z;
-            const double n1x = b0y * b1z - b0z * b1y, n1y = b0z * b1x - b0x * b1z, n1z = b0x * b1y - b0y * b1x;
-            const double n2x = b1y * b2z - b1z * b2y, n2y = b1z * b2x - b1x * b2z, n2z = b1x * b2y - b1y * b2x;
-            const double x = n1x * n2x + n1y * n2y + n1z * n2z;
-            const double mx = n1y * n2z - n1z * n2y, my = n1z * n2x - n1x * n2z, mz = n1x * n2y - n1y * n2x;
-            const double l1 = sqrt(b1x * b1x + b1y * b1y + b1z * b1z);
-            const double q = mx * b1x + my * b1y + mz * b1z;
-            const double y = l1 == 0.0 ? 0.0 : q / l1;   // coincident middle atoms: atan2(0, 0)
-            if (kind == DCV_FEAT_TORSION) {
-                of[0] = (float)atan2(y, x);
-            } else {
-                const double r = hypot(x, y);
-                of[0] = (float)(r == 0.0 ? 0.0 : y / r);
-                of[1] = (float)(r == 0.0 ? 1.0 : x / r);
-            }
+            const FeatValue v = feature_value(lf, kind, s0, s1, s2, s3, lcs, unit);
+            of[0] = (float)v.v0;
+            if (kind == DCV_FEAT_TORSION_SINCOS) of[1] = (float)v.v1;
         }
     }
 }

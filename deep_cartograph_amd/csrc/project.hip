@@ -3,7 +3,8 @@
 // 16 lanes share a row (16-byte loads, 256 contiguous bytes per row segment), each lane keeps
 // 4 rows in flight so that the LDS-resident weights are read once per 4 rows; the 16 partial
 // dot products are combined with wave shuffles.  Per-column extrema of the output are reduced
-// per block and combined in a fixed order.  The 16-byte load and the host's rule for it are stream.h's.
+// per block and combined by minmax.h's finishing launch.  The 16-byte load and the host's rule for it are stream.h's.
+#include "minmax.h"
 #include "stream.h"
 
 namespace dcv {
@@ -171,27 +172,6 @@ __global__ __launch_bounds__(kProjThreads) void project_kernel(ProjArgs a) {
             a.part[((int64_t)blockIdx.x * 2 + which) * D + c] = v;
         }
     }
-}
-
-// one workgroup per (min | max, component): threads take the blocks b = t, t + 256, ..., LDS tree (min / max are exact
-// in any order)
-template <int D>
-__global__ __launch_bounds__(256) void project_minmax_final(const float* __restrict__ part, int nblocks, int d, float* __restrict__ minmax) {
-    __shared__ float s_red[256];
-    const int t = threadIdx.x;
-    const int which = blockIdx.x / d, c = blockIdx.x % d;
-    float v = which == 0 ? INFINITY : -INFINITY;
-    for (int b = t; b < nblocks; b += 256) {
-        const float w = part[((int64_t)b * 2 + which) * D + c];
-        v = which == 0 ? fminf(v, w) : fmaxf(v, w);
-    }
-    s_red[t] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) s_red[t] = which == 0 ? fminf(s_red[t], s_red[t + o]) : fmaxf(s_red[t], s_red[t + o]);
-        __syncthreads();
-    }
-    if (t == 0) minmax[which * d + c] = s_red[0];
 }
 
 static int proj_blocks(int64_t n) {

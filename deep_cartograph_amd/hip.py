@@ -176,6 +176,46 @@ def featurize(xyz: torch.Tensor, defs, n_atoms: int, strides=None, unit: float =
     return out
 
 
+def featurize_project(xyz: torch.Tensor, records, n_atoms: int, F: int, W: torch.Tensor, strides=None, unit: float = 0.1, fmean=None,
+                      frange=None, bias=None, cvmean=None, cvrange=None, want_minmax: bool = False, out: Optional[torch.Tensor] = None):
+    """(out [n, d] float32, minmax [2, d] or None): ``featurize`` then ``project_linear`` in one launch, without the
+    [n, F] matrix (dcv_featurize_project).
+
+    ``xyz``, ``n_atoms``, ``strides`` and ``unit`` as in :func:`featurize`.  ``records``: (n_rec, 8) int32
+    [kind, a0, a1, a2, a3, feature0, feature1, 0] on the host -- what ``trajectory.definitions_from_labels`` returns;
+    every feature in [0, F) is the value of exactly one record.  ``W``: contiguous float32 [F, d], d <= 16; the five
+    vectors as in :func:`project_linear`.  ``out``: optional float32 [n, d] tensor or view with unit column stride."""
+    _require_gpu(xyz, W, fmean, frange, bias, cvmean, cvrange, out)
+    records = np.ascontiguousarray(np.asarray(records), dtype=np.int32)
+    if records.ndim != 2 or records.shape[1] != 8 or records.shape[0] == 0:
+        raise DcvError(f"featurize_project: records must be a non-empty (n_rec, 8) int32 array, got shape {records.shape}")
+    n_atoms, F = int(n_atoms), int(F)
+    n, base, fs, as_, cs = _coordinates("featurize_project", xyz, n_atoms, strides)
+    if W.dim() != 2 or W.shape[0] != F or not W.is_contiguous() or W.dtype != torch.float32 or W.device != xyz.device:
+        raise DcvError(f"featurize_project: W must be a contiguous float32 {F} x d tensor on {xyz.device}")
+    d = W.shape[1]
+    for v, length, name in ((fmean, F, "fmean"), (frange, F, "frange"), (bias, d, "bias"), (cvmean, d, "cvmean"), (cvrange, d, "cvrange")):
+        _check_vector(v, length, "featurize_project: " + name, xyz.device)
+    if out is None:
+        out = torch.empty(n, d, dtype=torch.float32, device=xyz.device)
+    else:
+        _check_matrix(out)
+        if tuple(out.shape) != (n, d) or out.device != xyz.device:
+            raise DcvError(f"featurize_project: out has shape {tuple(out.shape)} on {out.device}, expected ({n}, {d}) on {xyz.device}")
+    mm = torch.empty(2, d, dtype=torch.float32, device=xyz.device) if want_minmax else None
+    if n == 0:   # an empty tensor has no data pointer to hand to the library
+        if mm is not None:
+            mm[0], mm[1] = float("inf"), float("-inf")
+        return out, mm
+    lib = _lib.load()
+    ws = _ws(lib.dcv_featurize_project_workspace(n, n_atoms, records.shape[0], F, d), xyz.device)
+    ldo = max(out.stride(0), d)   # the stride of a one-row tensor is arbitrary
+    check(lib.dcv_featurize_project(base, n, fs, as_, cs, n_atoms, records.ctypes.data, records.shape[0], F, float(unit), _ptr(fmean),
+                                    _ptr(frange), _ptr(W), d, _ptr(bias), _ptr(cvmean), _ptr(cvrange), _ptr(out), ldo, _ptr(mm), _ptr(ws),
+                                    ws.numel(), _stream()), "dcv_featurize_project")
+    return out, mm
+
+
 SUPERPOSE_OUTPUTS = ("transform", "rmsd", "aligned", "moments")
 
 

@@ -390,24 +390,47 @@ def train_colvars(configuration: Dict, train_colvars_paths: Union[str, List[str]
 
 def traj_projection(configuration: Dict, colvars_paths: List[str], topologies: List[str] = None, trajectory_names: List[str] = None,
                     model_paths: List[str] = None, model_traj_paths: Optional[List[List[str]]] = None,
-                    output_folder: Optional[str] = "traj_projection") -> Dict[str, List[str]]:
-    """Project new colvars files onto saved models: <out>/<cv>/<traj>/projected_trajectory.csv."""
+                    output_folder: Optional[str] = "traj_projection", *, trajectories: Optional[List[str]] = None) -> Dict[str, List[str]]:
+    """Project new colvars files onto saved models: <out>/<cv>/<traj>/projected_trajectory.csv.  With `trajectories`
+    (.dcd / .npy) instead of `colvars_paths` every model projects the coordinates themselves (project_trajectory): the
+    features it needs are recomputed on the device from its own feature names and the topology (`topologies`: one for
+    all trajectories, or one each), no colvars file and no features configuration involved."""
+    colvars_paths, trajectories = _as_list(colvars_paths) or [], _as_list(trajectories)
+    from_coordinates = trajectories is not None
+    if from_coordinates:
+        import torch
+
+        from ._lib import DcvError
+
+        topologies = _as_list(topologies) or []
+        if colvars_paths:
+            raise ValueError("traj_projection: give either colvars_paths or trajectories, not both")
+        if len(topologies) == 1:
+            topologies = topologies * len(trajectories)
+        if len(trajectories) != len(topologies):
+            raise ValueError(f"Number of trajectories ({len(trajectories)}) and topologies ({len(topologies)}) do not match.")
+        if not torch.cuda.is_available():
+            raise DcvError("traj_projection of trajectories needs an MI355X (cuda) device: the features are computed by libdcv.so, "
+                           "there is no CPU fallback")
     os.makedirs(output_folder, exist_ok=True)
     validate_configuration(configuration or {}, TrajProjectionSchema, output_folder)
-    colvars_paths = _as_list(colvars_paths)
+    inputs = trajectories if from_coordinates else colvars_paths
     if trajectory_names is None:
-        trajectory_names = [Path(p).stem for p in colvars_paths]
+        trajectory_names = [Path(p).stem for p in inputs]
     out: Dict[str, List[str]] = {}
     for model_path in model_paths or []:
         calc = CVCalculator.load(model_path, output_folder)
         paths = []
-        for i, (cp, name) in enumerate(zip(colvars_paths, trajectory_names)):
+        for i, (cp, name) in enumerate(zip(inputs, trajectory_names)):
             folder = os.path.join(output_folder, calc.cv_name, name)
             p = os.path.join(folder, "projected_trajectory.csv")
             if os.path.exists(p):  # traj_projection_workflow.py:235-238
                 paths.append(p)
                 continue
-            df = calc.project_colvars([cp], [topologies[i]] if topologies else None)
+            if from_coordinates:
+                df = calc.project_trajectory(cp, topologies[i])
+            else:
+                df = calc.project_colvars([cp], [topologies[i]] if topologies else None)
             if df is None:
                 continue
             os.makedirs(folder, exist_ok=True)

@@ -479,3 +479,92 @@ def feature_definitions(features_configuration: Dict, top: Topology) -> Tuple[Li
     if not names:
         raise ValueError("No features found, please check the features section of the configuration file and the topology.")
     return names, np.asarray(defs, dtype=np.int32).reshape(-1, 6)
+
+
+# ------------------------------------------------------------------------------------------------ labels -> records
+_LABEL_KINDS = {"dist": (FEAT_DISTANCE, 2), "tor": (FEAT_TORSION, 4), "sin": (FEAT_TORSION_SINCOS, 4), "cos": (FEAT_TORSION_SINCOS, 4)}
+
+
+def _label_atoms(label: str, n_entities: int, rest: str, index: Dict[Tuple[str, int], List[int]]) -> List[int]:
+    """The atoms of the entities ``@name_resid`` of a label, joined by '-' as ``feature_definitions`` joins them."""
+    if "center_" in rest:
+        raise ValueError(f"feature label '{label}': distances to a geometric center are not supported")
+    if not rest.startswith("@"):
+        raise ValueError(f"feature label '{label}' is not of the form <kind>-@name_resid-...")
+    parts = rest[1:].split("-@")
+    atoms = []
+    for part in parts:
+        name, sep, resid = part.rpartition("_")
+        if not sep or not name or not re.fullmatch(r"-?\d+", resid):
+            raise ValueError(f"feature label '{label}': entity '@{part}' is not of the form @name_resid")
+        found = index.get((name, int(resid)), [])
+        if len(found) != 1:
+            if len(parts) == 1 and n_entities == 4:   # '@phi_5', '@psi_5', ...: a named dihedral of the reference's real search mode
+                raise ValueError(f"feature label '{label}': named dihedrals ('@{part}') are not supported, only virtual dihedrals "
+                                 "given by their four atoms")
+            raise ValueError(f"feature label '{label}': entity '@{part}' matches {'no atom' if not found else f'{len(found)} atoms'} "
+                             "of the topology" + (" (several chains? the label cannot tell them apart)" if found else ""))
+        atoms.append(found[0])
+    if len(atoms) != n_entities:
+        raise ValueError(f"feature label '{label}' names {len(atoms)} atoms, its kind needs {n_entities}")
+    return atoms
+
+
+def definitions_from_labels(labels: List[str], top: Topology) -> np.ndarray:
+    """The inverse of the naming rules of ``feature_definitions``: the (n_rec, 8) int32 records
+    [kind, a0, a1, a2, a3, feature0, feature1, 0] of hip.featurize_project for the feature names of a model
+    (features_labels.txt).  The position of a label is its feature index.  ``dist-@a-@b`` and ``tor-@a-@b-@c-@d`` give
+    one record each (feature1 = -1); ``sin-X`` and ``cos-X`` of the same four atoms share ONE record (feature0 the sine,
+    feature1 the cosine), the index of a partner the model does not keep is -1.  Records stand in the order in which
+    the labels first name them.  Nothing is guessed: an entity that matches no atom or several, a duplicate label and
+    every other form (``coord-``, ``center_`` entities, ``@phi_7``, ...) raise ValueError naming the label."""
+    index: Dict[Tuple[str, int], List[int]] = {}
+    for i, (name, resid) in enumerate(zip(top.names, top.resids)):
+        index.setdefault((name, int(resid)), []).append(i)
+    records: List[List[int]] = []
+    sincos: Dict[Tuple[int, ...], int] = {}   # four atoms -> record
+    seen: Set[str] = set()
+    for feature, label in enumerate(labels):
+        label = str(label)
+        if label in seen:
+            raise ValueError(f"feature label '{label}' appears twice")
+        seen.add(label)
+        kind_name, sep, rest = label.partition("-")
+        if kind_name == "coord":
+            raise ValueError(f"feature label '{label}': coordinate features are not supported (they need a per-frame optimal fit)")
+        if not sep or kind_name not in _LABEL_KINDS:
+            raise ValueError(f"feature label '{label}' is not a dist-, tor-, sin- or cos- label")
+        kind, n_entities = _LABEL_KINDS[kind_name]
+        atoms = _label_atoms(label, n_entities, rest, index)
+        if kind != FEAT_TORSION_SINCOS:
+            records.append([kind, *atoms, *([0] * (4 - n_entities)), feature, -1, 0])
+            continue
+        r = sincos.setdefault(tuple(atoms), len(records))
+        if r == len(records):
+            records.append([kind, *atoms, -1, -1, 0])
+        records[r][5 if kind_name == "sin" else 6] = feature
+    if not records:
+        raise ValueError("no feature labels given")
+    return np.asarray(records, dtype=np.int32).reshape(-1, 8)
+
+
+def records_to_featurize_defs(records: np.ndarray, n_features: int) -> Tuple[np.ndarray, int, np.ndarray, np.ndarray]:
+    """(defs, n_columns, src, dst): the (n_rec, 6) records of hip.featurize that fill a frames x n_columns matrix whose
+    column i < n_features is feature i of ``records``.  A sine / cosine record whose two features are not neighbouring
+    columns (a lone sine or cosine, or a pair the model's order separates) writes its two values into a scratch pair
+    behind the features; column ``src[k]`` is then to be copied to column ``dst[k]``."""
+    records = np.asarray(records, dtype=np.int32).reshape(-1, 8)
+    defs = np.zeros((len(records), 6), dtype=np.int32)
+    defs[:, :5] = records[:, :5]
+    n_columns, src, dst = int(n_features), [], []
+    for r, (kind, f0, f1) in enumerate(records[:, [0, 5, 6]].tolist()):
+        if kind != FEAT_TORSION_SINCOS or (f0 >= 0 and f1 == f0 + 1):
+            defs[r, 5] = f0
+            continue
+        defs[r, 5] = n_columns
+        for k, f in enumerate((f0, f1)):
+            if f >= 0:
+                src.append(n_columns + k)
+                dst.append(f)
+        n_columns += 2
+    return defs, n_columns, np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)

@@ -121,6 +121,35 @@ int dcv_featurize(const float* xyz_d, int64_t n_frames, int64_t frame_stride, in
                   int32_t n_atoms, const int32_t* defs_h, int32_t n_defs, double unit,
                   float* out_d, int64_t ldo, void* ws_d, size_t ws_bytes, void* stream);
 
+/* ---- featurise and project in one launch (project_trajectory) ------------------------------------------------------
+ * dcv_featurize followed by dcv_project_linear without the frames x features matrix: coordinates in (addressed as in
+ * dcv_featurize), n_frames x d collective variables out, d <= 16.  Replaces, for a linear CV, what the reference hands
+ * to PLUMED through write_plumed_files (DISTANCE / TORSION commands and COMBINE lines evaluated during a simulation).
+ * rec_h is a HOST array of n_rec records of eight int32 [kind, a0, a1, a2, a3, feature0, feature1, 0]: kind and atoms as
+ * in dcv_featurize; feature0 is the feature index (row of W, entry of fmean / frange) of the record's value -- the sine
+ * of a DCV_FEAT_TORSION_SINCOS record, whose cosine is feature1.  An index of -1 means the value is not a feature (a
+ * sine or a cosine whose partner the model dropped); the single-valued kinds have feature1 = -1.
+ * Per frame and output column j:
+ *   f_i   the value dcv_featurize would store for feature i: float64 arithmetic, rounded once to float32;
+ *   xn_i  = (f_i - fmean_i) / frange_i in float32 IEEE, the bits dcv_normalize forms (f_i when both vectors are NULL);
+ *   y_j   = sum_i (double)xn_i * (double)W[i][j], accumulated in float64;
+ *   out_j = (float)((y_j + bias_j - cvmean_j) / cvrange_j), evaluated in float64 and rounded once
+ * (bias_d NULL = 0; cvmean_d / cvrange_d NULL = 0 / 1, both or neither).  The order of the sum over i is a function of
+ * the record list and d alone, so a frame's result depends on nothing but its own coordinates: it is bit-identical for
+ * any frame count, chunking of the frames between calls and layout of the coordinates.  out_d has row stride ldo >= d;
+ * minmax_d (2*d float32: per-column min then max of the stored values, or NULL) is reduced per workgroup and folded by
+ * the finishing launch of dcv_project_linear, without floating-point atomics.
+ * Validated before anything is launched (DCV_EINVAL): kinds, atom indices, feature indices in [-1, F) with at least one
+ * >= 0 per record, every feature in [0, F) written by exactly one record, 1 <= d <= 16, ldo >= d, fmean / frange both or
+ * neither, the strides, one frame of the staged atoms within LDS (5461 atoms); a workspace that is too small is
+ * DCV_ENOMEM.  n_frames = 0 is DCV_OK.  Algorithmic traffic per frame: 12 bytes per staged atom + 4*d. */
+size_t dcv_featurize_project_workspace(int64_t n_frames, int32_t n_atoms, int32_t n_rec, int32_t F, int32_t d);
+int dcv_featurize_project(const float* xyz_d, int64_t n_frames, int64_t frame_stride, int64_t atom_stride, int64_t comp_stride,
+                          int32_t n_atoms, const int32_t* rec_h, int32_t n_rec, int32_t F, double unit,
+                          const float* fmean_d, const float* frange_d, const float* W_d, int32_t d,
+                          const float* bias_d, const float* cvmean_d, const float* cvrange_d,
+                          float* out_d, int64_t ldo, float* minmax_d, void* ws_d, size_t ws_bytes, void* stream);
+
 /* ---- optimal rigid superposition (analyze_geometry: RMSD, average structure, RMSF) --------------------------------
  * Fits every frame onto a reference structure on the n_fit atoms fit_h (weights fit_w_h, NULL = all 1) and measures
  * on the n_sel atoms sel_h.  Coordinates are addressed as in dcv_featurize (xyz_d, the three strides, n_atoms); no
