@@ -4,6 +4,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdcv.so")
 
@@ -16,6 +18,12 @@ MODEL_VAE = 3
 FEAT_DISTANCE, FEAT_TORSION_SINCOS, FEAT_TORSION = 0, 1, 2   # DCV_FEAT_*: record kinds of dcv_featurize
 SUPERPOSE_MAX_GROUPS = 768   # DCV_SUPERPOSE_MAX_GROUPS
 INTERP_PCHIP, INTERP_MAKIMA = 0, 1   # DCV_INTERP_*: kinds of dcv_interpolate
+# dcv_xtc_frame: the per-frame descriptor of dcv_xtc_decode, as a NumPy record
+XTC_FRAME_DTYPE = np.dtype([("offset", "<i8"), ("nbytes", "<i4"), ("smallidx", "<i4"), ("precision", "<f4"), ("raw", "<i4"),
+                            ("minint", "<i4", (3,)), ("maxint", "<i4", (3,))], align=True)
+assert XTC_FRAME_DTYPE.itemsize == 48
+XTC_STATUS = {1: "the stream needs bits behind its nbytes", 2: "a run of small atoms would pass the atom count", 3: "smallidx left [9, 72]",
+              4: "maxint below minint, or a precision that is not finite and positive"}   # DCV_XTC_*
 
 
 class MlpDesc(C.Structure):
@@ -82,6 +90,8 @@ SIGNATURES = {
     "dcv_interpolate_workspace": (_SZ, [_I64, _I32, _I32, _I64]),
     "dcv_interpolate": (C.c_int, [_P, _I64, _I64, _I64, _I64, _I32, _P, _I32, _I32, _I32, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _SZ, _P]),
     "dcv_transform_frames": (C.c_int, [_P, _I64, _I64, _I64, _I64, _I32, _P, _I64, _P, _I64, _I64, _I64, _P]),
+    "dcv_xtc_decode_workspace": (_SZ, [_I64]),
+    "dcv_xtc_decode": (C.c_int, [_P, _I64, _P, _I64, _I32, C.c_float, _P, _I64, _I64, _I64, _P, _P, _SZ, _P]),
     "dcv_normalize": (C.c_int, [_P, _P, _I64, _I32, _I64, _I64, _P, _P, _P]),
     "dcv_lagged_cov_workspace": (_SZ, [_I64, _I32, _I32]),
     "dcv_lagged_cov": (C.c_int, [_P, _I64, _I32, _I64, _I32, _P, _P, _P, _SZ, _P]),

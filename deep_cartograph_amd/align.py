@@ -17,7 +17,7 @@ def main(argv=None):
 
     p = argparse.ArgumentParser("Deep Cartograph: Align Trajectories (MI355X)",
                                 description="Aligns trajectories and topologies to a reference topology.")
-    p.add_argument("-traj_data", dest="trajectory_data", required=True, nargs="+", help="trajectories to align (.dcd / .npy)")
+    p.add_argument("-traj_data", dest="trajectory_data", required=True, nargs="+", help="trajectories to align (.dcd / .npy; a GROMACS .xtc is imported first)")
     p.add_argument("-top_data", dest="topology_data", required=True, nargs="+", help="topology (.pdb): one for all, or one per trajectory")
     p.add_argument("-ref_top", dest="reference_topology", type=str, default=None,
                    help="reference topology (.pdb); defaults to the first topology of -top_data")

@@ -156,7 +156,7 @@ def main(argv=None):
     p = argparse.ArgumentParser("Deep Cartograph: Trajectory Augmentation (MI355X)",
                                 description="Augments trajectory samples interpolating the existing frames.")
     p.add_argument("-conf", "-configuration", dest="configuration_path", type=str, required=True, help="Path to configuration file (.yml).")
-    p.add_argument("-traj_data", dest="trajectory_data", required=True, nargs="+", help="trajectories to augment (.dcd / .npy)")
+    p.add_argument("-traj_data", dest="trajectory_data", required=True, nargs="+", help="trajectories to augment (.dcd / .npy; a GROMACS .xtc is imported first)")
     p.add_argument("-top_data", dest="topology_data", required=True, nargs="+", help="topology (.pdb): one for all, or one per trajectory")
     p.add_argument("-n", "-num_replicas", dest="num_replicas", type=int, default=1,
                    help="replicas of each trajectory; they differ by the noise (seed + replica)")

@@ -302,16 +302,17 @@ class CVCalculator(ABC):
 
     def project_trajectory(self, trajectory_path: str, topology_path: str, traj_stride: int = 1,
                            memory_budget: Optional[int] = None) -> pd.DataFrame:
-        """Project a trajectory (.dcd / .npy) with a fitted / loaded CV straight from its coordinates: the model's own
+        """Project a trajectory (.dcd / .npy; a GROMACS .xtc is imported first) with a fitted / loaded CV straight from its coordinates: the model's own
         feature names are turned back into atoms of ``topology_path`` (trajectory.definitions_from_labels), so neither a
         colvars file nor the features configuration of the training run is needed.  Frames are streamed in chunks as
         tools.compute_features streams them (``memory_budget`` bytes of device memory per chunk, DCD records read in
         place); only the frames x d result leaves the device.  Columns: the CV labels, as project_colvars.  No CPU fallback."""
-        from . import trajectory
+        from . import trajectory, xtc
         from .tools import ANGSTROM_TO_NM, DEFAULT_CHUNK_BYTES
 
         if self.cv is None:
             raise ValueError("CV has not been computed. Cannot project a trajectory.")
+        trajectory_path = xtc.route(trajectory_path, str(self.parent_output_path), memory_budget)   # a GROMACS .xtc is imported first
         for path in (trajectory_path, topology_path):
             if not os.path.exists(path):
                 raise FileNotFoundError(f"File not found: {path}")

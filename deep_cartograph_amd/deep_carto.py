@@ -1,6 +1,6 @@
 """`deep_carto`-style entry point for the accelerated part of the workflow:
 (analyze_geometry) -> (traj_augmentation) -> (compute_features) -> (filter_features) -> train_colvars -> (traj_projection of supplementary data) -> traj_cluster,
-starting from trajectories (.dcd / .npy coordinates plus a PDB topology: distances and virtual dihedrals are computed
+starting from trajectories (.dcd / .npy coordinates, or GROMACS .xtc files that are decoded first into <out>/xtc_import, plus a PDB topology: distances and virtual dihedrals are computed
 on the device) or from pre-computed feature matrices (PLUMED COLVAR text or the binary .npy fast path).
 With trajectories and an `analyze_geometry` section in the YAML, RMSD / RMSF / dRMSD are computed first (on the device,
 geometry.py) into <out>/analyze_geometry.  With seed trajectories (-seed_traj / -seed_top: a short morph between two
@@ -26,6 +26,7 @@ import sys
 import time
 from typing import Dict, List, Optional
 
+from . import xtc
 from .common import get_unique_path, read_configuration, read_features_list
 from .tools import analyze_geometry, compute_features, filter_features, traj_augmentation, traj_cluster, traj_projection, train_colvars
 
@@ -51,6 +52,9 @@ def deep_cartograph(configuration: Dict, colvars_paths: List[str], sup_colvars_p
     if not restart:
         output_folder = get_unique_path(output_folder)
     os.makedirs(output_folder, exist_ok=True)
+    # GROMACS .xtc inputs are decoded once, into <out>/xtc_import, and every step below reads the .dcd (xtc.py)
+    trajectory_data, sup_trajectory_data, seed_trajectory_data = (xtc.route(t, output_folder) for t in
+                                                                  (trajectory_data, sup_trajectory_data, seed_trajectory_data))
     trajectory_names = None
     if trajectory_data and colvars_paths:
         raise ValueError("give either colvars_paths or trajectory_data, not both: the computed features would replace the given ones")
@@ -112,9 +116,9 @@ def main(argv=None):
     p = argparse.ArgumentParser("deep_carto (MI355X CV-fit path)")
     p.add_argument("-conf", "-configuration", dest="configuration_path", required=True, help="YAML configuration")
     p.add_argument("-colvars", dest="colvars", nargs="+", default=None, help="training feature matrices (COLVAR text or .npy)")
-    p.add_argument("-traj", "-traj_data", dest="traj", nargs="+", default=None, help="training trajectories (.dcd / .npy); replaces -colvars")
+    p.add_argument("-traj", "-traj_data", dest="traj", nargs="+", default=None, help="training trajectories (.dcd / .npy; a GROMACS .xtc is imported first, into <out>/xtc_import); replaces -colvars")
     p.add_argument("-top", "-top_data", dest="top", nargs="+", default=None, help="topology (.pdb): one for all -traj files, or one per -traj file in the same order")
-    p.add_argument("-seed_traj", "-seed_traj_data", dest="seed_traj", nargs="+", default=None, help="seed trajectories (.dcd / .npy) to augment by interpolation; the augmented trajectories join the training trajectories")
+    p.add_argument("-seed_traj", "-seed_traj_data", dest="seed_traj", nargs="+", default=None, help="seed trajectories (.dcd / .npy / .xtc) to augment by interpolation; the augmented trajectories join the training trajectories")
     p.add_argument("-seed_top", "-seed_top_data", dest="seed_top", nargs="+", default=None, help="topology (.pdb) of the seed trajectories: one for all, or one per -seed_traj file")
     p.add_argument("-sup_traj", "-sup_traj_data", dest="sup_traj", nargs="*", default=None, help="supplementary trajectories to project; they are read with the first -top file")
     p.add_argument("-sup_colvars", dest="sup_colvars", nargs="*", default=None, help="supplementary feature matrices to project")

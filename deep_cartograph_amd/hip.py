@@ -377,6 +377,61 @@ def transform_frames(xyz: torch.Tensor, n_atoms: int, transform: torch.Tensor, s
     return result
 
 
+def xtc_decode(data: torch.Tensor, frames, n_atoms: int, scale: float = 10.0, out: Optional[torch.Tensor] = None, out_strides=None,
+               return_status: bool = False):
+    """The frames of a GROMACS ``.xtc`` file decoded on the device (dcv_xtc_decode).  Returns a float32
+    [n, n_atoms, 3] tensor: the file's nanometres times ``scale`` (10: Angstrom), ``(float)i * (1.0f / precision) * scale``
+    in float32.
+
+    ``data``: the bytes of the file, or a slice of them that starts on a multiple of 4 bytes, as a contiguous 1-D uint8
+    tensor on the device.  ``frames``: a host array of ``_lib.XTC_FRAME_DTYPE`` records, one per frame to decode, with
+    offsets relative to ``data`` -- ``trajectory.XtcIndex.span`` makes both; choosing records is how a stride or a
+    sub-range is applied.  ``out`` / ``out_strides = (offset, frame, atom, comp)`` as in :func:`interpolate`: a 1-D float32
+    buffer in which only the coordinate slots are written (the planes of DCD frame records, for instance).
+    A frame whose stream is inconsistent (it asks for bits behind its ``nbytes``, a run passes the atom count,
+    ``smallidx`` leaves [9, 72]) raises DcvError naming the first such frame; with ``return_status`` nothing is raised
+    and ``(out, status)`` is returned, ``status`` an int32 [n] device tensor (0: decoded), the coordinates of a marked
+    frame unwritten from the inconsistency on.  No stream makes the kernel read or write out of range."""
+    _require_gpu(data, out)
+    frames = np.ascontiguousarray(frames)
+    if frames.dtype != _lib.XTC_FRAME_DTYPE or frames.ndim != 1:
+        raise DcvError(f"xtc_decode: frames must be a 1-D array of XTC_FRAME_DTYPE records, got {frames.dtype} {frames.shape}")
+    if data.dim() != 1 or data.dtype != torch.uint8 or not data.is_contiguous():
+        raise DcvError(f"xtc_decode: data must be a contiguous 1-D uint8 tensor, got {tuple(data.shape)} {data.dtype}")
+    n, n_atoms = int(frames.size), int(n_atoms)
+    if n_atoms < 1:
+        raise DcvError(f"xtc_decode: {n_atoms} atoms")
+    if (out is None) != (out_strides is None):
+        raise DcvError("xtc_decode: out and out_strides go together")
+    if out is None:
+        out = result = torch.empty(n, n_atoms, 3, dtype=torch.float32, device=data.device)
+        off, ofs, oas, ocs = 0, 3 * n_atoms, 3, 1
+    else:
+        result = out
+        off, ofs, oas, ocs = (int(v) for v in out_strides)
+        if out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous() or out.device != data.device:
+            raise DcvError("xtc_decode: out must be a contiguous 1-D float32 buffer on the device of the bytes")
+        last = off + max(n - 1, 0) * ofs + (n_atoms - 1) * oas + 2 * ocs
+        if off < 0 or min(ofs, oas, ocs) < 1 or (n > 0 and last >= out.numel()):
+            raise DcvError(f"xtc_decode: output layout {tuple(out_strides)} with {n_atoms} atoms and {n} frames reaches element "
+                           f"{last} of a buffer of {out.numel()} (strides must be >= 1)")
+    status = torch.empty(n, dtype=torch.int32, device=data.device)
+    if n == 0:
+        return (result, status) if return_status else result   # an empty tensor has no data pointer to hand to the library
+    lib = _lib.load()
+    ws = _ws(lib.dcv_xtc_decode_workspace(n), data.device)
+    check(lib.dcv_xtc_decode(data.data_ptr(), data.numel(), frames.ctypes.data, n, n_atoms, float(scale), out.data_ptr() + 4 * off, ofs, oas, ocs,
+                             _ptr(status), _ptr(ws), ws.numel(), _stream()), "dcv_xtc_decode")
+    if return_status:
+        return result, status
+    bad = torch.nonzero(status)
+    if bad.numel():
+        f = int(bad[0])
+        code = int(status[f])
+        raise DcvError(f"xtc_decode: frame {f} of the {n} given did not decode: {_lib.XTC_STATUS.get(code, f'status {code}')} (corrupt or truncated file)")
+    return result
+
+
 def normalize(X: torch.Tensor, mean: torch.Tensor, rng: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(x - mean) / range in float32; ``out`` may be X itself (in place)."""
     _require_gpu(X, mean, rng, out)

@@ -19,7 +19,7 @@ def main(argv=None):
 
     p = argparse.ArgumentParser("Deep Cartograph: Project Trajectories (MI355X)",
                                 description="Projects trajectories onto saved collective-variable models from their coordinates.")
-    p.add_argument("-traj", dest="trajectories", required=True, nargs="+", help="trajectories to project (.dcd / .npy)")
+    p.add_argument("-traj", dest="trajectories", required=True, nargs="+", help="trajectories to project (.dcd / .npy; a GROMACS .xtc is imported first)")
     p.add_argument("-top", dest="topologies", required=True, nargs="+", help="topology (.pdb): one for all, or one per trajectory")
     p.add_argument("-model", dest="model_paths", required=True, nargs="+", help="model.zip files written by train_colvars")
     p.add_argument("-out", dest="output_folder", type=str, default=None, help="Path to the output folder.")

@@ -33,6 +33,28 @@ ANGSTROM_TO_NM = 0.1   # PLUMED's length unit
 DEFAULT_CHUNK_BYTES = 4 << 30   # default upper limit of a compute_features chunk (device bytes; the same again on the host)
 
 
+def import_trajectories(trajectories: Union[str, List[str]], output_folder: str, traj_format: Literal["dcd", "npy"] = "dcd", traj_stride: int = 1,
+                        memory_budget: Optional[int] = None) -> List[str]:
+    """GROMACS ``.xtc`` trajectories decoded on the device (hip.xtc_decode) into <out>/<trajectory stem>.dcd (or .npy, (n, A, 3)
+    float32), in Angstrom, every `traj_stride`-th frame; returns the paths in the order given.  Inputs that are not
+    ``.xtc`` pass through unchanged and a trajectory whose output exists is skipped.  Each file is indexed on the host
+    (trajectory.index_xtc), then the compressed bytes of a chunk of frames are uploaded, decoded straight into a device
+    image of DCD frame records, downloaded and appended; chunks take at most `memory_budget` bytes of device memory
+    (default: a quarter of what is free, at most 4 GiB).  The file is written under a temporary name and renamed at the
+    end.  The box, the steps and the times of the frames are not written (xtc.py).  The tools that take trajectories call
+    this themselves for ``.xtc`` inputs, into <their output folder>/xtc_import.  No CPU fallback."""
+    from . import xtc
+
+    return xtc.import_trajectories(trajectories, output_folder, traj_format, traj_stride, memory_budget)
+
+
+def _route_xtc(trajectories, output_folder: str, memory_budget: Optional[int] = None):
+    """``.xtc`` inputs imported into <output_folder>/xtc_import and replaced by the .dcd; everything else as it came."""
+    from . import xtc
+
+    return xtc.route(trajectories, output_folder, memory_budget)
+
+
 def compute_features(configuration: Dict, trajectory_data: Union[str, List[str]], topology_data: Union[str, List[str]],
                      reference_topology: Optional[str] = None, traj_stride: Optional[int] = None,
                      output_folder: str = "compute_features", memory_budget: Optional[int] = None) -> List[str]:
@@ -51,7 +73,7 @@ def compute_features(configuration: Dict, trajectory_data: Union[str, List[str]]
     from .colvars import write_colvars
 
     t0 = time.time()
-    trajectories = _as_list(trajectory_data) or []
+    trajectories = _route_xtc(_as_list(trajectory_data) or [], output_folder, memory_budget)
     topologies = _as_list(topology_data) or []
     if not trajectories:
         raise ValueError("compute_features: no trajectories given")
@@ -141,7 +163,7 @@ def analyze_geometry(configuration: Dict, trajectories: List[str], topologies: L
     from ._lib import DcvError
 
     t0 = time.time()
-    trajectories, topologies = _as_list(trajectories) or [], _as_list(topologies) or []
+    trajectories, topologies = _route_xtc(_as_list(trajectories) or [], output_folder, memory_budget), _as_list(topologies) or []
     ref_topologies = _as_list(ref_topologies)
     if len(topologies) == 1:
         topologies = topologies * len(trajectories)
@@ -199,7 +221,7 @@ def traj_augmentation(configuration: Dict, trajectories: Union[str, List[str]], 
     from . import augmentation
 
     t0 = time.time()
-    trajectories, topologies = _as_list(trajectories) or [], _as_list(topologies) or []
+    trajectories, topologies = _route_xtc(_as_list(trajectories) or [], output_folder, memory_budget), _as_list(topologies) or []
     if len(topologies) == 1:
         topologies = topologies * len(trajectories)
     if len(trajectories) != len(topologies):
@@ -247,7 +269,7 @@ def align_trajectories(trajectory_data: Union[str, List[str]], topology_data: Un
     from ._lib import DcvError
 
     t0 = time.time()
-    trajectories, topologies = _as_list(trajectory_data) or [], _as_list(topology_data) or []
+    trajectories, topologies = _route_xtc(_as_list(trajectory_data) or [], output_folder, memory_budget), _as_list(topology_data) or []
     if not trajectories:
         logger.warning("No trajectories provided. Nothing to align.")
         return [], []
@@ -392,10 +414,10 @@ def traj_projection(configuration: Dict, colvars_paths: List[str], topologies: L
                     model_paths: List[str] = None, model_traj_paths: Optional[List[List[str]]] = None,
                     output_folder: Optional[str] = "traj_projection", *, trajectories: Optional[List[str]] = None) -> Dict[str, List[str]]:
     """Project new colvars files onto saved models: <out>/<cv>/<traj>/projected_trajectory.csv.  With `trajectories`
-    (.dcd / .npy) instead of `colvars_paths` every model projects the coordinates themselves (project_trajectory): the
+    (.dcd / .npy; a GROMACS .xtc is imported first) instead of `colvars_paths` every model projects the coordinates themselves (project_trajectory): the
     features it needs are recomputed on the device from its own feature names and the topology (`topologies`: one for
     all trajectories, or one each), no colvars file and no features configuration involved."""
-    colvars_paths, trajectories = _as_list(colvars_paths) or [], _as_list(trajectories)
+    colvars_paths, trajectories = _as_list(colvars_paths) or [], _route_xtc(_as_list(trajectories), output_folder)
     from_coordinates = trajectories is not None
     if from_coordinates:
         import torch

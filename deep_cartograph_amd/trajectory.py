@@ -8,6 +8,8 @@ modules/md/md.py) is restated for the feature kinds its own test data pins:
 * ``read_topology``        PDB ATOM / HETATM / CONECT records up to the first ENDMDL;
 * ``select_atoms``         a documented subset of the MDAnalysis selection grammar (below);
 * ``open_trajectory``      little-endian CHARMM / NAMD ``.dcd`` (memory-mapped, never transposed) and ``.npy``;
+* ``index_xtc``            the frame index of a GROMACS ``.xtc`` (headers only; the payloads are decoded on the device by
+                           hip.xtc_decode, xtc.py has the import step);
 * ``write_dcd``, ``write_topology``  the way back out (traj_augmentation): a chunked DCD writer whose record images a
                            kernel fills in place, and a PDB of a selection with its CONECT records;
 * ``feature_definitions``  names and kernel records of the distance and virtual-dihedral groups, with the
@@ -23,17 +25,19 @@ the chain identifier where that field is blank, as in MDAnalysis.
 Out of scope (ValueError naming the option): ``coordinate_groups`` (need a per-frame optimal fit),
 ``distance_to_center_groups``, and the ``protein_backbone`` / ``real`` dihedral search modes.  Periodic boundaries
 are not applied: the reference's distances are NOPBC and its torsions follow a WHOLEMOLECULES step, so a trajectory
-whose molecule is split across the box must be made whole first.  XTC (compressed) is not read."""
+whose molecule is split across the box must be made whole first.  XTC is not mapped but imported (xtc.py)."""
 from __future__ import annotations
 
+import math
 import os
 import re
+import struct
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Set, Tuple
 
 import numpy as np
 
-from ._lib import FEAT_DISTANCE, FEAT_TORSION, FEAT_TORSION_SINCOS
+from ._lib import FEAT_DISTANCE, FEAT_TORSION, FEAT_TORSION_SINCOS, XTC_FRAME_DTYPE
 
 COVALENT_BOND_THRESHOLD = 2.0   # Angstrom: the reference's guess for a bond when the topology has no CONECT records
 
@@ -272,7 +276,10 @@ def _open_dcd(path: str, n_atoms: Optional[int]) -> Trajectory:
 
 def open_trajectory(path: str, n_atoms: Optional[int] = None) -> Trajectory:
     """Memory-map a trajectory: ``.dcd`` (little-endian CHARMM / NAMD / X-PLOR, with or without the unit-cell block) or
-    ``.npy`` holding (n, A, 3) float32 in Angstrom.  ``n_atoms`` (the topology's) is checked when given."""
+    ``.npy`` holding (n, A, 3) float32 in Angstrom.  ``n_atoms`` (the topology's) is checked when given.  A GROMACS
+    ``.xtc`` is refused: its coordinates are a variable-length bit stream, which cannot be mapped; ``index_xtc`` finds its
+    frames and tools.import_trajectories decodes them on the device into a ``.dcd`` or ``.npy`` this function maps (the
+    tool entries do that themselves for ``.xtc`` inputs)."""
     ext = os.path.splitext(path)[1].lower()
     if ext == ".dcd":
         return _open_dcd(path, n_atoms)
@@ -283,7 +290,126 @@ def open_trajectory(path: str, n_atoms: Optional[int] = None) -> Trajectory:
         if n_atoms is not None and arr.shape[1] != n_atoms:
             raise ValueError(f"{path}: {arr.shape[1]} atoms in the trajectory, {n_atoms} in the topology")
         return Trajectory(arr.reshape(-1), arr.shape[0], arr.shape[1], 0, 3 * arr.shape[1], 3, 1)
-    raise ValueError(f"{path}: unsupported trajectory format '{ext}' (supported: .dcd, .npy; XTC is compressed and out of scope)")
+    raise ValueError(f"{path}: unsupported trajectory format '{ext}' (supported: .dcd, .npy; XTC is a compressed bit stream that cannot be "
+                     "mapped in place: decode it first with tools.import_trajectories, as the tools do for their .xtc inputs)")
+
+
+# ------------------------------------------------------------------------------------------------ XTC frame index
+XTC_MAGIC, XTC_MAGIC_64 = 1995, 2023
+XTC_FIRSTIDX, XTC_LASTIDX = 9, 72
+_XTC_HEADER = struct.Struct(">iiif9fi")      # magic, natoms, step, time, box, natoms
+_XTC_COMPRESSED = struct.Struct(">f3i3iii")  # precision, minint, maxint, smallidx, nbytes
+
+
+@dataclass
+class XtcIndex:
+    """Where the frames of a GROMACS ``.xtc`` file lie and what their headers say (``index_xtc``).  Per frame (arrays of
+    ``n_frames``): ``offset`` -- the byte offset of the compressed payload, or of the float32 coordinates of a *raw* frame
+    (``raw``: a file of at most 9 atoms stores them uncompressed) --, ``nbytes`` of payload (0 for raw frames),
+    ``precision``, ``minint`` / ``maxint`` [n, 3], ``smallidx``, ``step``, ``time`` (ps) and ``box`` [n, 3, 3] (nm).  The box,
+    the steps and the times are kept here only: nothing downstream applies periodic boundaries."""
+    path: str
+    n_frames: int
+    n_atoms: int
+    raw: bool
+    offset: np.ndarray
+    nbytes: np.ndarray
+    precision: np.ndarray
+    minint: np.ndarray
+    maxint: np.ndarray
+    smallidx: np.ndarray
+    step: np.ndarray
+    time: np.ndarray
+    box: np.ndarray
+
+    def frame_bytes(self) -> np.ndarray:
+        """Bytes each frame's coordinates take in the file (payload padded to 4; 12 per atom for raw frames)."""
+        return np.full(self.n_frames, 12 * self.n_atoms, dtype=np.int64) if self.raw else (self.nbytes.astype(np.int64) + 3) // 4 * 4
+
+    def span(self, frames) -> Tuple[int, int, np.ndarray]:
+        """(first byte, end byte, descriptors) of the frames ``frames`` (ascending indices): the smallest slice of the file
+        that holds them -- it starts on the 4-byte grid, as every field of the file does -- and their XTC_FRAME_DTYPE
+        descriptors with offsets relative to that slice: what one chunk uploads and hands to hip.xtc_decode."""
+        frames = np.asarray(frames, dtype=np.int64).reshape(-1)
+        desc = np.zeros(frames.size, dtype=XTC_FRAME_DTYPE)
+        if frames.size == 0:
+            return 0, 0, desc
+        first = int(self.offset[frames[0]])
+        last = int(self.offset[frames[-1]] + self.frame_bytes()[frames[-1]])
+        desc["offset"] = self.offset[frames] - first
+        desc["nbytes"], desc["smallidx"], desc["precision"] = self.nbytes[frames], self.smallidx[frames], self.precision[frames]
+        desc["raw"] = int(self.raw)
+        desc["minint"], desc["maxint"] = self.minint[frames], self.maxint[frames]
+        return first, last, desc
+
+
+def index_xtc(path: str, n_atoms: Optional[int] = None) -> XtcIndex:
+    """One pass over the frame headers of a GROMACS ``.xtc`` file (memory-mapped; the payloads are not read).  Every
+    integer and float of the file is big-endian; a frame is
+    ``int32 magic (1995), natoms, step; float32 time, box[9]; int32 natoms``, then for at most 9 atoms ``3 natoms`` float32
+    (nm) and nothing else, otherwise ``float32 precision; int32 minint[3], maxint[3], smallidx, nbytes`` and ``nbytes`` of
+    payload padded with zeros to a multiple of 4 (include/dcv.h has the payload).  Raises ValueError naming the file and
+    the frame for: magic 2023 (the variant with 64-bit byte counts, not read), any other magic, an atom count that
+    changes between frames or differs from ``n_atoms``, a header or payload that runs past the end of the file,
+    ``smallidx`` outside [9, 72], ``maxint < minint`` and a precision that is not finite and positive."""
+    size = os.path.getsize(path)
+    data = np.memmap(path, dtype=np.uint8, mode="r") if size else np.zeros(0, dtype=np.uint8)
+    cols: Dict[str, list] = {k: [] for k in ("offset", "nbytes", "precision", "minint", "maxint", "smallidx", "step", "time", "box")}
+    pos, frame, natoms = 0, 0, None
+    while pos < size:
+        where = f"{path}: frame {frame}"
+        if pos + 56 > size:
+            raise ValueError(f"{where}: the header at byte {pos} runs past the end of the file ({size} bytes): truncated file")
+        magic, n, step, time, *box, n2 = _XTC_HEADER.unpack_from(data, pos)
+        if magic == XTC_MAGIC_64:
+            raise ValueError(f"{where}: magic 2023, the XTC variant with 64-bit byte counts, is not supported (only magic 1995)")
+        if magic != XTC_MAGIC:
+            raise ValueError(f"{where}: magic {magic} at byte {pos}, not an XTC frame (expected 1995)")
+        if n != n2 or n < 1:
+            raise ValueError(f"{where}: inconsistent atom counts in the header ({n} and {n2})")
+        if natoms is None:
+            if n_atoms is not None and n != n_atoms:
+                raise ValueError(f"{where}: {n} atoms in the trajectory, {n_atoms} in the topology")
+            natoms = n
+        elif n != natoms:
+            raise ValueError(f"{where}: {n} atoms, the frames before it have {natoms}: the atom count changes")
+        cols["step"].append(step)
+        cols["time"].append(time)
+        cols["box"].append(box)
+        pos += 56
+        if natoms <= 9:
+            length = 12 * natoms
+            fields = (0, 0.0, (0, 0, 0), (0, 0, 0), 0)
+        else:
+            if pos + 36 > size:
+                raise ValueError(f"{where}: the header at byte {pos - 56} runs past the end of the file ({size} bytes): truncated file")
+            precision, *ints = _XTC_COMPRESSED.unpack_from(data, pos)
+            minint, maxint, smallidx, nbytes = ints[0:3], ints[3:6], ints[6], ints[7]
+            if not (math.isfinite(precision) and precision > 0):
+                raise ValueError(f"{where}: precision {precision} is not finite and positive")
+            if any(hi < lo for lo, hi in zip(minint, maxint)):
+                raise ValueError(f"{where}: maxint {maxint} below minint {minint}")
+            if not XTC_FIRSTIDX <= smallidx <= XTC_LASTIDX:
+                raise ValueError(f"{where}: smallidx {smallidx} outside [{XTC_FIRSTIDX}, {XTC_LASTIDX}]")
+            if nbytes < 0:
+                raise ValueError(f"{where}: a payload of {nbytes} bytes")
+            pos += 36
+            length = (nbytes + 3) // 4 * 4
+            fields = (nbytes, precision, minint, maxint, smallidx)
+        if pos + length > size:
+            raise ValueError(f"{where}: {length} bytes of coordinates at byte {pos} run past the end of the file ({size} bytes): truncated file")
+        cols["offset"].append(pos)
+        for key, v in zip(("nbytes", "precision", "minint", "maxint", "smallidx"), fields):
+            cols[key].append(v)
+        pos += length
+        frame += 1
+    if frame == 0:
+        raise ValueError(f"{path}: frame 0: the file is empty")
+    return XtcIndex(path, frame, natoms, natoms <= 9, np.asarray(cols["offset"], dtype=np.int64), np.asarray(cols["nbytes"], dtype=np.int32),
+                    np.asarray(cols["precision"], dtype=np.float32), np.asarray(cols["minint"], dtype=np.int32).reshape(-1, 3),
+                    np.asarray(cols["maxint"], dtype=np.int32).reshape(-1, 3), np.asarray(cols["smallidx"], dtype=np.int32),
+                    np.asarray(cols["step"], dtype=np.int64), np.asarray(cols["time"], dtype=np.float32),
+                    np.asarray(cols["box"], dtype=np.float32).reshape(-1, 3, 3))
 
 
 # ------------------------------------------------------------------------------------------------ writers

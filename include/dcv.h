@@ -260,6 +260,84 @@ int dcv_transform_frames(const float* xyz_d, int64_t n_frames, int64_t frame_str
                          int32_t n_atoms, const double* transform_d, int64_t ldt,
                          float* out_d, int64_t out_frame_stride, int64_t out_atom_stride, int64_t out_comp_stride, void* stream);
 
+/* ---- GROMACS XTC frames decoded on the device (import_trajectories) ---------------------------------------------------
+ * bytes_d holds the bytes of an XTC file, or a contiguous slice of them that starts on a multiple of 4 bytes of the file,
+ * 4-byte aligned; frames_h, on the host, one descriptor per frame to decode (trajectory.index_xtc makes them; choosing
+ * descriptors is how a frame stride or a sub-range is applied).  Coordinate c of atom a of decoded frame f goes to
+ * out_d[f*out_frame_stride + a*out_atom_stride + c*out_comp_stride] (strides in ELEMENTS, all >= 1) as in
+ * dcv_interpolate and dcv_transform_frames: a dense (n, A, 3) array or the planes of a DCD record image.  Only those
+ * elements are written.  status_d[f] = 0: the frame decoded; anything else: its stream was inconsistent
+ * (DCV_XTC_*) and the coordinates of the frame from the first inconsistency on are left unwritten.
+ *
+ * The file (magic 1995; every integer and float big-endian).  A frame is
+ *     int32 magic (1995)  int32 natoms  int32 step  float32 time  float32 box[9]  int32 natoms
+ *     natoms <= 9 :  3*natoms float32 (nm), nothing else                                        (descriptor: raw != 0)
+ *     natoms >  9 :  float32 precision  int32 minint[3]  int32 maxint[3]  int32 smallidx  int32 nbytes
+ *                    nbytes of payload, padded with zeros to a multiple of 4
+ * and `offset` of a descriptor is the byte offset, inside bytes_d, of the payload (of the floats for a raw frame).
+ * The payload is a bit stream, most significant bit first.  With FIRSTIDX = 9 and
+ *   magic[] = 0 x9, 8,10,12,16,20,25,32,40,50,64,80,101,128,161,203,256,322,406,512,645,812,1024,1290,1625,2048,2580,
+ *     3250,4096,5060,6501,8192,10321,13003,16384,20642,26007,32768,41285,52015,65536,82570,104031,131072,165140,208063,
+ *     262144,330280,416127,524287,660561,832255,1048576,1321122,1664510,2097152,2642245,3329021,4194304,5284491,6658042,
+ *     8388607,10568983,13316085,16777216                                                   (73 entries, indices 0..72)
+ *   sizeint[k] = maxint[k] - minint[k] + 1
+ *   if any sizeint > 0xffffff: bitsizeint[k] = smallest b with 2^b > sizeint[k], at most 32;  bitsize = 0
+ *   else: bitsize = bit length of the product sizeint[0]*sizeint[1]*sizeint[2]                        (up to 72 bits)
+ *   smaller = magic[max(FIRSTIDX, smallidx-1)]/2;  smallnum = magic[smallidx]/2;  sizesmall = magic[smallidx];  run = 0;  i = 0
+ *   while i < natoms:
+ *       this = bitsize == 0 ? three fields of bitsizeint[k] bits : unpack3(bitsize, sizeint);   i++;   this += minint;   prev = this
+ *       flag = 1 bit;  is_smaller = 0
+ *       if flag: run = 5 bits;  is_smaller = run % 3;  run -= is_smaller;  is_smaller -= 1    (run otherwise KEEPS its last value)
+ *       if run > 0:
+ *           for k = 0, 3, ..., < run:
+ *               this = unpack3(smallidx, {sizesmall x3});  i++;  this += prev - smallnum
+ *               if k == 0: swap(this, prev); emit(prev)       (the water swap: the second atom of a run is written first)
+ *               else:      prev = this
+ *               emit(this)
+ *       else: emit(this)
+ *       smallidx += is_smaller
+ *       if is_smaller < 0: smallnum = smaller;  smaller = smallidx > FIRSTIDX ? magic[smallidx-1]/2 : 0
+ *       if is_smaller > 0: smaller = smallnum;  smallnum = magic[smallidx]/2
+ *       sizesmall = magic[smallidx]
+ *   unpack3(nbits, sizes): read nbits/8 whole bytes, LEAST significant byte first, then the nbits%8 remaining bits as the
+ *       top byte, into one unsigned integer v;  n2 = v % sizes[2]; v /= sizes[2];  n1 = v % sizes[1];  n0 = v / sizes[1]
+ *       (v is held in three 32-bit limbs and divided limb by limb; n0 is the low 32 bits of the last quotient).
+ * emit(i) writes x = (float)i * inv with inv = 1.0f / precision, then x * scale (scale = 10 for Angstrom): two float32
+ * multiplications, never contracted -- what xdrfile followed by a unit conversion in float32 produce.  A raw frame
+ * writes value * scale.  Integer sums wrap in 32 bits.
+ *
+ * A lane owns a frame (inside a frame the stream is strictly sequential); the bit reader keeps a 64-bit window refilled
+ * by 4-byte loads with a byte swap; every iteration decodes one atom in every lane, so the lanes of a wave stay within one
+ * atom of each other, a lane stages its last nine atoms in LDS and the wave stores blocks of eight atoms of its 64 frames
+ * in contiguous pieces (96 bytes for dense rows, 32 for planes).  No stream, however corrupt, reads or writes out of range: the reader returns zero bits behind nbytes and marks the frame (DCV_XTC_SHORT); the atom
+ * counter is checked before every emit and a run that would pass natoms marks the frame and stops (DCV_XTC_RUN); a
+ * smallidx that leaves [9, 72] marks the frame and stops (DCV_XTC_SMALLIDX); maxint < minint, or a precision that is not
+ * finite and positive, mark it before anything is read (DCV_XTC_HEADER).
+ * Validated on the host before anything is launched (DCV_EINVAL): NULL pointers; n_atoms < 1; n_frames < 0; bytes_d or
+ * out_d off the 4-byte grid; a descriptor whose offset is negative or no multiple of 4, whose nbytes is negative, or whose
+ * bytes (nbytes rounded up to 4; 12*n_atoms for a raw frame) end behind n_bytes; a raw flag that disagrees with
+ * n_atoms <= 9; output strides below 1; an output, status or workspace range that overlaps the input bytes or each other's.
+ * The descriptors are copied into the workspace; one that is too small is DCV_ENOMEM, nothing launched.  n_frames = 0 is
+ * DCV_OK.  Algorithmic traffic per frame: its payload read once, 12 bytes per atom written. */
+#define DCV_XTC_OK 0
+#define DCV_XTC_SHORT 1     /* the stream needed bits behind nbytes */
+#define DCV_XTC_RUN 2       /* a run of small atoms would pass natoms */
+#define DCV_XTC_SMALLIDX 3  /* smallidx left [9, 72] */
+#define DCV_XTC_HEADER 4    /* maxint < minint or a precision that is not finite and positive */
+typedef struct dcv_xtc_frame {
+    int64_t offset;      /* bytes from bytes_d to the payload (raw: to the floats); a multiple of 4 */
+    int32_t nbytes;      /* payload bytes (raw: ignored) */
+    int32_t smallidx;
+    float precision;
+    int32_t raw;         /* != 0: 3*n_atoms big-endian float32, no payload (n_atoms <= 9) */
+    int32_t minint[3];
+    int32_t maxint[3];
+} dcv_xtc_frame;
+size_t dcv_xtc_decode_workspace(int64_t n_frames);
+int dcv_xtc_decode(const void* bytes_d, int64_t n_bytes, const dcv_xtc_frame* frames_h, int64_t n_frames, int32_t n_atoms,
+                   float scale, float* out_d, int64_t out_frame_stride, int64_t out_atom_stride, int64_t out_comp_stride,
+                   int32_t* status_d, void* ws_d, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- normalisation (a3)
  * Replaces LinearCalculator.normalize_data, cv_calculator.py:833-835
  * (data.sub_(mean).div_(range) in float32).  Y may alias X (in place, as the reference). */
