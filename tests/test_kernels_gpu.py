@@ -6,6 +6,7 @@ import torch
 
 from oracle import cluster as oc
 from oracle import linear as ol
+from tests import kmeans_oracle as ko
 
 pytestmark = pytest.mark.gpu
 
@@ -409,15 +410,21 @@ def test_kmeanspp_passes_even_and_odd_d(d):
     np.testing.assert_allclose(pot.cpu().numpy(), [ref.sum()], rtol=1e-12)
 
 
-_REG_STREAM_NEAREST = [(4, 6, 70_001), (2, 3, 5_000), (4, 17, 63)]
-_REG_STREAM_LLOYD = (4, 6, 70_001)
+_REG_STREAM_NEAREST = [(4, 6, 70_001), (2, 3, 5_000), (4, 17, 63)] + [(d, k, ko.NEAREST_STEADY_N) for d, k in ko.OTHER_STREAM_NEAREST_DK]
+_REG_STREAM_LLOYD = [(4, 6, 70_001)] + [(d, k, ko.LLOYD_STEADY_N) for d, k in ko.OTHER_STREAM_LLOYD_DK]
+_REG_STREAM_CHILD_SECONDS = 5   # measured: see test_register_stream_matches_ring_and_numpy
 
 
 def _reg_stream_inputs():
     """The point sets of the register-stream test, with duplicated rows (exact ties) and a centroid that IS a point, as
-    test_nearest_rows_one_pass_narrow_d builds them; the same in the parent and the child process."""
+    test_nearest_rows_one_pass_narrow_d builds them; the same in the parent and the child process.  The steady-state sizes
+    (tests/kmeans_oracle.py: more than 1024 points per workgroup, so that the register stream alternates its batches) come
+    from the oracle module's recipes and seeds.  Lloyd cases are (P, C, mean); the first one runs without an offset."""
     cases = []
     for d, k, n in _REG_STREAM_NEAREST:
+        if n == ko.NEAREST_STEADY_N:
+            cases.append(ko.nearest_case(d, k, n, ko.nearest_seed(d, k, n))[:2])
+            continue
         rng = np.random.Generator(np.random.PCG64(4000 + 10 * d + k))
         P = np.round(rng.uniform(-1, 1, (n, d)), 4)
         m = min(50, n // 4)
@@ -425,40 +432,52 @@ def _reg_stream_inputs():
         C = np.round(rng.uniform(-1, 1, (k, d)), 3)
         C[0] = P[n // 2 + m // 5]
         cases.append((P, C))
-    d, k, n = _REG_STREAM_LLOYD
-    rng = np.random.Generator(np.random.PCG64(4500))
-    cent = rng.uniform(-1, 1, (k, d))
-    P = np.round(cent[rng.integers(0, k, n)] + 0.15 * rng.standard_normal((n, d)), 4)
-    P[n // 2:n // 2 + 50] = P[n // 8:n // 8 + 50]
-    C = P[rng.choice(n, k, replace=False)] + 1e-3
-    return cases, (P, C)
+    lloyd = []
+    for d, k, n in _REG_STREAM_LLOYD:
+        if n == ko.LLOYD_STEADY_N:
+            lloyd.append(ko.lloyd_case(d, k, n, ko.lloyd_seed(d, k, n)))
+            continue
+        rng = np.random.Generator(np.random.PCG64(4500))
+        cent = rng.uniform(-1, 1, (k, d))
+        P = np.round(cent[rng.integers(0, k, n)] + 0.15 * rng.standard_normal((n, d)), 4)
+        P[n // 2:n // 2 + 50] = P[n // 8:n // 8 + 50]
+        C = P[rng.choice(n, k, replace=False)] + 1e-3
+        lloyd.append((P, C, None))
+    return cases, lloyd
 
 
-def _reg_stream_run():
-    """rows / distances of every nearest-rows case and labels / acc of the Lloyd case, through whichever stream the process's
-    DCV_KM_RING selects."""
+def _reg_stream_run(inputs=None):
+    """rows / distances of every nearest-rows case and labels / acc of every Lloyd case, through whichever stream the
+    process's DCV_KM_RING selects."""
     from deep_cartograph_amd import hip
 
-    cases, (P, C) = _reg_stream_inputs()
+    cases, lloyd = inputs or _reg_stream_inputs()
     out = {}
     for q, (Pn, Cn) in enumerate(cases):
         dist, rows = hip.nearest_rows(dev(Pn), dev(Cn))
         out[f"dist{q}"], out[f"rows{q}"] = dist.cpu().numpy(), rows.cpu().numpy()
-    labels = torch.full((P.shape[0],), -1, dtype=torch.int32, device="cuda")
-    acc, _ = hip.kmeans_step(dev(P), dev(C), labels)
-    out["labels"], out["acc"] = labels.cpu().numpy(), acc.cpu().numpy()
+    for q, (P, C, mean) in enumerate(lloyd):
+        labels = torch.full((P.shape[0],), -1, dtype=torch.int32, device="cuda")
+        if mean is None:
+            acc, _ = hip.kmeans_step(dev(P), dev(C), labels)
+        else:
+            acc, _ = hip.kmeans_step(dev(P), dev(C - mean), labels, offset=dev(mean))
+        sfx = "" if q == 0 else str(q)
+        out["labels" + sfx], out["acc" + sfx] = labels.cpu().numpy(), acc.cpu().numpy()
     return out
 
 
 _REG_STREAM_SCRIPT = """
 import importlib.util
 import sys
+import time
 sys.path.insert(0, sys.argv[1])
 import numpy as np
 spec = importlib.util.spec_from_file_location("kernels_gpu_cases", sys.argv[3])
 tk = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(tk)
 np.savez(sys.argv[2], **tk._reg_stream_run())
+print("child seconds %.1f" % (time.time() - float(sys.argv[4])))
 """
 
 
@@ -466,25 +485,45 @@ def test_register_stream_matches_ring_and_numpy(tmp_path):
     """DCV_KM_RING=0 in a fresh process selects the register stream (kmeans.hip: reg_stream) where this process takes the
     LDS-DMA ring: nearest_rows (four points per thread and batch) at d = 4 (the lane-pair path; 17 centroids in three chunks
     on fewer points than one 64-point chunk) and d = 2, and the Lloyd pass at d = 4 (two points, the labels travel along).
-    Rows and distances bit-equal to np.linalg.norm / argmin and to the ring's, labels equal to the ring's."""
+    Rows and distances bit-equal to np.linalg.norm / argmin and to the ring's, labels equal to the ring's.
+
+    The steady-state sizes besides: nearest_rows at n = 4 300 003 (five batches per thread: ba, bb, ba, bb, ba, the planted
+    duplicates in the last) and the plain Lloyd pass at n = 2 400 011 (five batches of two points).  Labels, counts, sums
+    and inertia of BOTH processes against tests/kmeans_oracle.py (sums within the summation-tree bound L 2^-53 S derived
+    in tests/test_kmeans_streams_gpu.py).  One child, started once; this process computes the references while it runs.
+    The child took 5.0 s from its launch to the end of its work, measured on an MI355X machine (it prints the figure);
+    its limit is four times that."""
     import os
     import subprocess
     import sys
+    import time
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     assert os.environ.get("DCV_KM_RING", "1") != "0"
-    ring = _reg_stream_run()
+    inputs = _reg_stream_inputs()
+    cases, lloyd = inputs
+    ring = _reg_stream_run(inputs)
     script = tmp_path / "reg_stream.py"
     script.write_text(_REG_STREAM_SCRIPT)
     env = dict(os.environ)
     env["DCV_KM_RING"] = "0"
     out = tmp_path / "reg.npz"
-    res = subprocess.run([sys.executable, str(script), root, str(out), os.path.abspath(__file__)], env=env, cwd=root, capture_output=True, text=True, timeout=120)
-    assert res.returncode == 0, res.stderr[-2000:]
+    started = time.time()
+    child = subprocess.Popen([sys.executable, str(script), root, str(out), os.path.abspath(__file__), repr(started)], env=env, cwd=root,
+                             stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    try:
+        near_refs = [oc.find_centroid_rows(P, C) for P, C in cases]
+        lloyd_refs = [ko.lloyd_reference(P, C, np.zeros(P.shape[1]) if mean is None else mean) for P, C, mean in lloyd]
+        stdout, stderr = child.communicate(timeout=max(1.0, 4 * _REG_STREAM_CHILD_SECONDS - (time.time() - started)))
+    except BaseException:
+        child.kill()
+        child.communicate()
+        raise
+    assert child.returncode == 0, stderr[-2000:]
+    print(stdout.strip())
     reg = np.load(out)
-    cases, _ = _reg_stream_inputs()
     for q, (P, C) in enumerate(cases):
-        ref = oc.find_centroid_rows(P, C)
+        ref = near_refs[q]
         ref_dist = np.linalg.norm(P[ref] - C, axis=1)
         for got in (reg, ring):
             np.testing.assert_array_equal(got[f"rows{q}"], ref)
@@ -492,6 +531,23 @@ def test_register_stream_matches_ring_and_numpy(tmp_path):
         assert reg[f"dist{q}"].tobytes() == ring[f"dist{q}"].tobytes()
     np.testing.assert_array_equal(reg["labels"], ring["labels"])
     assert reg["labels"].min() >= 0
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    for q, (P, C, mean) in enumerate(lloyd):
+        n, d = P.shape
+        k = C.shape[0]
+        ref = lloyd_refs[q]
+        assert ref.margin > 1e-9   # every label decided whatever the order of a dot product
+        L = ko.lloyd_chain(n, cus)
+        sfx = "" if q == 0 else str(q)
+        for got in (reg, ring):
+            np.testing.assert_array_equal(got["labels" + sfx], ref.labels)
+            acc = got["acc" + sfx]
+            np.testing.assert_array_equal(acc[k * d:k * d + k], ref.counts)
+            assert acc[k * d + k + 1] == n
+            ok, err = ko.within_sum_bound(acc[:k * d].reshape(k, d), ref.sums, ref.abs_sums, L)
+            assert ok, (L, err)
+            ok, err = ko.within_sum_bound(acc[k * d + k], ref.inertia, ref.inertia, L)
+            assert ok, (L, err)
 
 
 @pytest.mark.parametrize("d,bins,blocks", [(1, 150, 1), (2, 100, 1), (2, 64, 4), (1, 5000, 1)])
