@@ -24,6 +24,7 @@ XTC_FRAME_DTYPE = np.dtype([("offset", "<i8"), ("nbytes", "<i4"), ("smallidx", "
 assert XTC_FRAME_DTYPE.itemsize == 48
 XTC_STATUS = {1: "the stream needs bits behind its nbytes", 2: "a run of small atoms would pass the atom count", 3: "smallidx left [9, 72]",
               4: "maxint below minint, or a precision that is not finite and positive"}   # DCV_XTC_*
+XTC_ENC_STATUS = {1: "a coordinate is NaN or infinite", 2: "a coordinate does not fit a 32-bit integer at this precision"}   # DCV_XTC_ENC_*
 
 
 class MlpDesc(C.Structure):
@@ -92,6 +93,11 @@ SIGNATURES = {
     "dcv_transform_frames": (C.c_int, [_P, _I64, _I64, _I64, _I64, _I32, _P, _I64, _P, _I64, _I64, _I64, _P]),
     "dcv_xtc_decode_workspace": (_SZ, [_I64]),
     "dcv_xtc_decode": (C.c_int, [_P, _I64, _P, _I64, _I32, C.c_float, _P, _I64, _I64, _I64, _P, _P, _SZ, _P]),
+    "dcv_xtc_encode_slot_bytes": (_SZ, [_I32]),
+    "dcv_xtc_encode_workspace": (_SZ, [_I64]),
+    "dcv_xtc_encode": (C.c_int, [_P, _I64, _I64, _I64, _I64, _I32, _P, _I64, C.c_float, C.c_float, _P, _SZ, _P, _P, _P, _SZ, _P]),
+    "dcv_xtc_pack_workspace": (_SZ, [_I64]),
+    "dcv_xtc_pack": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _P, _I64, _I32, _P, _SZ, _P, _SZ, _P]),
     "dcv_normalize": (C.c_int, [_P, _P, _I64, _I32, _I64, _I64, _P, _P, _P]),
     "dcv_lagged_cov_workspace": (_SZ, [_I64, _I32, _I32]),
     "dcv_lagged_cov": (C.c_int, [_P, _I64, _I32, _I64, _I32, _P, _P, _P, _SZ, _P]),

@@ -22,21 +22,9 @@
 #include <cmath>
 
 #include "common.h"
+#include "xtc_decode_frame.h"
 
 namespace dcv {
-
-constexpr int kXtcThreads = 64;
-constexpr int kXtcFirstIdx = 9, kXtcLastIdx = 72;
-
-// magic[i], 0 <= i <= 72; a function so that the host build of the decoder (a stand-alone check) reads the same table
-__host__ __device__ __forceinline__ int32_t xtc_magic(int i) {
-    constexpr int32_t kMagic[kXtcLastIdx + 1] = {
-    0, 0, 0, 0, 0, 0, 0, 0, 0, 8, 10, 12, 16, 20, 25, 32, 40, 50, 64, 80, 101, 128, 161, 203, 256, 322, 406, 512, 645, 812, 1024, 1290, 1625,
-    2048, 2580, 3250, 4096, 5060, 6501, 8192, 10321, 13003, 16384, 20642, 26007, 32768, 41285, 52015, 65536, 82570, 104031, 131072, 165140,
-    208063, 262144, 330280, 416127, 524287, 660561, 832255, 1048576, 1321122, 1664510, 2097152, 2642245, 3329021, 4194304, 5284491, 6658042,
-    8388607, 10568983, 13316085, 16777216};
-    return kMagic[i];
-}
 
 struct XtcArgs {
     const uint8_t* bytes;
@@ -48,219 +36,6 @@ struct XtcArgs {
     int32_t n_atoms;
     float scale;
 };
-
-// the payload of one frame as a stream of bits, most significant first
-struct XtcBits {
-    const uint32_t* words;   // 4-byte aligned
-    uint32_t n_words;        // nbytes rounded up to whole words: no word at or behind this index is ever loaded
-    uint32_t nbytes;
-    uint32_t next;           // the next word to load
-    uint64_t win;            // the `have` bits not yet handed out, at the top
-    int have;
-    uint64_t taken, total;   // bits handed out, bits the payload holds
-
-    __host__ __device__ __forceinline__ void open(const uint8_t* p, uint32_t nbytes_) {
-        words = reinterpret_cast<const uint32_t*>(p);
-        nbytes = nbytes_;
-        n_words = (nbytes_ + 3u) >> 2;
-        next = 0; win = 0; have = 0; taken = 0;
-        total = (uint64_t)nbytes_ * 8u;
-    }
-    // n in [0, 32]; behind the payload the bits are zero
-    __host__ __device__ __forceinline__ uint32_t get(int n) {
-        if (have < n) {
-            uint32_t w = 0;
-            if (next < n_words) {
-                w = __builtin_bswap32(words[next]);
-                const uint32_t left = nbytes - 4u * next;   // payload bytes in this word, >= 1
-                if (left < 4u) w &= ~(0xffffffffu >> (8u * left));
-            }
-            ++next;
-            win |= (uint64_t)w << (32 - have);
-            have += 32;
-        }
-        taken += (uint64_t)n;
-        if (n == 0) return 0;
-        const uint32_t v = (uint32_t)(win >> (64 - n));
-        win <<= n;
-        have -= n;
-        return v;
-    }
-    __host__ __device__ __forceinline__ bool overrun() const { return taken > total; }
-};
-
-// v / d in place and v % d, v in three 32-bit limbs (least significant first), 1 <= d
-__host__ __device__ __forceinline__ uint32_t xtc_divmod(uint32_t (&v)[3], uint32_t d) {
-    uint64_t rem = 0;
-#pragma unroll
-    for (int j = 2; j >= 0; --j) {
-        const uint64_t cur = (rem << 32) | v[j];
-        const uint64_t q = cur / d;
-        rem = cur - q * d;
-        v[j] = (uint32_t)q;
-    }
-    return (uint32_t)rem;
-}
-
-// three integers packed into nbits <= 72 bits (dcv.h: unpack3)
-__host__ __device__ __forceinline__ void xtc_unpack3(XtcBits& in, int nbits, uint32_t s1, uint32_t s2, uint32_t (&n)[3]) {
-    uint32_t v[3] = {0, 0, 0};
-    const int full = nbits >> 3, rest = nbits & 7;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const int b = full - 4 * j;   // whole bytes of this limb and the ones above it
-        if (b >= 4) v[j] = __builtin_bswap32(in.get(32));
-        else if (b > 0) v[j] = __builtin_bswap32(in.get(8 * b) << (32 - 8 * b));
-    }
-    if (rest) v[full >> 2] |= in.get(rest) << (8 * (full & 3));
-    n[2] = xtc_divmod(v, s2);
-    n[1] = xtc_divmod(v, s1);
-    n[0] = v[0];
-}
-
-__host__ __device__ __forceinline__ int xtc_bits_of(uint32_t size) {   // smallest b with 2^b > size, at most 32
-    return size == 0 ? 0 : 32 - __builtin_clz(size);
-}
-
-// bit length of a * b * c, each below 2^24
-__host__ __device__ __forceinline__ int xtc_product_bits(uint32_t a, uint32_t b, uint32_t c) {
-    const uint64_t ab = (uint64_t)a * b;                   // < 2^48
-    const uint64_t lo = (ab & 0xffffffffu) * c;            // < 2^56
-    const uint64_t hi = (ab >> 32) * c + (lo >> 32);       // < 2^40 + 2^24
-    return hi ? 96 - __builtin_clzll(hi) : 32 - __builtin_clz((uint32_t)lo | 1u);   // a, b, c >= 1: the product is not 0
-}
-
-// One compressed frame: descriptor `d`, payload inside `bytes`; returns the frame's status.  `live` = false (a lane behind
-// the last frame) decodes nothing.  Every coordinate goes through emit(atom, x, y, z), atom < natoms checked here; after
-// every iteration -- all frames of a launch have the same natoms, so the trip count is the same in every lane, and a
-// frame that is marked idles through the rest -- step(decoded, emitted) is called with the numbers of atoms read and
-// written so far: decoded is the same in every live lane, emitted is decoded or one less (the atom in front of a run
-// waits for the run's first small atom).  Host and device: the kernel runs it one lane a frame, a stand-alone host
-// program can run the same code on host memory.
-template <class Emit, class Step>
-__host__ __device__ __forceinline__ int xtc_decode_frame(const uint8_t* bytes, const dcv_xtc_frame& d, int32_t natoms, float scale, bool live,
-                                                         Emit&& emit_atom, Step&& step) {
-#pragma clang fp contract(off)
-    int status = DCV_XTC_OK;
-    int smallidx = d.smallidx;
-    uint32_t sizeint[3] = {1, 1, 1};
-    if (live) {
-        bool header_ok = std::isfinite(d.precision) && d.precision > 0.0f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            header_ok = header_ok && d.maxint[k] >= d.minint[k];
-            sizeint[k] = (uint32_t)d.maxint[k] - (uint32_t)d.minint[k] + 1u;
-            header_ok = header_ok && sizeint[k] != 0;   // the whole int32 range: 2^32 sizes, which the format cannot hold
-        }
-        if (!header_ok) status = DCV_XTC_HEADER;
-        else if (smallidx < kXtcFirstIdx || smallidx > kXtcLastIdx) status = DCV_XTC_SMALLIDX;
-    }
-    bool active = live && status == DCV_XTC_OK;
-    if (!active) {   // nothing of a marked frame's descriptor is used
-        smallidx = kXtcFirstIdx;
-        sizeint[0] = sizeint[1] = sizeint[2] = 1;
-    }
-    int bitsize, bitsizeint[3] = {0, 0, 0};
-    if ((sizeint[0] | sizeint[1] | sizeint[2]) > 0xffffffu) {
-        bitsize = 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) bitsizeint[k] = xtc_bits_of(sizeint[k]);
-    } else {
-        bitsize = xtc_product_bits(sizeint[0], sizeint[1], sizeint[2]);
-    }
-    const float inv = 1.0f / d.precision;
-
-    XtcBits in;
-    in.open(bytes + (active ? d.offset : 0), active ? (uint32_t)d.nbytes : 0u);
-    int32_t smaller = xtc_magic(smallidx - 1 > kXtcFirstIdx ? smallidx - 1 : kXtcFirstIdx) / 2;
-    int32_t smallnum = xtc_magic(smallidx) / 2;
-    uint32_t sizesmall = (uint32_t)xtc_magic(smallidx);
-
-    int32_t emitted = 0;                     // atoms written
-    int run = 0, left = 0, is_smaller = 0;   // small atoms of the current run still to read
-    bool first = false;                      // the next small atom is the first of its run
-    uint32_t prev[3] = {0, 0, 0};            // the atom decoded last (32-bit wrapping sums)
-
-    auto emit = [&](const uint32_t (&v)[3]) {
-        if (emitted < natoms) {
-            float x[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) x[c] = ((float)(int32_t)v[c] * inv) * scale;
-            emit_atom(emitted, x[0], x[1], x[2]);
-        }
-        ++emitted;
-    };
-
-    for (int32_t decoded = 0; decoded < natoms;) {
-        if (active) {
-            const bool small = left > 0;
-            uint32_t n[3];
-            if (!small && bitsize == 0) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) n[k] = in.get(bitsizeint[k]);
-            } else {
-                xtc_unpack3(in, small ? smallidx : bitsize, small ? sizesmall : sizeint[1], small ? sizesmall : sizeint[2], n);
-            }
-            bool update = false;   // the end of an atom group: smallidx moves
-            if (!small) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) prev[k] = n[k] + (uint32_t)d.minint[k];
-                is_smaller = 0;
-                if (in.get(1)) {
-                    run = (int)in.get(5);
-                    is_smaller = run % 3;
-                    run -= is_smaller;
-                    is_smaller -= 1;
-                }
-                if (run > 0) {
-                    left = run / 3;
-                    first = true;
-                    if (decoded + 1 + left > natoms) {   // the run would pass natoms: nothing of it is read
-                        status = DCV_XTC_RUN;
-                        active = false;
-                    }
-                } else {
-                    emit(prev);
-                    update = true;
-                }
-            } else {
-                uint32_t cur[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) cur[k] = n[k] + prev[k] - (uint32_t)smallnum;
-                emit(cur);
-                if (first) emit(prev);   // the water swap: the atom in front of the run is written behind its first small atom
-                first = false;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) prev[k] = cur[k];
-                update = --left == 0;
-            }
-            if (active && in.overrun()) {
-                status = DCV_XTC_SHORT;
-                active = false;
-            }
-            if (active && update) {
-                smallidx += is_smaller;
-                if (smallidx < kXtcFirstIdx || smallidx > kXtcLastIdx) {
-                    if (decoded + 1 < natoms) status = DCV_XTC_SMALLIDX;   // behind the last atom the value is never used
-                    active = false;
-                    smallidx = kXtcFirstIdx;
-                } else {
-                    if (is_smaller < 0) {
-                        smallnum = smaller;
-                        smaller = smallidx > kXtcFirstIdx ? xtc_magic(smallidx - 1) / 2 : 0;
-                    } else if (is_smaller > 0) {
-                        smaller = smallnum;
-                        smallnum = xtc_magic(smallidx) / 2;
-                    }
-                    sizesmall = (uint32_t)xtc_magic(smallidx);
-                }
-            }
-        }
-        ++decoded;
-        step(decoded, emitted);
-    }
-    return status;
-}
 
 // The staging of a wave (64 frames) in LDS: a lane keeps its last kXtcRing atoms, word ((slot*3 + c)*65 + lane) -- lanes on
 // consecutive banks when they write, and the 24 words of a frame's block on different banks when the wave reads them
@@ -328,17 +103,6 @@ __global__ __launch_bounds__(kXtcThreads) void xtc_decode_kernel(const XtcArgs a
     for (; flushed * kXtcBlock < a.n_atoms; ++flushed) xtc_flush(a, ring, cnt, f0, flushed, comp_fast);
     if (live) a.status[f] = status;
 }
-
-// last element an output layout reaches, false when that does not fit 60 bits
-static bool xtc_extent(int64_t n_frames, int64_t n_atoms, int64_t fs, int64_t as, int64_t cs, int64_t& last) {
-    int64_t x, y, z;
-    if (__builtin_mul_overflow(n_frames - 1, fs, &x) || __builtin_mul_overflow(n_atoms - 1, as, &y) || __builtin_mul_overflow((int64_t)2, cs, &z))
-        return false;
-    if (__builtin_add_overflow(x, y, &last) || __builtin_add_overflow(last, z, &last)) return false;
-    return last < (int64_t)1 << 60;
-}
-
-static bool xtc_disjoint(uintptr_t a_lo, uintptr_t a_hi, uintptr_t b_lo, uintptr_t b_hi) { return a_hi <= b_lo || b_hi <= a_lo; }
 
 }  // namespace dcv
 

@@ -46,7 +46,10 @@ def deep_cartograph(configuration: Dict, colvars_paths: List[str], sup_colvars_p
     the features first unless `features_list` is given.  `restart` reuses the output folder and skips what exists.
     With `seed_trajectory_data` (and `seed_topology_data`: one PDB for all, or one per seed) the `traj_augmentation`
     section runs after analyze_geometry, into <out>/traj_augmentation, and its trajectories and topologies are appended
-    to the ones `compute_features` reads (reference deep_carto.py:202-215); `trajectory_data` may then be empty."""
+    to the ones `compute_features` reads (reference deep_carto.py:202-215); `trajectory_data` may then be empty.
+    A run that started from trajectories hands them, their topologies and `compute_features.plumed_settings.traj_stride`
+    on to `traj_cluster`, which then leaves `traj_cluster/<cv>/centroids/cluster_<k>.pdb` and, with
+    `traj_cluster: {output_structures: all}`, `traj_cluster/<cv>/<trajectory>/cluster_<k>.xtc` (reference :350-360)."""
     t0 = time.time()
     output_folder = output_folder or "deep_cartograph"
     if not restart:
@@ -106,8 +109,13 @@ def deep_cartograph(configuration: Dict, colvars_paths: List[str], sup_colvars_p
                                     output_folder=os.path.join(output_folder, "traj_projection"))
     clusters = {}
     for cv, paths in cv_paths.items():
+        # started from trajectories: traj_cluster extracts the centroid structures and the cluster ensembles from them
+        # (reference deep_carto.py:350-360); a sample of the CV trajectory is every traj_stride-th frame
+        from_trajectories = dict(trajectories=trajectory_data, topologies=topology_data, frames_per_sample=int(
+            ((configuration.get("compute_features") or {}).get("plumed_settings") or {}).get("traj_stride", 1))) if trajectory_data else {}
         clusters[cv] = traj_cluster(configuration=configuration.get("traj_cluster", {}), cv_traj_paths=paths,
-                                    sup_cv_traj_paths=sup_paths.get(cv), output_folder=os.path.join(output_folder, "traj_cluster", cv))
+                                    sup_cv_traj_paths=sup_paths.get(cv), output_folder=os.path.join(output_folder, "traj_cluster", cv),
+                                    **from_trajectories)
     logger.info("Total elapsed time: %s", time.strftime("%H h %M min %S s", time.gmtime(time.time() - t0)))
     return {"train_colvars": cv_paths, "traj_projection": sup_paths, "traj_cluster": clusters}
 

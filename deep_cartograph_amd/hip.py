@@ -432,6 +432,112 @@ def xtc_decode(data: torch.Tensor, frames, n_atoms: int, scale: float = 10.0, ou
     return result
 
 
+def xtc_encode_slots(xyz: torch.Tensor, n_atoms: int, strides=None, frames=None, precision: float = 1000.0, inv_scale: float = 0.1,
+                     slots: Optional[torch.Tensor] = None):
+    """The first half of :func:`xtc_encode` (dcv_xtc_encode): every frame compressed into a slot of its own.  Returns
+    ``(slots, desc, status)``: a uint8 device tensor of ``n * dcv_xtc_encode_slot_bytes(n_atoms)`` bytes (``slots`` when
+    given: a contiguous uint8 buffer or view of at least that size), the descriptors as a host array of
+    ``_lib.XTC_FRAME_DTYPE`` records (``offset`` is the slot's offset) and an int32 [n] device tensor of status words
+    (0: encoded; ``_lib.XTC_ENC_STATUS``).  Arguments as in :func:`xtc_encode`."""
+    _require_gpu(xyz, slots)
+    n_atoms = int(n_atoms)
+    if n_atoms < 1:
+        raise DcvError(f"xtc_encode: {n_atoms} atoms")
+    n_src, base, fs, as_, cs = _coordinates("xtc_encode", xyz, n_atoms, strides)
+    if frames is not None:
+        frames = np.ascontiguousarray(np.asarray(frames).reshape(-1), dtype=np.int64)
+    n = n_src if frames is None else int(frames.size)
+    lib = _lib.load()
+    slot = int(lib.dcv_xtc_encode_slot_bytes(n_atoms))
+    if slots is None:
+        slots = torch.empty(n * slot, dtype=torch.uint8, device=xyz.device)
+    elif slots.dim() != 1 or slots.dtype != torch.uint8 or not slots.is_contiguous() or slots.device != xyz.device:
+        raise DcvError("xtc_encode: slots must be a contiguous 1-D uint8 buffer on the device of the coordinates")
+    desc = torch.empty(n * _lib.XTC_FRAME_DTYPE.itemsize, dtype=torch.uint8, device=xyz.device)
+    status = torch.empty(n, dtype=torch.int32, device=xyz.device)
+    if n == 0:   # an empty tensor has no data pointer to hand to the library
+        return slots, np.zeros(0, dtype=_lib.XTC_FRAME_DTYPE), status
+    if n_src < 1:
+        raise DcvError(f"xtc_encode: {n} frame indices into a trajectory without frames")
+    ws = _ws(lib.dcv_xtc_encode_workspace(n), xyz.device)
+    check(lib.dcv_xtc_encode(base, n_src, max(fs, 1) if n_src == 1 else fs, as_, cs, n_atoms, None if frames is None else frames.ctypes.data, n,
+                             float(inv_scale), float(precision), _ptr(slots), slots.numel(), _ptr(desc), _ptr(status), _ptr(ws), ws.numel(),
+                             _stream()), "dcv_xtc_encode")
+    return slots, desc.cpu().numpy().view(_lib.XTC_FRAME_DTYPE).reshape(-1), status
+
+
+def xtc_image_offsets(desc: np.ndarray, status: np.ndarray, n_atoms: int) -> Tuple[np.ndarray, int]:
+    """(offsets, bytes): where every frame begins in the file image -- the prefix sum over 56 + 36 + nbytes rounded up to 4
+    (56 + 12 n_atoms for raw frames) of the frames that are not marked, -1 for the marked ones -- and the image's size."""
+    good = np.asarray(status) == 0
+    size = np.full(len(desc), 56 + 12 * int(n_atoms), dtype=np.int64) if n_atoms <= 9 else 92 + (desc["nbytes"].astype(np.int64) + 3) // 4 * 4
+    size = np.where(good, size, 0)
+    offsets = np.cumsum(size) - size
+    offsets[~good] = -1
+    return np.ascontiguousarray(offsets, dtype=np.int64), int(size.sum())
+
+
+def xtc_pack(slots: torch.Tensor, desc: np.ndarray, offsets: np.ndarray, n_atoms: int, step, time, box=None,
+             image: Optional[torch.Tensor] = None, image_bytes: Optional[int] = None) -> torch.Tensor:
+    """The second half of :func:`xtc_encode` (dcv_xtc_pack): the slots copied behind their headers into one file image
+    (a uint8 device tensor of ``image_bytes``, or ``image`` when given).  ``desc`` and ``offsets`` (-1: not packed) on the
+    host, ``step`` int32 [n], ``time`` float32 [n], ``box`` float32 [n, 3, 3] or None (zeros)."""
+    _require_gpu(slots, image)
+    n = len(desc)
+    desc = np.ascontiguousarray(desc)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    step = np.ascontiguousarray(np.asarray(step).reshape(-1), dtype=np.int32)
+    time = np.ascontiguousarray(np.asarray(time).reshape(-1), dtype=np.float32)
+    if desc.dtype != _lib.XTC_FRAME_DTYPE or offsets.size != n or step.size != n or time.size != n:
+        raise DcvError(f"xtc_pack: {n} descriptors of {desc.dtype}, {offsets.size} offsets, {step.size} steps and {time.size} times")
+    if box is not None:
+        box = np.ascontiguousarray(np.asarray(box, dtype=np.float32).reshape(-1))
+        if box.size != 9 * n:
+            raise DcvError(f"xtc_pack: box must hold 9 values for each of the {n} frames, got {box.size}")
+    if image is None:
+        image = torch.empty(int(image_bytes), dtype=torch.uint8, device=slots.device)
+    elif image.dim() != 1 or image.dtype != torch.uint8 or not image.is_contiguous() or image.device != slots.device:
+        raise DcvError("xtc_pack: image must be a contiguous 1-D uint8 buffer on the device of the slots")
+    if n == 0:
+        return image
+    lib = _lib.load()
+    ws = _ws(lib.dcv_xtc_pack_workspace(n), slots.device)
+    check(lib.dcv_xtc_pack(_ptr(slots), slots.numel(), desc.ctypes.data, offsets.ctypes.data, step.ctypes.data, time.ctypes.data,
+                           None if box is None else box.ctypes.data, n, int(n_atoms), _ptr(image) if image.numel() else _ptr(ws), image.numel(),
+                           _ptr(ws), ws.numel(), _stream()), "dcv_xtc_pack")
+    return image
+
+
+def xtc_encode(xyz: torch.Tensor, n_atoms: int, strides=None, frames=None, precision: float = 1000.0, inv_scale: float = 0.1, step=None,
+               time=None, box=None, return_status: bool = False):
+    """Frames written as a GROMACS ``.xtc`` file image on the device (dcv_xtc_encode, dcv_xtc_pack).  Returns the image
+    as a uint8 device tensor: the bytes of a file that holds the frames in the order given.
+
+    ``xyz``, ``n_atoms`` and ``strides`` as in :func:`featurize` (Angstrom; ``inv_scale`` 0.1 makes the file's
+    nanometres).  ``frames``: indices of the source frames to write, in any order, repeats allowed (None: all, in
+    order) -- the frames of a cluster are gathered by the encoder itself.  ``precision``: the file's precision (1000:
+    0.001 nm).  ``step`` (int32), ``time`` (float32) and ``box`` ([n, 3, 3] float32, nm) fill the frame headers; the
+    defaults are the source frame index, that index as float32, and zeros.
+    Internally: encode into per-frame slots, download the descriptors, prefix sum of the lengths on the host, pack.
+    A frame with a NaN or infinite coordinate, or one that does not fit a 32-bit integer at this precision, raises
+    DcvError naming the first such frame; with ``return_status`` nothing is raised, the marked frames are absent from the
+    image and ``(image, desc, status)`` is returned: the descriptors (host, ``_lib.XTC_FRAME_DTYPE``) and an int32 [n]
+    device tensor (0: encoded)."""
+    slots, desc, status = xtc_encode_slots(xyz, n_atoms, strides, frames, precision, inv_scale)
+    n = len(desc)
+    status_h = status.cpu().numpy()
+    bad = np.flatnonzero(status_h)
+    if bad.size and not return_status:
+        code = int(status_h[bad[0]])
+        raise DcvError(f"xtc_encode: frame {int(bad[0])} of the {n} given cannot be written: {_lib.XTC_ENC_STATUS.get(code, f'status {code}')}")
+    source = np.arange(n, dtype=np.int64) if frames is None else np.asarray(frames, dtype=np.int64).reshape(-1)
+    step = source if step is None else step
+    time = source.astype(np.float32) if time is None else time
+    offsets, image_bytes = xtc_image_offsets(desc, status_h, int(n_atoms))
+    image = xtc_pack(slots, desc, offsets, n_atoms, step, time, box, image_bytes=image_bytes)
+    return (image, desc, status) if return_status else image
+
+
 def normalize(X: torch.Tensor, mean: torch.Tensor, rng: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(x - mean) / range in float32; ``out`` may be X itself (in place)."""
     _require_gpu(X, mean, rng, out)

@@ -1,8 +1,9 @@
 """The tools of the CV-fit path with the reference's API (argument names, output tree,
 CSV formats): align_trajectories (tools/align_trajectories/align_trajectories.py:70-189), analyze_geometry (tools/analyze_geometry/analyze_geometry.py:13-143), traj_augmentation (tools/traj_augmentation/traj_augmentation.py:23-131), compute_features (tools/compute_features/compute_features.py:25-227), filter_features (tools/filter_features/filter_features.py:22-31), train_colvars (tools/train_colvars/train_colvars.py:20-36), traj_projection
 (tools/traj_projection/traj_projection.py:19-27), traj_cluster (tools/traj_cluster/traj_cluster.py:
-18-28).  Figures, FES estimation and PDB/XTC extraction (matplotlib / MDAnalysis) are outside the
-accelerated path and are not produced."""
+18-28).  traj_cluster extracts its structures itself: centroid PDBs on the host, the frames of every cluster as GROMACS
+.xtc files compressed on the device (trajectory.extract_frames).  Figures and FES estimation (matplotlib) are outside
+the accelerated path and are not produced."""
 from __future__ import annotations
 
 import logging
@@ -471,17 +472,52 @@ def _read_cv_traj(paths: List[str]) -> pd.DataFrame:
     return pd.concat(data, ignore_index=True)
 
 
+def _extract_centroids(cv_data: pd.DataFrame, trajectories: List[str], topologies: List[str], folder: str) -> None:
+    """<folder>/cluster_<label>.pdb for every row marked as a centroid: the topology with the positions of that frame, read
+    on the host (one frame each), without bonds (reference traj_cluster_workflow.py:140-168, md.py extract_PDB)."""
+    import dataclasses
+
+    from . import trajectory
+
+    logger.info("Extracting centroids from the trajectories...")
+    for _, row in cv_data[cv_data["centroid"] == True].iterrows():   # noqa: E712 -- the column may hold objects
+        i, frame, label = int(row["traj_label"]), int(row["frame"]), int(row["cluster"])
+        top = trajectory.read_topology(topologies[i])
+        traj = trajectory.open_trajectory(trajectories[i], top.n_atoms)
+        if not 0 <= frame < traj.n_frames:
+            raise ValueError(f"{trajectories[i]}: frame {frame} asked for, the trajectory has frames 0 to {traj.n_frames - 1}")
+        os.makedirs(folder, exist_ok=True)
+        logger.info(f"Extracting centroid for cluster {label} from trajectory {Path(trajectories[i]).name} at frame {frame}.")
+        trajectory.write_topology(os.path.join(folder, f"cluster_{label}.pdb"),
+                                  dataclasses.replace(top, positions=traj.frames(frame, frame + 1)[0], bonds=None))
+
+
 def traj_cluster(configuration: Dict, cv_traj_paths: Union[str, List[str]], trajectories: Optional[List[str]] = None,
                  topologies: Optional[List[str]] = None, sup_cv_traj_paths: Optional[List[str]] = None,
                  sup_trajectories: Optional[List[str]] = None, sup_topologies: Optional[List[str]] = None,
-                 frames_per_sample: Optional[int] = 1, output_folder: str = "traj_cluster") -> Dict[str, List[str]]:
-    """Cluster the CV trajectories (CSV in, CSV with cluster / centroid / frame columns out)."""
+                 frames_per_sample: Optional[int] = 1, output_folder: str = "traj_cluster", memory_budget: Optional[int] = None) -> Dict[str, List[str]]:
+    """Cluster the CV trajectories (CSV in, CSV with cluster / centroid / frame columns out).  With `trajectories` and
+    `topologies` (one PDB for all, or one per trajectory; .dcd / .npy, a GROMACS .xtc is imported first into
+    <out>/xtc_import) and `output_structures` "centroids" or "all", <out>/centroids/cluster_<label>.pdb holds the frame of
+    every centroid (the topology's atoms with that frame's positions, no CONECT records, as the reference strips them);
+    with "all", <out>/<trajectory>/cluster_<label>.xtc holds the frames of every cluster of every trajectory in ascending
+    order, HDBSCAN's noise label -1 included (reference traj_cluster_workflow.py:140-194), compressed on the device
+    (trajectory.extract_frames) in chunks of at most `memory_budget` bytes.  The returned dictionary names the CSV files."""
     os.makedirs(output_folder, exist_ok=True)
     configuration = validate_configuration(configuration or {}, TrajClusterSchema, output_folder)
     if configuration["run"] is False:
         logger.info("traj_cluster workflow set to not run. Exiting...")
         return {}
     cv_traj_paths = _as_list(cv_traj_paths)
+    trajectories, topologies = _as_list(trajectories), _as_list(topologies)
+    extract = configuration["output_structures"] in ("centroids", "all") and bool(trajectories) and bool(topologies)
+    if extract:
+        if len(topologies) == 1:
+            topologies = topologies * len(trajectories)
+        if len(trajectories) != len(cv_traj_paths) or len(topologies) != len(trajectories):
+            raise ValueError(f"traj_cluster: {len(trajectories)} trajectories and {len(topologies)} topologies for {len(cv_traj_paths)} "
+                             "CV trajectories (one topology for all, or one per trajectory)")
+        trajectories = _route_xtc(trajectories, output_folder, memory_budget)
     cv_data = _read_cv_traj(cv_traj_paths)
     cv_labels = cv_data.columns[:-1].tolist()
     labels, centroids = statistics.optimize_clustering(cv_data[cv_labels].to_numpy(), configuration)
@@ -500,6 +536,22 @@ def traj_cluster(configuration: Dict, cv_traj_paths: Union[str, List[str]], traj
         p = os.path.join(folder, "projected_trajectory.csv")
         cv_data[cv_data["traj_label"] == i].to_csv(p, index=False)
         out[name] = [p]
+    if configuration["output_structures"] in ("centroids", "all"):
+        if extract:
+            _extract_centroids(cv_data, trajectories, topologies, os.path.join(output_folder, "centroids"))
+        else:
+            logger.warning("Trajectory and/or topology files not provided. Skipping extraction of centroids from the trajectory.")
+    if configuration["output_structures"] == "all":
+        if extract:
+            for i in range(len(cv_traj_paths)):
+                rows = cv_data[cv_data["traj_label"] == i]
+                for label in rows["cluster"].unique():
+                    from . import trajectory
+
+                    trajectory.extract_frames(trajectories[i], topologies[i], rows.loc[rows["cluster"] == label, "frame"].to_numpy(),
+                                              os.path.join(output_folder, Path(trajectories[i]).stem, f"cluster_{int(label)}.xtc"), memory_budget)
+        else:
+            logger.warning("Trajectory and/or topology files not provided. Skipping extraction of cluster ensembles from the trajectory.")
     if sup_cv_traj_paths:
         sup = _read_cv_traj(_as_list(sup_cv_traj_paths))
         if sup.shape[1] - 1 != len(cv_labels):

@@ -12,6 +12,9 @@ modules/md/md.py) is restated for the feature kinds its own test data pins:
                            hip.xtc_decode, xtc.py has the import step);
 * ``write_dcd``, ``write_topology``  the way back out (traj_augmentation): a chunked DCD writer whose record images a
                            kernel fills in place, and a PDB of a selection with its CONECT records;
+* ``write_xtc``, ``extract_frames``  chosen frames of a trajectory written as a GROMACS ``.xtc`` (traj_cluster's cluster
+                           ensembles): the frames are compressed on the device (hip.xtc_encode), the writer appends
+                           finished file images;
 * ``feature_definitions``  names and kernel records of the distance and virtual-dihedral groups, with the
                            reference's labelling rules and order (md.py:26-129, 226-273, 479-545, 580-717).
 
@@ -28,6 +31,7 @@ are not applied: the reference's distances are NOPBC and its torsions follow a W
 whose molecule is split across the box must be made whole first.  XTC is not mapped but imported (xtc.py)."""
 from __future__ import annotations
 
+import logging
 import math
 import os
 import re
@@ -38,6 +42,8 @@ from typing import Dict, List, Optional, Set, Tuple
 import numpy as np
 
 from ._lib import FEAT_DISTANCE, FEAT_TORSION, FEAT_TORSION_SINCOS, XTC_FRAME_DTYPE
+
+logger = logging.getLogger(__name__)
 
 COVALENT_BOND_THRESHOLD = 2.0   # Angstrom: the reference's guess for a bond when the topology has no CONECT records
 
@@ -488,6 +494,117 @@ class DcdWriter:
 def write_dcd(path: str, n_atoms: int) -> DcdWriter:
     """Open ``path`` for chunked DCD output (see :class:`DcdWriter`)."""
     return DcdWriter(path, n_atoms)
+
+
+class XtcWriter:
+    """Chunked writer of a GROMACS ``.xtc`` file.  A chunk is a finished *file image* -- whole big-endian frames, as
+    hip.xtc_encode returns them -- so ``append`` only checks that the image starts with a frame of this writer's atom
+    count and appends it.  The frames land under ``<path>.partial``; ``close`` renames that file to ``path``, so an
+    interrupted run leaves nothing a restart could take for a finished ensemble."""
+
+    def __init__(self, path: str, n_atoms: int):
+        if n_atoms < 1:
+            raise ValueError(f"write_xtc: {n_atoms} atoms")
+        self.path, self.partial_path, self.n_atoms, self.n_bytes = path, path + ".partial", int(n_atoms), 0
+        self._file = open(self.partial_path, "wb")
+
+    def append(self, image) -> None:
+        """Append whole frames: the bytes of a file image (bytes, or a uint8 array)."""
+        data = image if isinstance(image, (bytes, bytearray, memoryview)) else np.ascontiguousarray(image, dtype=np.uint8).tobytes()
+        if len(data) == 0:
+            return
+        if len(data) % 4 or len(data) < 56:
+            raise ValueError(f"write_xtc: an image of {len(data)} bytes is not a whole number of frames (every field of the file takes 4 bytes)")
+        magic, n = struct.unpack_from(">ii", data, 0)
+        if magic != XTC_MAGIC or n != self.n_atoms:
+            raise ValueError(f"write_xtc: the image starts with magic {magic} and {n} atoms, expected {XTC_MAGIC} and {self.n_atoms}")
+        self._file.write(data)
+        self.n_bytes += len(data)
+
+    def close(self) -> None:
+        if self._file is None:
+            return
+        self._file.close()
+        self._file = None
+        os.replace(self.partial_path, self.path)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        elif self._file is not None:   # nothing is left under the final name, and nothing half-written under the other
+            self._file.close()
+            self._file = None
+            os.remove(self.partial_path)
+        return False
+
+
+def write_xtc(path: str, n_atoms: int) -> XtcWriter:
+    """Open ``path`` for chunked XTC output (see :class:`XtcWriter`)."""
+    return XtcWriter(path, n_atoms)
+
+
+def extraction_chunks(frames: np.ndarray, frame_bytes: int, out_bytes: int, memory_budget: int) -> List[Tuple[int, int]]:
+    """[lo, hi) ranges of the ascending frame indices ``frames`` so that a chunk's device memory -- the source frames from
+    its first to its last index (``frame_bytes`` each, the skipped ones included) and ``out_bytes`` per chosen frame --
+    stays within ``memory_budget``; a chunk holds at least one frame."""
+    chunks, lo, n = [], 0, len(frames)
+    while lo < n:
+        hi = lo + 1
+        while hi < n and (int(frames[hi]) - int(frames[lo]) + 1) * frame_bytes + (hi + 1 - lo) * out_bytes <= memory_budget:
+            hi += 1
+        chunks.append((lo, hi))
+        lo = hi
+    return chunks
+
+
+def extract_frames(trajectory_path: str, topology_path: str, frames, out_path: str, memory_budget: Optional[int] = None,
+                   precision: float = 1000.0) -> Optional[str]:
+    """The frames ``frames`` of a trajectory (``.dcd``, mapped in place, or ``.npy``) written as the GROMACS ``.xtc`` file
+    ``out_path``, in ascending order of their indices whatever order they are given in (reference md.py:715-760,
+    extract_XTC).  The topology (a PDB) gives the atom count the trajectory must have.  An index outside the trajectory
+    raises ValueError naming the file and the index; an empty list logs a warning and writes nothing (returns None).
+    The frames go through the device in chunks of at most ``memory_budget`` bytes (default: a quarter of free device
+    memory, at most 4 GiB): the source frames of a chunk are uploaded as they lie in the file, hip.xtc_encode gathers and
+    compresses the chosen ones, and the finished file image is downloaded and appended.  Steps are the source frame
+    indices, times those indices as float32, the box zeros: DCD input carries neither times nor, here, a box.
+    No CPU fallback."""
+    frames = np.sort(np.asarray(list(frames) if not isinstance(frames, np.ndarray) else frames, dtype=np.int64).reshape(-1))
+    if frames.size == 0:
+        logger.warning(f"No frames to extract from {trajectory_path}: {out_path} is not written.")
+        return None
+    traj = open_trajectory(trajectory_path, read_topology(topology_path).n_atoms)
+    if frames[0] < 0 or frames[-1] >= traj.n_frames:
+        bad = int(frames[0]) if frames[0] < 0 else int(frames[-1])
+        raise ValueError(f"{trajectory_path}: frame {bad} asked for, the trajectory has frames 0 to {traj.n_frames - 1}")
+    import torch
+
+    from . import hip
+    from ._lib import DcvError
+    from .tools import DEFAULT_CHUNK_BYTES
+
+    if not torch.cuda.is_available():
+        raise DcvError("extract_frames needs an MI355X (cuda) device: XTC frames are encoded by libdcv.so, there is no CPU fallback")
+    if memory_budget is None:
+        memory_budget = min(torch.cuda.mem_get_info()[0] // 4, DEFAULT_CHUNK_BYTES)
+    A = traj.n_atoms
+    out_bytes = 2 * (13 * A + 4) + 92 + 120 + 48 + 8 + 4   # slot and image, pack record, descriptor, index, status
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with write_xtc(out_path, A) as writer:
+        for lo, hi in extraction_chunks(frames, 4 * traj.frame_stride, out_bytes, int(memory_budget)):
+            first, last = int(frames[lo]), int(frames[hi - 1])
+            data, layout = traj.span(first, last + 1)
+            buf = torch.from_numpy(np.array(data)).cuda()
+            try:
+                image = hip.xtc_encode(buf, A, strides=layout, frames=frames[lo:hi] - first, precision=precision, step=frames[lo:hi],
+                                       time=frames[lo:hi].astype(np.float32))
+            except DcvError as e:
+                raise DcvError(f"{trajectory_path}: frames {first}..{last}: {e}") from None
+            writer.append(image.cpu().numpy())
+            del buf, image
+    return out_path
 
 
 def write_topology(path: str, top: Topology, atoms=None) -> None:

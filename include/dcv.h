@@ -338,6 +338,85 @@ int dcv_xtc_decode(const void* bytes_d, int64_t n_bytes, const dcv_xtc_frame* fr
                    float scale, float* out_d, int64_t out_frame_stride, int64_t out_atom_stride, int64_t out_comp_stride,
                    int32_t* status_d, void* ws_d, size_t ws_bytes, void* stream);
 
+/* ---- GROMACS XTC frames encoded on the device (traj_cluster: the frames of every cluster) ---------------------------
+ * The inverse of dcv_xtc_decode, in two launches.  dcv_xtc_encode compresses frames into *slots*, one per frame, because
+ * the length of a frame's stream is known only when it has been written; the host sums the lengths; dcv_xtc_pack writes
+ * the finished big-endian frames -- header, fields, payload, zero padding -- into one contiguous file image.
+ *
+ * Input.  Coordinate c of atom a of source frame s is xyz_d[s*frame_stride + a*atom_stride + c*comp_stride] (strides in
+ * ELEMENTS, all >= 1), as in dcv_featurize: dense rows or the planes of DCD frame records, read in place.  frames_h (HOST,
+ * or NULL) holds n_frames indices into the n_src_frames source frames, in any order, repeats allowed: output frame f is
+ * source frame frames_h[f].  NULL: output frame f is source frame f, n_frames <= n_src_frames.  The indices are checked
+ * and copied into the workspace; gathering costs no pass of its own.
+ *
+ * Quantisation, per coordinate, in float32 and never contracted into a fused multiply-add:
+ *     lf = (x * inv_scale) * precision          (x in Angstrom: inv_scale = 0.1f;  the usual precision is 1000)
+ *     i  = (int32)truncf(lf + copysignf(0.5f, lf))
+ * A frame with a coordinate that is not finite is marked DCV_XTC_ENC_NONFINITE; otherwise one with a value for which
+ * !(fabsf(lf) < 2147483520.0f) -- the largest float32 below 2^31 -- is marked DCV_XTC_ENC_RANGE.  Nothing is written to
+ * the slot of a marked frame and its descriptor keeps offset, precision and raw only.  Quantising what dcv_xtc_decode
+ * wrote (scale 10) gives back the integers of the file: a trajectory that came from an .xtc is re-encoded losslessly.
+ *
+ * The frame.  minint / maxint per component over the frame; sizeint, bitsize or the three bitsizeint, the payload's bit
+ * order and unpack3 as described for dcv_xtc_decode above; pack3 is the inverse of unpack3: v = (n0*sizes[1] + n1)*sizes[2]
+ * + n2 in three 32-bit limbs, nbits/8 whole bytes LEAST significant first, then the nbits%8 remaining bits.  natoms <= 9 is
+ * the raw form: 3*natoms big-endian float32 of x * inv_scale (marked only for coordinates that are not finite).
+ *
+ * The policy -- which legal stream is written.  q[a] the quantised atoms, N = natoms, all differences exact (64 bits):
+ *   starting smallidx:  mindiff = min over a >= 1 of |dx| + |dy| + |dz| between q[a] and q[a-1];
+ *                       s = 9;  while s < 72 and magic[s] < mindiff: s++
+ *   the group that starts at atom p with the current s:   smallnum = magic[s]/2;  sizesmall = magic[s]
+ *       reach(a, b): 0 <= a_c - b_c + smallnum < sizesmall for all three components
+ *       r = 0;  if p+1 < N and reach(q[p], q[p+1]):  r = 1, prev = q[p]      (the water swap: q[p+1] is written as the
+ *                                                                             full-range atom, q[p] is coded against it)
+ *           while r < 8 and p+1+r < N and reach(q[p+1+r], prev):  prev = q[p+1+r];  r++
+ *       (a run always begins with the swap: without it the group is the single atom p.)  The group covers atoms p .. p+r.
+ *   step of smallidx:   r == 0:  +1 when s < 72, else 0
+ *                       r >  0:  -1 when s > 9 and every component of every difference coded in the group has
+ *                                |d| < magic[max(9, s-1)]/2, else 0
+ *   flag = 0 (the run value is reused) exactly when 3r equals the run value written last (0 at the start of a frame) and
+ *   the step is 0; otherwise flag = 1 and the 5-bit value 3r + step + 1.
+ * tests/xtc_encode_oracle.py restates all of it in Python; the device bytes are compared with it bit for bit.
+ *
+ * Capacity.  A frame needs at most 102*natoms bits: 96 for a full-range atom plus 6 of flag and run value, and a small
+ * atom costs smallidx <= 72 bits.  The slot of frame f is dcv_xtc_encode_slot_bytes(natoms) = ceil(102*natoms/8) rounded
+ * up to 4 bytes, at slots_d + f*slot; it receives the payload and its zero padding to a multiple of 4 (a raw frame: the
+ * floats) and nothing behind that; the writer checks the slot's end before every store all the same.
+ * desc_d[f] (DEVICE) is the dcv_xtc_frame of frame f -- offset = f*slot, nbytes, smallidx, precision, raw, minint, maxint;
+ * a raw frame has zeros in all of them but offset and raw, as trajectory.index_xtc reports it -- and status_d[f] its status.
+ *
+ * A lane owns a frame, one-wave workgroups, one atom consumed per iteration in every lane; the wave stages blocks of 16
+ * atoms of its 64 frames in LDS with loads that are contiguous along the atoms of a frame (two blocks resident: the policy
+ * looks at most 8 atoms ahead); two passes over the atoms (minima, maxima and mindiff; then the stream), quantising from
+ * the staged floats both times; a 64-bit window, finished 32-bit words stored byte-swapped.  No atomics.
+ * Validated on the host before anything is launched (DCV_EINVAL): NULL pointers; n_atoms < 1; negative frame counts;
+ * misaligned pointers (4 bytes; descriptors and workspace 8); strides below 1; an index outside [0, n_src_frames);
+ * n_frames > n_src_frames without indices; a precision that is not finite and positive; coordinates, slots, descriptors,
+ * status words and workspace that overlap.  DCV_ENOMEM: a workspace below dcv_xtc_encode_workspace(n_frames) when indices
+ * are given, or slots_bytes below n_frames slots.  Nothing is launched or written then.  n_frames = 0 is DCV_OK.
+ * Algorithmic traffic per frame: 12 bytes per atom read twice (the second time from L2 at best), its payload written.
+ *
+ * dcv_xtc_pack.  desc_h: the descriptors as dcv_xtc_encode left them, downloaded (HOST); image_offset_h[f]: where frame f
+ * begins in the image -- the prefix sum over 56 + 36 + nbytes rounded up to 4, or 56 + 12*natoms for raw frames -- or a
+ * negative value for a frame that is not packed (a marked one); step_h, time_h and box_h (9 floats a frame; NULL: zeros)
+ * fill the header.  A wave copies a frame in 4-byte words.  DCV_EINVAL: NULL or misaligned pointers; a descriptor whose
+ * raw flag disagrees with n_atoms, whose nbytes is negative or above the slot size, or whose payload does not lie on the
+ * 4-byte grid inside slots_bytes; an image offset off the 4-byte grid, below the end of the frame before or whose frame ends
+ * behind image_bytes; slots, image and workspace that overlap.  DCV_ENOMEM: a workspace below
+ * dcv_xtc_pack_workspace(n_frames).  Traffic: every packed frame's bytes read once and written once. */
+#define DCV_XTC_ENC_NONFINITE 1   /* a coordinate of the frame is NaN or infinite */
+#define DCV_XTC_ENC_RANGE 2       /* a coordinate of the frame does not fit a 32-bit integer at this precision */
+size_t dcv_xtc_encode_slot_bytes(int32_t n_atoms);
+size_t dcv_xtc_encode_workspace(int64_t n_frames);
+int dcv_xtc_encode(const float* xyz_d, int64_t n_src_frames, int64_t frame_stride, int64_t atom_stride, int64_t comp_stride,
+                   int32_t n_atoms, const int64_t* frames_h, int64_t n_frames, float inv_scale, float precision,
+                   void* slots_d, size_t slots_bytes, dcv_xtc_frame* desc_d, int32_t* status_d, void* ws_d, size_t ws_bytes,
+                   void* stream);
+size_t dcv_xtc_pack_workspace(int64_t n_frames);
+int dcv_xtc_pack(const void* slots_d, size_t slots_bytes, const dcv_xtc_frame* desc_h, const int64_t* image_offset_h,
+                 const int32_t* step_h, const float* time_h, const float* box_h, int64_t n_frames, int32_t n_atoms,
+                 void* image_d, size_t image_bytes, void* ws_d, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- normalisation (a3)
  * Replaces LinearCalculator.normalize_data, cv_calculator.py:833-835
  * (data.sub_(mean).div_(range) in float32).  Y may alias X (in place, as the reference). */
