@@ -35,7 +35,6 @@ logger = logging.getLogger(__name__)
 
 WRITTEN_FORMATS = ("dcd", "npy")
 KINDS = {"pchip": "pchip", "akima": "makima", None: "pchip"}   # interpolation_method -> kind of hip.interpolate
-DEFAULT_CHUNK_BYTES = 4 << 30   # default upper limit of a chunk of output frames on the device
 
 
 def new_frame_times(n: int, num_frames: int, keep_original_frames: bool) -> np.ndarray:
@@ -87,7 +86,7 @@ def interpolate_trajectory(topology_file: str, trajectory_file: str, num_frames:
     ``memory_budget`` bytes of device memory (default: a quarter of what is free, at most 4 GiB).  No CPU fallback."""
     import torch
 
-    from . import hip, trajectory
+    from . import frame_io, hip, trajectory
     from ._lib import DcvError
 
     if interpolation_method not in KINDS:
@@ -118,34 +117,19 @@ def interpolate_trajectory(topology_file: str, trajectory_file: str, num_frames:
     logger.info(f"Interpolating {ns} atoms of {n} frames of {Path(trajectory_file).name} to {n_out} frames ({interpolation_method})")
 
     span, layout = traj.span(0, n)
-    knots = torch.from_numpy(np.array(span, dtype=np.float32)).cuda()
-    if memory_budget is None:
-        memory_budget = min(torch.cuda.mem_get_info()[0] // 4, DEFAULT_CHUNK_BYTES)
+    knots = frame_io.upload(span)
     noise = None if noise_std is None else NoiseStream(random_seed, noise_std)
     os.makedirs(os.path.dirname(new_traj_path) or ".", exist_ok=True)
     trajectory.write_topology(new_top_path, top, sel)
-    # the frames land under a temporary name: an interrupted run leaves nothing a restart would take for done
-    tmp_path = new_traj_path + ".partial"
     words = 3 * (ns + 2) if traj_format == "dcd" else 3 * ns
-    chunk = int(max(1, min(n_out, memory_budget // (4 * words + (24 * ns if noise else 0)))))
-    writer = trajectory.write_dcd(tmp_path, ns) if traj_format == "dcd" else None
-    rows = None if writer else np.lib.format.open_memmap(tmp_path, mode="w+", dtype=np.float32, shape=(n_out, ns, 3))
-    for lo in range(0, n_out, chunk):
-        hi = min(n_out, lo + chunk)
-        noise_d = torch.from_numpy(noise.draw(hi - lo, ns, 3)).cuda() if noise else None
-        kw = dict(kind=kind, sel=sel, strides=layout, extrapolate=True, noise=noise_d)
-        if writer:
-            image = torch.empty((hi - lo) * writer.frame_words, dtype=torch.float32, device="cuda")
-            hip.interpolate(knots, top.n_atoms, times[lo:hi], out=image, out_strides=writer.layout(), **kw)
-            writer.append(image.cpu().numpy())   # the kernel writes the planes, the host the record markers
-        else:
-            rows[lo:hi] = hip.interpolate(knots, top.n_atoms, times[lo:hi], **kw).cpu().numpy()
-    if writer:
-        writer.close()
-    else:
-        rows.flush()
-        del rows
-    os.replace(tmp_path, new_traj_path)
+    _, ranges = frame_io.plan_chunks(n_out, 4 * words + (24 * ns if noise else 0), frame_io.resolve_budget(memory_budget))
+    with frame_io.CoordinateSink(new_traj_path, n_out, ns) as sink:
+        for lo, hi in ranges:
+            noise_d = torch.from_numpy(noise.draw(hi - lo, ns, 3)).cuda() if noise else None
+            image = sink.image(hi - lo)
+            hip.interpolate(knots, top.n_atoms, times[lo:hi], kind=kind, sel=sel, strides=layout, extrapolate=True, noise=noise_d,
+                            out=image, out_strides=sink.layout())
+            sink.append(image)
     return new_traj_path, new_top_path
 
 

@@ -304,11 +304,11 @@ class CVCalculator(ABC):
                            memory_budget: Optional[int] = None) -> pd.DataFrame:
         """Project a trajectory (.dcd / .npy; a GROMACS .xtc is imported first) with a fitted / loaded CV straight from its coordinates: the model's own
         feature names are turned back into atoms of ``topology_path`` (trajectory.definitions_from_labels), so neither a
-        colvars file nor the features configuration of the training run is needed.  Frames are streamed in chunks as
-        tools.compute_features streams them (``memory_budget`` bytes of device memory per chunk, DCD records read in
+        colvars file nor the features configuration of the training run is needed.  Frames are streamed in chunks
+        (frame_io.stream: ``memory_budget`` bytes of device memory per chunk, DCD records read in
         place); only the frames x d result leaves the device.  Columns: the CV labels, as project_colvars.  No CPU fallback."""
-        from . import trajectory, xtc
-        from .tools import ANGSTROM_TO_NM, DEFAULT_CHUNK_BYTES
+        from . import frame_io, trajectory, xtc
+        from .tools import ANGSTROM_TO_NM
 
         if self.cv is None:
             raise ValueError("CV has not been computed. Cannot project a trajectory.")
@@ -329,16 +329,10 @@ class CVCalculator(ABC):
             raise ValueError(f"{trajectory_path}: no frames")
         dev = _device()
         row_floats, project_chunk = self._trajectory_projector(records, top.n_atoms, ANGSTROM_TO_NM, dev)
-        if memory_budget is None:
-            memory_budget = min(torch.cuda.mem_get_info()[0] // 4, DEFAULT_CHUNK_BYTES)
-        per_frame = 4 * (stride * traj.frame_stride + row_floats)
-        chunk = int(max(1, min(n, memory_budget // per_frame)))
+        chunk, ranges = frame_io.plan_chunks(n, 4 * (stride * traj.frame_stride + row_floats), frame_io.resolve_budget(memory_budget))
         logger.info(f"Projecting {n} frames of {Path(trajectory_path).name} onto {self.cv_name} in chunks of {chunk} frames")
         rows = np.empty((n, self.cv_dimension), dtype=np.float32)
-        for lo in range(0, n, chunk):
-            hi = min(n, lo + chunk)
-            span, layout = traj.span(lo * stride, (hi - 1) * stride + 1, stride)
-            buf = torch.from_numpy(np.array(span, dtype=np.float32)).to(dev)
+        for lo, hi, buf, layout in frame_io.stream(traj, ranges, stride):
             block, finite = project_chunk(buf, layout)
             rows[lo:hi] = block.cpu().numpy()
             if not finite or not np.isfinite(rows[lo:hi]).all():

@@ -2,8 +2,8 @@
 (hip.featurize).  What the reference does with MDAnalysis, one Python iteration per frame (modules/md/md.py:1397-1574),
 restated on the per-frame optimal superposition kernel.
 
-Frames are streamed as tools.compute_features streams them: `Trajectory.span` slices of at most `memory_budget` bytes go
-to the device as they are in the file, results come back per chunk.  No CPU fallback: without a device every function
+Frames are streamed in chunks (frame_io.py): `Trajectory.span` slices of at most `memory_budget` bytes go to the device
+as they are in the file, results come back per chunk.  No CPU fallback: without a device every function
 raises DcvError.
 
 Not reproduced: MDAnalysis rounds the aligned positions to float32 before the group RMSD and the RMSF, here they stay
@@ -13,18 +13,16 @@ fits unweighted too)."""
 from __future__ import annotations
 
 import logging
-import os
 from typing import Optional, Tuple
 
 import numpy as np
 
-from . import trajectory
+from . import frame_io, trajectory
 from ._lib import DcvError
 
 logger = logging.getLogger(__name__)
 
-ANGSTROM_TO_NM = 0.1            # PLUMED's length unit: dRMSD values are in nm
-DEFAULT_CHUNK_BYTES = 4 << 30   # default upper limit of a chunk (device bytes; the same again on the host)
+ANGSTROM_TO_NM = 0.1   # PLUMED's length unit: dRMSD values are in nm
 
 
 def _as_topology(top) -> trajectory.Topology:
@@ -56,21 +54,13 @@ def _require_device(what: str):
 
 def _chunks(traj: trajectory.Trajectory, per_frame_out: int, memory_budget: Optional[int]):
     """(lo, hi, device buffer, layout) of consecutive chunks of frames that fit the budget."""
-    torch = _require_device("analyze_geometry")
+    _require_device("analyze_geometry")
     n = traj.n_frames
     if n == 0:
         raise ValueError("the trajectory has no frames")
-    if memory_budget is None:
-        # every chunk also exists once as a pageable host copy on its way up, so the default is capped for the host's sake
-        memory_budget = min(torch.cuda.mem_get_info()[0] // 4, DEFAULT_CHUNK_BYTES)
-    chunk = int(max(1, min(n, memory_budget // (4 * traj.frame_stride + per_frame_out))))
+    chunk, ranges = frame_io.plan_chunks(n, 4 * traj.frame_stride + per_frame_out, frame_io.resolve_budget(memory_budget))
     logger.info(f"Superposing {n} frames in chunks of {chunk} frames")
-    for lo in range(0, n, chunk):
-        hi = min(n, lo + chunk)
-        span, layout = traj.span(lo, hi)
-        buf = torch.from_numpy(np.array(span, dtype=np.float32)).cuda()
-        yield lo, hi, buf, layout
-        del buf
+    return frame_io.stream(traj, ranges)
 
 
 def rmsd(traj, top, selection: str, fit_selection: str, ref_top=None, memory_budget: Optional[int] = None) -> np.ndarray:
@@ -164,55 +154,31 @@ def align_trajectory(traj, top, fit, fit_ref, output_path: str, memory_budget: O
     ALL atoms of every frame, moved by the frame's transform (hip.transform_frames), to `output_path`: a `.dcd` without
     unit-cell blocks or a `.npy` of (n, A, 3) float32.  Returns the aligned first frame, float32 [A, 3].  Frames go
     through the device in chunks that hold their input records and their output image at once, at most `memory_budget`
-    bytes (default: a quarter of free device memory, at most 4 GiB); they land under `<output_path>.partial` and are
-    renamed at the end.  The fit set is bounded by dcv_superpose's staging limit of 5 461 atoms; the number of atoms
+    bytes (default: a quarter of free device memory, at most 4 GiB), into a frame_io.CoordinateSink: they land under
+    `<output_path>.partial` and are renamed at the end.  The fit set is bounded by dcv_superpose's staging limit of 5 461 atoms; the number of atoms
     written is not bounded.  float64 arithmetic with one rounding (MDAnalysis translates, rotates and translates in
     float32)."""
     from . import hip
 
-    torch = _require_device("align_trajectory")
+    _require_device("align_trajectory")
     top = _as_topology(top)
     traj = _as_trajectory(traj, top.n_atoms)
-    ext = os.path.splitext(output_path)[1].lower()
-    if ext not in (".dcd", ".npy"):
-        raise ValueError(f"{output_path}: the aligned trajectory is written as .dcd or .npy")
+    ext = frame_io.coordinate_format(output_path, "the aligned trajectory")
     fit = np.asarray(fit, dtype=np.int64).reshape(-1)
     fit_ref = np.asarray(fit_ref, dtype=np.float64)
     n, A = traj.n_frames, traj.n_atoms
     if n == 0:
         raise ValueError("the trajectory has no frames")
-    if memory_budget is None:
-        memory_budget = min(torch.cuda.mem_get_info()[0] // 4, DEFAULT_CHUNK_BYTES)
-    chunk = int(max(1, min(n, memory_budget // align_frame_bytes(traj, ext == ".dcd"))))
+    chunk, ranges = frame_io.plan_chunks(n, align_frame_bytes(traj, ext == ".dcd"), frame_io.resolve_budget(memory_budget))
     logger.info(f"Aligning {n} frames of {A} atoms on {len(fit)} atoms in chunks of {chunk} frames")
-    tmp_path = output_path + ".partial"
-    writer = trajectory.write_dcd(tmp_path, A) if ext == ".dcd" else None
-    rows = None if writer else np.lib.format.open_memmap(tmp_path, mode="w+", dtype=np.float32, shape=(n, A, 3))
-    first = None
-    for lo in range(0, n, chunk):
-        hi = min(n, lo + chunk)
-        span, layout = traj.span(lo, hi)
-        buf = torch.from_numpy(np.array(span, dtype=np.float32)).cuda()
-        transform = hip.superpose(buf, A, fit, fit_ref, strides=layout, want=("transform",))["transform"]
-        if writer:
-            image = torch.empty((hi - lo) * writer.frame_words, dtype=torch.float32, device="cuda")
-            hip.transform_frames(buf, A, transform, strides=layout, out=image, out_strides=writer.layout())
-            image = image.cpu().numpy()   # the kernel writes the planes, the host the record markers
-            if lo == 0:
-                first = np.ascontiguousarray(image[:writer.frame_words].reshape(3, A + 2)[:, 1:-1].T)
-            writer.append(image)
-        else:
-            rows[lo:hi] = hip.transform_frames(buf, A, transform, strides=layout).cpu().numpy()
-            if lo == 0:
-                first = np.array(rows[0], dtype=np.float32)
-        del buf
-    if writer:
-        writer.close()
-    else:
-        rows.flush()
-        del rows
-    os.replace(tmp_path, output_path)
-    return first
+    with frame_io.CoordinateSink(output_path, n, A) as sink:
+        for lo, hi, buf, layout in frame_io.stream(traj, ranges):
+            transform = hip.superpose(buf, A, fit, fit_ref, strides=layout, want=("transform",))["transform"]
+            image = sink.image(hi - lo)
+            hip.transform_frames(buf, A, transform, strides=layout, out=image, out_strides=sink.layout())
+            sink.append(image)
+            del buf, image
+    return trajectory.open_trajectory(output_path).frames(0, 1)[0]
 
 
 def drmsd(traj, top, selection: str, selection_stride: int, ref_top, memory_budget: Optional[int] = None) -> np.ndarray:

@@ -281,6 +281,25 @@ def superpose(xyz: torch.Tensor, n_atoms: int, fit, fit_ref, sel=None, sel_ref=N
     return out
 
 
+def _output(who: str, out: Optional[torch.Tensor], out_strides, n: int, n_atoms: int, device, source: str = "coordinates"):
+    """The ``out`` / ``out_strides`` pair of `who` (interpolate, transform_frames, xtc_decode) checked and resolved for
+    `n` frames of `n_atoms` atoms: (the tensor to return, the address of its first coordinate, frame, atom and component
+    stride in elements).  Without ``out`` that is a new dense float32 [n, n_atoms, 3] tensor on `device`."""
+    if (out is None) != (out_strides is None):
+        raise DcvError(f"{who}: out and out_strides go together")
+    if out is None:
+        out = torch.empty(n, n_atoms, 3, dtype=torch.float32, device=device)
+        return out, out.data_ptr(), 3 * n_atoms, 3, 1
+    off, ofs, oas, ocs = (int(v) for v in out_strides)
+    if out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
+        raise DcvError(f"{who}: out must be a contiguous 1-D float32 buffer on the device of the {source}")
+    last = off + max(n - 1, 0) * ofs + (n_atoms - 1) * oas + 2 * ocs
+    if off < 0 or min(ofs, oas, ocs) < 1 or (n > 0 and last >= out.numel()):
+        raise DcvError(f"{who}: output layout {tuple(out_strides)} with {n_atoms} atoms and {n} frames reaches element "
+                       f"{last} of a buffer of {out.numel()} (strides must be >= 1)")
+    return out, out.data_ptr() + 4 * off, ofs, oas, ocs
+
+
 INTERP_KINDS = {"pchip": INTERP_PCHIP, "makima": INTERP_MAKIMA}
 
 
@@ -313,27 +332,14 @@ def interpolate(xyz: torch.Tensor, n_atoms: int, t, kind: str = "pchip", sel=Non
                               or noise.device != xyz.device):
         raise DcvError(f"interpolate: noise must be a contiguous float64 ({n_out}, {n_sel}, 3) tensor on {xyz.device}, "
                        f"got {tuple(noise.shape)} {noise.dtype} on {noise.device}")
-    if (out is None) != (out_strides is None):
-        raise DcvError("interpolate: out and out_strides go together")
-    if out is None:
-        out = result = torch.empty(n_out, n_sel, 3, dtype=torch.float32, device=xyz.device)
-        off, ofs, oas, ocs = 0, 3 * n_sel, 3, 1
-    else:
-        result = out
-        off, ofs, oas, ocs = (int(v) for v in out_strides)
-        if out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous() or out.device != xyz.device:
-            raise DcvError("interpolate: out must be a contiguous 1-D float32 buffer on the device of the coordinates")
-        last = off + max(n_out - 1, 0) * ofs + (n_sel - 1) * oas + 2 * ocs
-        if off < 0 or min(ofs, oas, ocs) < 1 or (n_out > 0 and last >= out.numel()):
-            raise DcvError(f"interpolate: output layout {tuple(out_strides)} with {n_sel} atoms and {n_out} frames reaches element "
-                           f"{last} of a buffer of {out.numel()} (strides must be >= 1)")
+    result, out_ptr, ofs, oas, ocs = _output("interpolate", out, out_strides, n_out, n_sel, xyz.device)
     if n_out == 0:
         return result   # an empty tensor has no data pointer to hand to the library
     lib = _lib.load()
     ws = _ws(lib.dcv_interpolate_workspace(n, n_atoms, 0 if sel is None else n_sel, n_out), xyz.device)
     check(lib.dcv_interpolate(base if n else ws.data_ptr(), n, fs, as_, cs, n_atoms, None if sel is None else sel.ctypes.data,
                               0 if sel is None else n_sel, INTERP_KINDS[kind], int(bool(extrapolate)), t.ctypes.data, n_out,
-                              _ptr(noise), out.data_ptr() + 4 * off, ofs, oas, ocs, _ptr(ws), ws.numel(), _stream()),
+                              _ptr(noise), out_ptr, ofs, oas, ocs, _ptr(ws), ws.numel(), _stream()),
           "dcv_interpolate")
     return result
 
@@ -356,23 +362,10 @@ def transform_frames(xyz: torch.Tensor, n_atoms: int, transform: torch.Tensor, s
         raise DcvError(f"transform_frames: transform must be a float64 ({n}, >= 15) tensor with unit column stride on {xyz.device}, "
                        f"got {tuple(transform.shape)} {transform.dtype} strides {transform.stride()} on {transform.device}")
     ldt = max(int(transform.stride(0)), int(transform.shape[1])) if n <= 1 else int(transform.stride(0))   # a one-row stride is arbitrary
-    if (out is None) != (out_strides is None):
-        raise DcvError("transform_frames: out and out_strides go together")
-    if out is None:
-        out = result = torch.empty(n, n_atoms, 3, dtype=torch.float32, device=xyz.device)
-        off, ofs, oas, ocs = 0, 3 * n_atoms, 3, 1
-    else:
-        result = out
-        off, ofs, oas, ocs = (int(v) for v in out_strides)
-        if out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous() or out.device != xyz.device:
-            raise DcvError("transform_frames: out must be a contiguous 1-D float32 buffer on the device of the coordinates")
-        last = off + max(n - 1, 0) * ofs + (n_atoms - 1) * oas + 2 * ocs
-        if off < 0 or min(ofs, oas, ocs) < 1 or (n > 0 and last >= out.numel()):
-            raise DcvError(f"transform_frames: output layout {tuple(out_strides)} with {n_atoms} atoms and {n} frames reaches element "
-                           f"{last} of a buffer of {out.numel()} (strides must be >= 1)")
+    result, out_ptr, ofs, oas, ocs = _output("transform_frames", out, out_strides, n, n_atoms, xyz.device)
     if n == 0:
         return result   # an empty tensor has no data pointer to hand to the library
-    check(_lib.load().dcv_transform_frames(base, n, fs, as_, cs, n_atoms, _ptr(transform), ldt, out.data_ptr() + 4 * off, ofs, oas, ocs,
+    check(_lib.load().dcv_transform_frames(base, n, fs, as_, cs, n_atoms, _ptr(transform), ldt, out_ptr, ofs, oas, ocs,
                                            _stream()), "dcv_transform_frames")
     return result
 
@@ -401,26 +394,13 @@ def xtc_decode(data: torch.Tensor, frames, n_atoms: int, scale: float = 10.0, ou
     n, n_atoms = int(frames.size), int(n_atoms)
     if n_atoms < 1:
         raise DcvError(f"xtc_decode: {n_atoms} atoms")
-    if (out is None) != (out_strides is None):
-        raise DcvError("xtc_decode: out and out_strides go together")
-    if out is None:
-        out = result = torch.empty(n, n_atoms, 3, dtype=torch.float32, device=data.device)
-        off, ofs, oas, ocs = 0, 3 * n_atoms, 3, 1
-    else:
-        result = out
-        off, ofs, oas, ocs = (int(v) for v in out_strides)
-        if out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous() or out.device != data.device:
-            raise DcvError("xtc_decode: out must be a contiguous 1-D float32 buffer on the device of the bytes")
-        last = off + max(n - 1, 0) * ofs + (n_atoms - 1) * oas + 2 * ocs
-        if off < 0 or min(ofs, oas, ocs) < 1 or (n > 0 and last >= out.numel()):
-            raise DcvError(f"xtc_decode: output layout {tuple(out_strides)} with {n_atoms} atoms and {n} frames reaches element "
-                           f"{last} of a buffer of {out.numel()} (strides must be >= 1)")
+    result, out_ptr, ofs, oas, ocs = _output("xtc_decode", out, out_strides, n, n_atoms, data.device, source="bytes")
     status = torch.empty(n, dtype=torch.int32, device=data.device)
     if n == 0:
         return (result, status) if return_status else result   # an empty tensor has no data pointer to hand to the library
     lib = _lib.load()
     ws = _ws(lib.dcv_xtc_decode_workspace(n), data.device)
-    check(lib.dcv_xtc_decode(data.data_ptr(), data.numel(), frames.ctypes.data, n, n_atoms, float(scale), out.data_ptr() + 4 * off, ofs, oas, ocs,
+    check(lib.dcv_xtc_decode(data.data_ptr(), data.numel(), frames.ctypes.data, n, n_atoms, float(scale), out_ptr, ofs, oas, ocs,
                              _ptr(status), _ptr(ws), ws.numel(), _stream()), "dcv_xtc_decode")
     if return_status:
         return result, status

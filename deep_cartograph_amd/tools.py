@@ -30,8 +30,25 @@ def _as_list(x):
     return [x] if isinstance(x, str) else list(x)
 
 
+def _one_topology_each(trajectories: List[str], topologies) -> List[str]:
+    """The topologies as a list, a single one repeated for every trajectory."""
+    topologies = _as_list(topologies) or []
+    return topologies * len(trajectories) if len(topologies) == 1 else topologies
+
+
+def _pair_topologies(trajectories: List[str], topologies, others=(), must_exist: bool = True) -> List[str]:
+    """One topology per trajectory (one serves all, or one each); with `must_exist` every path given, `others` included,
+    is checked (traj_projection leaves that to the calculator, behind its restart check)."""
+    topologies = _one_topology_each(trajectories, topologies)
+    if len(trajectories) != len(topologies):
+        raise ValueError(f"Number of trajectories ({len(trajectories)}) and topologies ({len(topologies)}) do not match.")
+    for path in (trajectories + topologies + [p for p in others if p]) if must_exist else []:
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"File not found: {path}")
+    return topologies
+
+
 ANGSTROM_TO_NM = 0.1   # PLUMED's length unit
-DEFAULT_CHUNK_BYTES = 4 << 30   # default upper limit of a compute_features chunk (device bytes; the same again on the host)
 
 
 def import_trajectories(trajectories: Union[str, List[str]], output_folder: str, traj_format: Literal["dcd", "npy"] = "dcd", traj_stride: int = 1,
@@ -69,22 +86,15 @@ def compute_features(configuration: Dict, trajectory_data: Union[str, List[str]]
     into a memory-mapped .npy, so neither side ever holds a whole matrix twice.  No CPU fallback."""
     import torch
 
-    from . import hip, trajectory
+    from . import frame_io, hip, trajectory
     from ._lib import DcvError
     from .colvars import write_colvars
 
     t0 = time.time()
     trajectories = _route_xtc(_as_list(trajectory_data) or [], output_folder, memory_budget)
-    topologies = _as_list(topology_data) or []
     if not trajectories:
         raise ValueError("compute_features: no trajectories given")
-    if len(topologies) == 1:
-        topologies = topologies * len(trajectories)
-    if len(trajectories) != len(topologies):
-        raise ValueError(f"Number of trajectories ({len(trajectories)}) and topologies ({len(topologies)}) do not match.")
-    for path in trajectories + topologies + ([reference_topology] if reference_topology else []):
-        if not os.path.exists(path):
-            raise FileNotFoundError(f"File not found: {path}")
+    topologies = _pair_topologies(trajectories, topology_data, [reference_topology])
     os.makedirs(output_folder, exist_ok=True)
     configuration = validate_configuration(configuration or {}, ComputeFeaturesSchema, output_folder)
     binary = configuration["colvars_format"] == "npy"
@@ -99,9 +109,7 @@ def compute_features(configuration: Dict, trajectory_data: Union[str, List[str]]
         raise ValueError(f"traj_stride must be at least 1, got {stride}")
     features_configuration = configuration["plumed_settings"]["features"]
     ref_names, _ = trajectory.feature_definitions(features_configuration, trajectory.read_topology(reference_topology or topologies[0]))
-    if memory_budget is None:
-        # every chunk also exists once as a pageable host copy on its way up, so the default is capped for the host's sake
-        memory_budget = min(torch.cuda.mem_get_info()[0] // 4, DEFAULT_CHUNK_BYTES)
+    memory_budget = frame_io.resolve_budget(memory_budget)
     for traj_path, top_path, out_path in zip(trajectories, topologies, colvars_paths):
         if os.path.exists(out_path):
             logger.info(f"Skipping {Path(traj_path).stem}. Colvars file already exists.")
@@ -119,13 +127,9 @@ def compute_features(configuration: Dict, trajectory_data: Union[str, List[str]]
         # rows land in a memory-mapped .npy under a temporary name: an interrupted run leaves nothing a restart would take for done
         tmp_path = os.path.join(os.path.dirname(out_path), "colvars.partial.npy")
         rows = np.lib.format.open_memmap(tmp_path, mode="w+", dtype=np.float32, shape=(n, len(names)))
-        per_frame = 4 * (stride * traj.frame_stride + len(names))
-        chunk = int(max(1, min(n, memory_budget // per_frame)))
+        chunk, ranges = frame_io.plan_chunks(n, 4 * (stride * traj.frame_stride + len(names)), memory_budget)
         logger.info(f"Computing {len(names)} features of {n} frames of {Path(traj_path).name} in chunks of {chunk} frames")
-        for lo in range(0, n, chunk):
-            hi = min(n, lo + chunk)
-            span, layout = traj.span(lo * stride, (hi - 1) * stride + 1, stride)
-            buf = torch.from_numpy(np.array(span, dtype=np.float32)).cuda()
+        for lo, hi, buf, layout in frame_io.stream(traj, ranges, stride):
             block = hip.featurize(buf, defs, top.n_atoms, strides=layout, unit=ANGSTROM_TO_NM).cpu().numpy()
             if np.isnan(block).any():
                 raise ValueError(f"NaNs in the features of frames {lo * stride}..{(hi - 1) * stride} of {traj_path}: check the coordinates")
@@ -164,15 +168,9 @@ def analyze_geometry(configuration: Dict, trajectories: List[str], topologies: L
     from ._lib import DcvError
 
     t0 = time.time()
-    trajectories, topologies = _route_xtc(_as_list(trajectories) or [], output_folder, memory_budget), _as_list(topologies) or []
+    trajectories = _route_xtc(_as_list(trajectories) or [], output_folder, memory_budget)
     ref_topologies = _as_list(ref_topologies)
-    if len(topologies) == 1:
-        topologies = topologies * len(trajectories)
-    if len(trajectories) != len(topologies):
-        raise ValueError(f"Number of trajectories ({len(trajectories)}) and topologies ({len(topologies)}) do not match.")
-    for path in trajectories + topologies + (ref_topologies or []):
-        if not os.path.exists(path):
-            raise FileNotFoundError(f"File not found: {path}")
+    topologies = _pair_topologies(trajectories, topologies, ref_topologies or [])
     os.makedirs(output_folder, exist_ok=True)
     configuration = validate_configuration(configuration or {}, AnalyzeGeometrySchema, output_folder)
     written: Dict[str, str] = {}
@@ -222,14 +220,8 @@ def traj_augmentation(configuration: Dict, trajectories: Union[str, List[str]], 
     from . import augmentation
 
     t0 = time.time()
-    trajectories, topologies = _route_xtc(_as_list(trajectories) or [], output_folder, memory_budget), _as_list(topologies) or []
-    if len(topologies) == 1:
-        topologies = topologies * len(trajectories)
-    if len(trajectories) != len(topologies):
-        raise ValueError(f"Number of trajectories ({len(trajectories)}) and topologies ({len(topologies)}) do not match.")
-    for path in trajectories + topologies:
-        if not os.path.exists(path):
-            raise FileNotFoundError(f"File not found: {path}")
+    trajectories = _route_xtc(_as_list(trajectories) or [], output_folder, memory_budget)
+    topologies = _pair_topologies(trajectories, topologies)
     os.makedirs(output_folder, exist_ok=True)
     configuration = validate_configuration(configuration or {}, TrajAugmentationSchema, output_folder)
     augmented_trajectories, augmented_topologies = [], []
@@ -270,20 +262,14 @@ def align_trajectories(trajectory_data: Union[str, List[str]], topology_data: Un
     from ._lib import DcvError
 
     t0 = time.time()
-    trajectories, topologies = _route_xtc(_as_list(trajectory_data) or [], output_folder, memory_budget), _as_list(topology_data) or []
+    trajectories = _route_xtc(_as_list(trajectory_data) or [], output_folder, memory_budget)
     if not trajectories:
         logger.warning("No trajectories provided. Nothing to align.")
         return [], []
-    if len(topologies) == 1:
-        topologies = topologies * len(trajectories)
-    if len(trajectories) != len(topologies):
-        raise ValueError(f"Number of trajectories ({len(trajectories)}) and topologies ({len(topologies)}) do not match.")
+    topologies = _pair_topologies(trajectories, topology_data, [ref_topology])
     if ref_topology is None:
         ref_topology = topologies[0]
         logger.info(f"No reference topology provided. Using first topology as reference: {Path(ref_topology).name}")
-    for path in trajectories + topologies + [ref_topology]:
-        if not os.path.exists(path):
-            raise FileNotFoundError(f"File not found: {path}")
     out_trajs = [os.path.join(output_folder, Path(t).name) for t in trajectories]
     out_tops = [os.path.join(output_folder, Path(t).stem + ".pdb") for t in topologies]
     for src, dst in zip(trajectories, out_trajs):
@@ -425,13 +411,9 @@ def traj_projection(configuration: Dict, colvars_paths: List[str], topologies: L
 
         from ._lib import DcvError
 
-        topologies = _as_list(topologies) or []
         if colvars_paths:
             raise ValueError("traj_projection: give either colvars_paths or trajectories, not both")
-        if len(topologies) == 1:
-            topologies = topologies * len(trajectories)
-        if len(trajectories) != len(topologies):
-            raise ValueError(f"Number of trajectories ({len(trajectories)}) and topologies ({len(topologies)}) do not match.")
+        topologies = _pair_topologies(trajectories, topologies, must_exist=False)
         if not torch.cuda.is_available():
             raise DcvError("traj_projection of trajectories needs an MI355X (cuda) device: the features are computed by libdcv.so, "
                            "there is no CPU fallback")
@@ -512,8 +494,7 @@ def traj_cluster(configuration: Dict, cv_traj_paths: Union[str, List[str]], traj
     trajectories, topologies = _as_list(trajectories), _as_list(topologies)
     extract = configuration["output_structures"] in ("centroids", "all") and bool(trajectories) and bool(topologies)
     if extract:
-        if len(topologies) == 1:
-            topologies = topologies * len(trajectories)
+        topologies = _one_topology_each(trajectories, topologies)   # the count error below names the CV trajectories too
         if len(trajectories) != len(cv_traj_paths) or len(topologies) != len(trajectories):
             raise ValueError(f"traj_cluster: {len(trajectories)} trajectories and {len(topologies)} topologies for {len(cv_traj_paths)} "
                              "CV trajectories (one topology for all, or one per trajectory)")

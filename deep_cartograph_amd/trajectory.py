@@ -581,14 +581,12 @@ def extract_frames(trajectory_path: str, topology_path: str, frames, out_path: s
         raise ValueError(f"{trajectory_path}: frame {bad} asked for, the trajectory has frames 0 to {traj.n_frames - 1}")
     import torch
 
-    from . import hip
+    from . import frame_io, hip   # frame_io builds on this module
     from ._lib import DcvError
-    from .tools import DEFAULT_CHUNK_BYTES
 
     if not torch.cuda.is_available():
         raise DcvError("extract_frames needs an MI355X (cuda) device: XTC frames are encoded by libdcv.so, there is no CPU fallback")
-    if memory_budget is None:
-        memory_budget = min(torch.cuda.mem_get_info()[0] // 4, DEFAULT_CHUNK_BYTES)
+    memory_budget = frame_io.resolve_budget(memory_budget)
     A = traj.n_atoms
     out_bytes = 2 * (13 * A + 4) + 92 + 120 + 48 + 8 + 4   # slot and image, pack record, descriptor, index, status
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
@@ -596,7 +594,7 @@ def extract_frames(trajectory_path: str, topology_path: str, frames, out_path: s
         for lo, hi in extraction_chunks(frames, 4 * traj.frame_stride, out_bytes, int(memory_budget)):
             first, last = int(frames[lo]), int(frames[hi - 1])
             data, layout = traj.span(first, last + 1)
-            buf = torch.from_numpy(np.array(data)).cuda()
+            buf = frame_io.upload(data)
             try:
                 image = hip.xtc_encode(buf, A, strides=layout, frames=frames[lo:hi] - first, precision=precision, step=frames[lo:hi],
                                        time=frames[lo:hi].astype(np.float32))

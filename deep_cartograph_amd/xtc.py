@@ -20,7 +20,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import trajectory
+from . import frame_io, trajectory
 
 logger = logging.getLogger(__name__)
 
@@ -41,11 +41,8 @@ def import_trajectory(path: str, output_path: str, traj_stride: int = 1, memory_
 
     from . import hip
     from ._lib import DcvError
-    from .tools import DEFAULT_CHUNK_BYTES
 
-    ext = os.path.splitext(output_path)[1].lower()
-    if ext not in (".dcd", ".npy"):
-        raise ValueError(f"{output_path}: an imported trajectory is written as .dcd or .npy")
+    ext = frame_io.coordinate_format(output_path, "an imported trajectory")
     stride = int(traj_stride)
     if stride < 1:
         raise ValueError(f"traj_stride must be at least 1, got {stride}")
@@ -54,43 +51,25 @@ def import_trajectory(path: str, output_path: str, traj_stride: int = 1, memory_
         raise DcvError("import_trajectories needs an MI355X (cuda) device: XTC frames are decoded by libdcv.so, there is no CPU fallback")
     frames = np.arange(0, index.n_frames, stride, dtype=np.int64)
     n, A = int(frames.size), index.n_atoms
-    if memory_budget is None:
-        memory_budget = min(torch.cuda.mem_get_info()[0] // 4, DEFAULT_CHUNK_BYTES)
     words = 3 * (A + 2) if ext == ".dcd" else 3 * A
     # a chunk holds the file bytes from its first to its last frame (skipped frames included), its descriptors, status words
     # and decoded image; sized by the mean frame, the longest chunk of a file whose frames differ in size is a little larger
     per_frame = stride * int(np.ceil((index.offset[-1] + index.frame_bytes()[-1] - index.offset[0]) / index.n_frames)) + 48 + 4 + 4 * words
-    chunk = int(max(1, min(n, memory_budget // per_frame)))
+    chunk, ranges = frame_io.plan_chunks(n, per_frame, frame_io.resolve_budget(memory_budget))
     logger.info(f"Importing {n} frames of {A} atoms of {Path(path).name} in chunks of {chunk} frames")
     data = np.memmap(path, dtype=np.uint8, mode="r")
     os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
-    tmp_path = output_path + ".partial"
-    writer = trajectory.write_dcd(tmp_path, A) if ext == ".dcd" else None
-    rows = None if writer else np.lib.format.open_memmap(tmp_path, mode="w+", dtype=np.float32, shape=(n, A, 3))
-    for lo in range(0, n, chunk):
-        hi = min(n, lo + chunk)
-        first, last, desc = index.span(frames[lo:hi])
-        buf = torch.from_numpy(np.array(data[first:last])).cuda()
-        try:
-            if writer:
-                image = torch.zeros((hi - lo) * writer.frame_words, dtype=torch.float32, device="cuda")
-                hip.xtc_decode(buf, desc, A, NM_TO_ANGSTROM, out=image, out_strides=writer.layout())
-                writer.append(image.cpu().numpy())   # the kernel writes the planes, the host the record markers
-            else:
-                rows[lo:hi] = hip.xtc_decode(buf, desc, A, NM_TO_ANGSTROM).cpu().numpy()
-        except DcvError as e:   # a corrupt frame: nothing is left behind that a restart could take for done
-            if writer:
-                writer.__exit__(DcvError, e, None)
-            rows = None
-            os.remove(tmp_path)
-            raise DcvError(f"{path}: frames {int(frames[lo])}..{int(frames[hi - 1])} (every {stride}): {e}") from None
-        del buf
-    if writer:
-        writer.close()
-    else:
-        rows.flush()
-        del rows
-    os.replace(tmp_path, output_path)
+    with frame_io.CoordinateSink(output_path, n, A) as sink:
+        for lo, hi in ranges:
+            first, last, desc = index.span(frames[lo:hi])
+            buf = torch.from_numpy(np.array(data[first:last])).cuda()
+            image = sink.image(hi - lo)
+            try:
+                hip.xtc_decode(buf, desc, A, NM_TO_ANGSTROM, out=image, out_strides=sink.layout())
+            except DcvError as e:   # a corrupt frame: the sink leaves nothing behind that a restart could take for done
+                raise DcvError(f"{path}: frames {int(frames[lo])}..{int(frames[hi - 1])} (every {stride}): {e}") from None
+            sink.append(image)
+            del buf, image
     return output_path
 
 
