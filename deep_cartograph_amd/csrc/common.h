@@ -27,6 +27,15 @@ void set_error(const char* fmt, ...);
         }                                                                                \
     } while (0)
 
+// the workspace of `entry` (its name, a string literal) holds `need` bytes; callers put their own conditions around it
+#define DCV_REQUIRE_WORKSPACE(entry, ws_d, ws_bytes, need)                                \
+    do {                                                                                 \
+        if (!(ws_d) || (ws_bytes) < (need)) {                                            \
+            dcv::set_error(entry ": workspace too small (%zu bytes, need %zu)", (size_t)(ws_bytes), (size_t)(need)); \
+            return DCV_ENOMEM;                                                           \
+        }                                                                                \
+    } while (0)
+
 #define DCV_CHECK_LAUNCH() DCV_CHECK_HIP(hipGetLastError())
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }

@@ -86,16 +86,16 @@ extern "C" int dcv_featurize(const float* xyz_d, int64_t n_frames, int64_t frame
         DCV_REQUIRE(r[5] >= 0 && (int64_t)r[5] + nc <= ldo, "dcv_featurize: record %d writes column %d (+%d), outside ldo = %lld", d, r[5],
                     nc - 1, (long long)ldo);
     }
-    if (!ws_d || ws_bytes < dcv_featurize_workspace(n_frames, n_atoms, n_defs)) {
-        set_error("dcv_featurize: workspace too small (%zu bytes, need %zu)", ws_bytes, dcv_featurize_workspace(n_frames, n_atoms, n_defs));
-        return DCV_ENOMEM;
-    }
+    DCV_REQUIRE_WORKSPACE("dcv_featurize", ws_d, ws_bytes, dcv_featurize_workspace(n_frames, n_atoms, n_defs));
     if (n_frames == 0) return DCV_OK;
+    const CoordStrides in{frame_stride, atom_stride, comp_stride};
+    int64_t in_last;
+    DCV_REQUIRE_COORDS_FIT("dcv_featurize", coord_extent(n_frames, n_atoms, in, in_last), n_frames, n_atoms);
 
     // ---- the atoms to stage and their LDS slots
     FeatArgs a{};
     StagePlan plan;
-    stage_plan(is_used, n_atoms, atom_stride, comp_stride, a.st, plan);
+    stage_plan(is_used, n_atoms, in, a.st, plan);
     const std::vector<int32_t>&used = plan.used, &slot = plan.slot;
     const int64_t per_frame = plan.per_frame;
     DCV_REQUIRE_STAGE_FITS("dcv_featurize", per_frame);
@@ -119,7 +119,7 @@ extern "C" int dcv_featurize(const float* xyz_d, int64_t n_frames, int64_t frame
     DCV_CHECK_HIP(hipMemcpyAsync(defs_d, rec.data(), rec.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     DCV_CHECK_HIP(hipMemcpyAsync(used_d, used.data(), used.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
 
-    stage_source(a.st, xyz_d, frame_stride, atom_stride, comp_stride, n_frames, used_d);
+    stage_source(a.st, xyz_d, in, n_frames, used_d);
     a.defs = defs_d;
     a.n_defs = n_defs;
     a.unit = unit;

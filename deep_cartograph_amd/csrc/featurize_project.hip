@@ -310,14 +310,14 @@ extern "C" int dcv_featurize_project(const float* xyz_d, int64_t n_frames, int64
 
     FpArgs a{};
     StagePlan plan;
-    stage_plan(is_used, n_atoms, atom_stride, comp_stride, a.st, plan);
+    const CoordStrides in{frame_stride, atom_stride, comp_stride};
+    stage_plan(is_used, n_atoms, in, a.st, plan);
     DCV_REQUIRE_STAGE_FITS("dcv_featurize_project", plan.per_frame);
     const FpWorkspace w = fp_workspace(n_atoms, n_rec, F);
-    if (!ws_d || ws_bytes < w.total) {
-        set_error("dcv_featurize_project: workspace too small (%zu bytes, need %zu)", ws_bytes, w.total);
-        return DCV_ENOMEM;
-    }
+    DCV_REQUIRE_WORKSPACE("dcv_featurize_project", ws_d, ws_bytes, w.total);
     if (n_frames == 0) return DCV_OK;
+    int64_t in_last;
+    DCV_REQUIRE_COORDS_FIT("dcv_featurize_project", coord_extent(n_frames, n_atoms, in, in_last), n_frames, n_atoms);
 
     const int D = d <= 2 ? 2 : d <= 4 ? 4 : d <= 8 ? 8 : 16;
     const int64_t fixed = (int64_t)kFpSlab * D * sizeof(float), per = (plan.per_frame + kFpSlabRow) * (int64_t)sizeof(float);
@@ -359,7 +359,7 @@ extern "C" int dcv_featurize_project(const float* xyz_d, int64_t n_frames, int64
                        gmean, grange);
     DCV_CHECK_LAUNCH();
 
-    stage_source(a.st, xyz_d, frame_stride, atom_stride, comp_stride, n_frames, reinterpret_cast<const int32_t*>(ws + w.used));
+    stage_source(a.st, xyz_d, in, n_frames, reinterpret_cast<const int32_t*>(ws + w.used));
     a.recs = reinterpret_cast<const int32_t*>(ws + w.recs);
     a.pass = reinterpret_cast<const int32_t*>(ws + w.pass);
     a.n_pass = (int32_t)fp.pass.size() / 2 - 1;

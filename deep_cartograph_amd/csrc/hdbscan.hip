@@ -182,7 +182,7 @@ extern "C" int dcv_core_distances(const double* P_d, int64_t n, int32_t d, int32
     DCV_REQUIRE(d >= 1 && d <= kHdMaxD, "dcv_core_distances: d = %d, supported 1..%d", d, kHdMaxD);
     DCV_REQUIRE(k >= 1 && k <= kHdMaxK && k <= n, "dcv_core_distances: k = %d, supported 1..min(n, %d)", k, kHdMaxK);
     DCV_REQUIRE(P_d && core_d, "dcv_core_distances: null points or result");
-    DCV_REQUIRE_WORKSPACE("dcv_core_distances", ws_d, ws_bytes, kCoreWsBytes);
+    DCV_REQUIRE_POINTS_WORKSPACE("dcv_core_distances", ws_d, ws_bytes, kCoreWsBytes);
     hipStream_t s = as_stream(stream);
     int32_t* status = static_cast<int32_t*>(ws_d);
     DCV_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
@@ -208,7 +208,7 @@ extern "C" int dcv_mr_mst(const double* P_d, int64_t n, int32_t d, const double*
     DCV_REQUIRE(n >= 2 && n <= kHdMaxN, "dcv_mr_mst: n = %lld, supported 2..%lld", (long long)n, (long long)kHdMaxN);
     DCV_REQUIRE(d >= 1 && d <= kHdMaxD, "dcv_mr_mst: d = %d, supported 1..%d", d, kHdMaxD);
     DCV_REQUIRE(P_d && core_d && src_h && dst_h && w_h, "dcv_mr_mst: null points, core distances or result");
-    DCV_REQUIRE_WORKSPACE("dcv_mr_mst", ws_d, ws_bytes, dcv_mr_mst_workspace(n, d));
+    DCV_REQUIRE_POINTS_WORKSPACE("dcv_mr_mst", ws_d, ws_bytes, dcv_mr_mst_workspace(n, d));
     DCV_REQUIRE((reinterpret_cast<uintptr_t>(ws_d) & 7) == 0, "dcv_mr_mst: workspace not 8-byte aligned");
     hipStream_t s = as_stream(stream);
     const MstLayout L(n, num_cus());

@@ -22,8 +22,7 @@
 #include <cmath>
 #include <vector>
 
-#include "common.h"
-#include "stage.h"   // DCV_REQUIRE_COORD_STRIDES
+#include "coords.h"
 
 namespace dcv {
 
@@ -35,7 +34,8 @@ constexpr int kInterpGroup = 4;                        // times per group of sca
 
 struct InterpArgs {
     const float* xyz;
-    int64_t n_knots, frame_stride, atom_stride, comp_stride;
+    int64_t n_knots;
+    CoordStrides in;
     const int32_t* sel;        // n_sel atoms or NULL (atom s is atom s)
     int64_t n_sel, n_cols;     // n_cols = 3 n_sel
     int32_t comp_fast;         // column q is (atom q / 3, component q % 3); otherwise (atom q % n_sel, component q / n_sel)
@@ -44,7 +44,7 @@ struct InterpArgs {
     int64_t n_out;
     const double* noise;       // n_out x n_sel x 3 or NULL
     float* out;
-    int64_t out_frame_stride, out_atom_stride, out_comp_stride;
+    CoordStrides outs;         // of the output
     int64_t runs, run_len, n_tasks;   // a task = (column block, run); runs of run_len outputs (knots in the G pass)
     double* partials;          // G pass: one maximum per task
     const double* G;           // evaluation: the reduced maximum (makima)
@@ -62,15 +62,15 @@ __device__ __forceinline__ InterpColumn interp_column(const InterpArgs& a, int64
     else { c = q / a.n_sel; s = q - c * a.n_sel; }
     const int64_t atom = a.sel ? (int64_t)a.sel[s] : s;
     InterpColumn col;
-    col.in = a.xyz + atom * a.atom_stride + c * a.comp_stride;
-    col.out = a.out ? a.out + s * a.out_atom_stride + c * a.out_comp_stride : nullptr;
+    col.in = a.xyz + atom * a.in.a + c * a.in.c;
+    col.out = a.out ? a.out + s * a.outs.a + c * a.outs.c : nullptr;
     col.noise = a.noise ? a.noise + 3 * s + c : nullptr;
     return col;
 }
 
 // knot k of a column, 0 outside the trajectory (such a value is never used: the end rules replace what it feeds)
 __device__ __forceinline__ float interp_knot(const InterpArgs& a, const float* col, int64_t k) {
-    return k >= 0 && k < a.n_knots ? col[k * a.frame_stride] : 0.0f;
+    return k >= 0 && k < a.n_knots ? col[k * a.in.f] : 0.0f;
 }
 
 __device__ __forceinline__ void interp_window(const InterpArgs& a, const float* col, int64_t K, double (&w)[6], float& nxt) {
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(kInterpThreads) void interp_kernel(const InterpArgs
             if (s == 1.0 && p == p) p = y1;   // the last knot is the right end of its piece
             if (!a.extrapolate && (t < 0.0 || t > last)) p = __builtin_nan("");
             if (col.noise) p += col.noise[j * a.n_cols];
-            col.out[j * a.out_frame_stride] = (float)p;
+            col.out[j * a.outs.f] = (float)p;
         }
     }
 }
@@ -327,9 +327,8 @@ extern "C" int dcv_interpolate(const float* xyz_d, int64_t n_knots, int64_t fram
                 kind == DCV_INTERP_MAKIMA ? "makima" : "pchip", kind == DCV_INTERP_MAKIMA ? 3 : 2);
     DCV_REQUIRE(!sel_h || n_sel >= 1, "dcv_interpolate: a selection of %d atoms", n_sel);
     DCV_REQUIRE_COORD_STRIDES("dcv_interpolate", frame_stride, atom_stride, comp_stride);
-    DCV_REQUIRE(out_frame_stride >= 1 && out_atom_stride >= 1 && out_comp_stride >= 1,
-                "dcv_interpolate: output strides (%lld, %lld, %lld) must all be >= 1", (long long)out_frame_stride,
-                (long long)out_atom_stride, (long long)out_comp_stride);
+    const CoordStrides in{frame_stride, atom_stride, comp_stride}, outs{out_frame_stride, out_atom_stride, out_comp_stride};
+    DCV_REQUIRE_STRIDES_GE1("dcv_interpolate", "output strides", outs);
     if (sel_h)
         for (int32_t i = 0; i < n_sel; ++i)
             DCV_REQUIRE(sel_h[i] >= 0 && sel_h[i] < n_atoms, "dcv_interpolate: selected atom %d is %d, outside [0, %d)", i, sel_h[i], n_atoms);
@@ -341,11 +340,11 @@ extern "C" int dcv_interpolate(const float* xyz_d, int64_t n_knots, int64_t fram
     const InterpPlan p = interp_plan(n_knots, n_atoms, sel_h ? n_sel : 0, n_out);
     DCV_REQUIRE(cdiv(p.n_tasks, kInterpWaves) <= 0x7fffffffLL && cdiv(p.k_tasks, kInterpWaves) <= 0x7fffffffLL,
                 "dcv_interpolate: %lld columns x %lld frames need more than 2^31 - 1 workgroups", (long long)p.n_cols, (long long)n_out);
-    if (!ws_d || ws_bytes < p.total) {
-        set_error("dcv_interpolate: workspace too small (%zu bytes, need %zu)", ws_bytes, p.total);
-        return DCV_ENOMEM;
-    }
+    DCV_REQUIRE_WORKSPACE("dcv_interpolate", ws_d, ws_bytes, p.total);
     if (n_out == 0) return DCV_OK;
+    int64_t in_last, out_last;
+    DCV_REQUIRE_COORDS_FIT("dcv_interpolate", coord_extent(n_knots, n_atoms, in, in_last), n_knots, n_atoms);
+    DCV_REQUIRE_COORDS_FIT("dcv_interpolate", coord_extent(n_out, p.n_sel, outs, out_last), n_out, (int)p.n_sel);
 
     hipStream_t s = as_stream(stream);
     char* ws = static_cast<char*>(ws_d);
@@ -355,18 +354,18 @@ extern "C" int dcv_interpolate(const float* xyz_d, int64_t n_knots, int64_t fram
 
     InterpArgs a{};
     a.xyz = xyz_d;
-    a.n_knots = n_knots; a.frame_stride = frame_stride; a.atom_stride = atom_stride; a.comp_stride = comp_stride;
+    a.n_knots = n_knots; a.in = in;
     a.sel = sel_h ? reinterpret_cast<const int32_t*>(ws + p.sel) : nullptr;
     a.n_sel = p.n_sel; a.n_cols = p.n_cols;
     // lanes along consecutive addresses of the output; with noise along those of the noise, which is twice the bytes (a
     // wave then writes DCD planes as three pieces of 21 or 22 atoms: measured faster than reading every third double)
-    a.comp_fast = out_comp_stride < out_atom_stride || noise_d != nullptr;
+    a.comp_fast = coord_comp_fast(outs) || noise_d != nullptr;
     a.extrapolate = extrapolate;
     a.t = reinterpret_cast<const double*>(ws + p.t);
     a.n_out = n_out;
     a.noise = noise_d;
     a.out = out_d;
-    a.out_frame_stride = out_frame_stride; a.out_atom_stride = out_atom_stride; a.out_comp_stride = out_comp_stride;
+    a.outs = outs;
     a.partials = reinterpret_cast<double*>(ws + p.partials);
     a.G = reinterpret_cast<const double*>(ws + p.G);
     if (kind == DCV_INTERP_MAKIMA) {

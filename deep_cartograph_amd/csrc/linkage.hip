@@ -255,7 +255,7 @@ extern "C" size_t dcv_linkage_workspace(int64_t n, int32_t d) {
 // the matrix fill alone, into a workspace laid out as dcv_linkage lays it out (tools/linkage_bench.py times it)
 extern "C" int dcv_linkage_pdist(const double* P_d, int64_t n, int32_t d, void* ws_d, size_t ws_bytes, void* stream) {
     DCV_REQUIRE(n >= 2 && n <= kLkMaxN && d >= 1 && d <= kLkMaxD && P_d, "dcv_linkage_pdist: bad arguments (n=%lld d=%d)", (long long)n, d);
-    DCV_REQUIRE_WORKSPACE("dcv_linkage_pdist", ws_d, ws_bytes, dcv_linkage_workspace(n, d));
+    DCV_REQUIRE_POINTS_WORKSPACE("dcv_linkage_pdist", ws_d, ws_bytes, dcv_linkage_workspace(n, d));
     const LinkLayout L(n, kLkThreads);
     const int col_blocks = (int)cdiv(n, kLkSlice);
     const int64_t pd_blocks = cdiv(n, kLkPdRows) * col_blocks;
@@ -273,7 +273,7 @@ extern "C" int dcv_linkage(const double* P_d, int64_t n, int32_t d, int32_t meth
     DCV_REQUIRE(method == kLkComplete || method == kLkAverage || method == kLkWard,
                 "dcv_linkage: method %d (0 complete, 1 average, 2 ward)", method);
     DCV_REQUIRE(P_d && Z_h, "dcv_linkage: null points or result");
-    DCV_REQUIRE_WORKSPACE("dcv_linkage", ws_d, ws_bytes, dcv_linkage_workspace(n, d));
+    DCV_REQUIRE_POINTS_WORKSPACE("dcv_linkage", ws_d, ws_bytes, dcv_linkage_workspace(n, d));
     DCV_REQUIRE((reinterpret_cast<uintptr_t>(ws_d) & 15) == 0, "dcv_linkage: workspace not 16-byte aligned");
     hipStream_t s = as_stream(stream);
     const LinkLayout L(n, num_cus());

@@ -226,8 +226,9 @@ inline StepGrid step_grid(int64_t len, int quantum, int cus) {
     return g;
 }
 
-// refuses a missing or short workspace: "<entry>: workspace of X bytes, Y needed", DCV_ENOMEM
-#define DCV_REQUIRE_WORKSPACE(entry, ws, bytes, needed)                                                            \
+// refuses a missing or short workspace: "<entry>: workspace of X bytes, Y needed", DCV_ENOMEM (the text of the clustering
+// entries; common.h's DCV_REQUIRE_WORKSPACE says "workspace too small (X bytes, need Y)")
+#define DCV_REQUIRE_POINTS_WORKSPACE(entry, ws, bytes, needed)                                                     \
     do {                                                                                                           \
         const size_t _need = (needed);                                                                             \
         if (!(ws) || (bytes) < _need) {                                                                            \

@@ -10,11 +10,12 @@
 //   GATHER  everything else (any strides, a sparse subset of an all-atom trajectory): one 4-byte load per coordinate
 //           of a used atom, lanes along the sorted list of used atoms, nothing else is read.
 // In LDS, coordinate c of the atom in slot s of frame f of the tile is lds[f * lfs + s * las + c * lcs].
-// The 16-byte load is stream.h's.  The host preamble the coordinate entries share is at the end: the stride requirement
-// (dcv_interpolate's too), the refusal of a frame that LDS cannot hold, and the source fields of StageArgs.
+// The 16-byte load is stream.h's; strides, layout forms and the stride requirement are coords.h's.  The host preamble of
+// the staging entries is at the end: the refusal of a frame that LDS cannot hold and the source fields of StageArgs.
 #pragma once
 #include <vector>
 
+#include "coords.h"
 #include "stream.h"
 
 namespace dcv {
@@ -26,7 +27,7 @@ constexpr int kStageLdsMax = 64 * 1024;      // one frame of the needed atoms mu
 
 struct StageArgs {
     const float* xyz;
-    int64_t frame_stride, atom_stride, comp_stride;
+    CoordStrides in;
     int64_t n_frames;
     const int32_t* used;   // GATHER: the nu used atoms, ascending
     int32_t nu;
@@ -34,7 +35,7 @@ struct StageArgs {
     int32_t rpf;           // ROWS: rows per frame (3 planes, or 1 dense row)
     int32_t L;             // ROWS: floats per row
     int64_t row_off;       // ROWS: a_lo * atom_stride
-    int32_t comp_fast;     // GATHER: the component runs fastest over the lanes (comp_stride < atom_stride)
+    int32_t comp_fast;     // GATHER: the component runs fastest over the lanes (coord_comp_fast)
     int32_t lfs, las, lcs; // LDS strides of frame, atom slot, component
     int32_t tile;          // frames per workgroup
 };
@@ -59,7 +60,7 @@ __device__ __forceinline__ void stage_rows(const StageArgs& a, int64_t f0, int n
             if (i >= total) continue;
             const int row = i / nsmax, k = i - row * nsmax;
             const int f = row / a.rpf, c = row - f * a.rpf;
-            g[u] = a.xyz + (f0 + f) * a.frame_stride + (int64_t)c * a.comp_stride + a.row_off;
+            g[u] = a.xyz + (f0 + f) * a.in.f + (int64_t)c * a.in.c + a.row_off;
             l[u] = lds + row * a.L;
             const int m = (int)((reinterpret_cast<uintptr_t>(g[u]) >> 2) & 3);
             const int j = 4 * k - m;
@@ -91,7 +92,7 @@ __device__ __forceinline__ void stage_gather(const StageArgs& a, int64_t f0, int
         int c, u;
         if (a.comp_fast) { u = r / 3; c = r - u * 3; }
         else { c = r / a.nu; u = r - c * a.nu; }
-        const int64_t off = (f0 + f) * a.frame_stride + (int64_t)a.used[u] * a.atom_stride + (int64_t)c * a.comp_stride;
+        const int64_t off = (f0 + f) * a.in.f + (int64_t)a.used[u] * a.in.a + (int64_t)c * a.in.c;
         lds[f * per + c * a.nu + u] = a.xyz[off];
     }
 }
@@ -109,29 +110,28 @@ struct StagePlan {
 
 // Fills the staging fields of `a` (everything but xyz / strides / n_frames / used / tile) and `p` from the flags
 // is_used[n_atoms] (at least one set).  The caller checks per_frame against the LDS it has and picks the tile.
-inline void stage_plan(const std::vector<char>& is_used, int32_t n_atoms, int64_t atom_stride, int64_t comp_stride, StageArgs& a,
-                       StagePlan& p) {
+inline void stage_plan(const std::vector<char>& is_used, int32_t n_atoms, const CoordStrides& in, StageArgs& a, StagePlan& p) {
     p.used.clear();
     p.slot.assign((size_t)n_atoms, 0);
     for (int32_t i = 0; i < n_atoms; ++i)
         if (is_used[(size_t)i]) p.used.push_back(i);
     const int32_t nu = (int32_t)p.used.size(), a_lo = p.used.front(), a_hi = p.used.back();
     const int64_t range = (int64_t)a_hi - a_lo + 1;
-    const bool planes = atom_stride == 1, dense = comp_stride == 1 && atom_stride == 3;
+    const bool planes = coord_form(in) == kCoordPlanes;
     a.nu = nu;
-    a.rows = (planes || dense) && range <= 2 * (int64_t)nu;
+    a.rows = coord_form(in) != kCoordStrided && range <= 2 * (int64_t)nu;
     if (a.rows) {
         for (int32_t i = a_lo; i <= a_hi; ++i) p.slot[(size_t)i] = i - a_lo;
         p.per_frame = 3 * range;
         a.rpf = planes ? 3 : 1;
         a.L = (int32_t)(planes ? range : 3 * range);
-        a.row_off = (int64_t)a_lo * atom_stride;
+        a.row_off = (int64_t)a_lo * in.a;
         a.las = planes ? 1 : 3;
         a.lcs = planes ? (int32_t)range : 1;
     } else {
         for (int32_t u = 0; u < nu; ++u) p.slot[(size_t)p.used[(size_t)u]] = u;
         p.per_frame = 3 * (int64_t)nu;
-        a.comp_fast = comp_stride < atom_stride;
+        a.comp_fast = coord_comp_fast(in);
         a.las = 1;
         a.lcs = nu;
     }
@@ -146,19 +146,12 @@ inline int stage_tile_frames(int64_t per_frame, int64_t bytes_per_frame_extra, i
 }
 
 // where the coordinates come from: everything of `a` that stage_plan and the choice of the tile leave open
-inline void stage_source(StageArgs& a, const float* xyz, int64_t frame_stride, int64_t atom_stride, int64_t comp_stride, int64_t n_frames,
-                         const int32_t* used_d) {
+inline void stage_source(StageArgs& a, const float* xyz, const CoordStrides& in, int64_t n_frames, const int32_t* used_d) {
     a.xyz = xyz;
-    a.frame_stride = frame_stride; a.atom_stride = atom_stride; a.comp_stride = comp_stride;
+    a.in = in;
     a.n_frames = n_frames;
     a.used = used_d;
 }
-
-// the strides every coordinate entry accepts; `entry` is the entry's name, a string literal
-#define DCV_REQUIRE_COORD_STRIDES(entry, frame_stride, atom_stride, comp_stride)                                                  \
-    DCV_REQUIRE((frame_stride) >= 0 && (atom_stride) >= 1 && (comp_stride) >= 1,                                                  \
-                entry ": strides (%lld, %lld, %lld): the frame stride must be >= 0, the atom and component strides >= 1",         \
-                (long long)(frame_stride), (long long)(atom_stride), (long long)(comp_stride))
 
 // one frame of the staged atoms (StagePlan::per_frame floats) must fit the LDS of a workgroup
 #define DCV_REQUIRE_STAGE_FITS(entry, per_frame)                                                                                  \

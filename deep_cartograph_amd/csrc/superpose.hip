@@ -249,7 +249,8 @@ extern "C" int dcv_superpose(const float* xyz_d, int64_t n_frames, int64_t frame
     DCV_REQUIRE(wsum > 0.0 && std::isfinite(wsum), "dcv_superpose: the weights sum to %g: the sum must be positive", wsum);
     SupArgs a{};
     StagePlan plan;
-    stage_plan(is_used, n_atoms, atom_stride, comp_stride, a.st, plan);
+    const CoordStrides in{frame_stride, atom_stride, comp_stride};
+    stage_plan(is_used, n_atoms, in, a.st, plan);
     const int64_t per_frame = plan.per_frame;
     DCV_REQUIRE_STAGE_FITS("dcv_superpose", per_frame);
     const bool phase_b = aligned_d || moments_d;
@@ -262,11 +263,10 @@ extern "C" int dcv_superpose(const float* xyz_d, int64_t n_frames, int64_t frame
                 "dcv_superpose: %lld bytes of LDS (one frame of %lld staged atoms%s%s) exceed %d", (long long)lds_bytes, (long long)(per_frame / 3),
                 phase_b ? ", its transform" : "", moments_d ? " and 48 bytes of moments per selected atom" : "", kStageLdsMax);
     const SupLayout lay = sup_layout(n_frames, n_atoms, n_fit, n_sel);
-    if (!ws_d || ws_bytes < lay.total) {
-        set_error("dcv_superpose: workspace too small (%zu bytes, need %zu)", ws_bytes, lay.total);
-        return DCV_ENOMEM;
-    }
+    DCV_REQUIRE_WORKSPACE("dcv_superpose", ws_d, ws_bytes, lay.total);
     if (n_frames == 0) return DCV_OK;
+    int64_t in_last;
+    DCV_REQUIRE_COORDS_FIT("dcv_superpose", coord_extent(n_frames, n_atoms, in, in_last), n_frames, n_atoms);
 
     // ---- the reference, centred on its weighted centroid, and the LDS slots of both atom lists
     double cr[3] = {0.0, 0.0, 0.0};
@@ -291,7 +291,7 @@ extern "C" int dcv_superpose(const float* xyz_d, int64_t n_frames, int64_t frame
     if (sel_ref_h) DCV_CHECK_HIP(hipMemcpyAsync(ws + lay.sel_ref, sel_ref_h, (size_t)n_sel * 3 * sizeof(double), hipMemcpyHostToDevice, s));
     DCV_CHECK_HIP(hipMemcpyAsync(ws + lay.used, plan.used.data(), plan.used.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
 
-    stage_source(a.st, xyz_d, frame_stride, atom_stride, comp_stride, n_frames, reinterpret_cast<const int32_t*>(ws + lay.used));
+    stage_source(a.st, xyz_d, in, n_frames, reinterpret_cast<const int32_t*>(ws + lay.used));
     a.fit_slot = reinterpret_cast<const int32_t*>(ws + lay.fit_slot);
     a.fit_rec = reinterpret_cast<const double*>(ws + lay.fit_rec);
     a.sel_slot = reinterpret_cast<const int32_t*>(ws + lay.sel_slot);

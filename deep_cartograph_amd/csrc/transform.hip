@@ -32,14 +32,12 @@
 // lanes of (the lanes of the other frames masked off), one pass wherever the wave is inside one frame; loads and stores
 // are issued once, outside that loop.  No LDS, no atomics, no workspace; at most kXfMaxGroups workgroups stride over
 // the items.
-#include "common.h"
-#include "stage.h"   // DCV_REQUIRE_COORD_STRIDES
+#include "coords.h"
 
 namespace dcv {
 
 constexpr int kXfThreads = 256;
 constexpr int64_t kXfMaxGroups = 2048;   // 256 CUs x 8 workgroups
-enum XfForm { kXfStrided = 0, kXfPlanes = 1, kXfDense = 2 };
 
 // a 16-byte non-temporal access that is only promised 4-byte alignment
 typedef float xf_float4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -54,9 +52,9 @@ __device__ __forceinline__ void xf_store4(float* p, float a, float b, float c, f
 }
 
 struct XfArgs {   // the three pointers are kernel arguments of their own: __restrict__ there lets the transform rows take scalar loads
-    int64_t fs, as, cs;
+    CoordStrides in;
     int64_t ldt;
-    int64_t ofs, oas, ocs;
+    CoordStrides outs;
     int64_t n_frames, n_atoms;
     int64_t slots, total;   // groups per frame (worst alignment), n_frames * slots
     uint32_t x_word, out_word;   // the bases in floats, mod 4
@@ -67,16 +65,16 @@ struct XfArgs {   // the three pointers are kernel arguments of their own: __res
 template <int FORM>
 __device__ __forceinline__ int xf_shift(uint32_t base_word, int64_t f, int64_t frame_stride) {
     const int r = (int)((base_word + (uint32_t)f * (uint32_t)frame_stride) & 3u);
-    return FORM == kXfPlanes ? r : (3 * r) & 3;   // dense: element 3 (4k - m) of the row, and 3 . 3 = 1 (mod 4)
+    return FORM == kCoordPlanes ? r : (3 * r) & 3;   // dense: element 3 (4k - m) of the row, and 3 . 3 = 1 (mod 4)
 }
 
 // the coordinates of the four atoms [j, j + 4) of a frame that starts at `in`; `vec`: the group lies inside the row
 template <int IN>
 __device__ __forceinline__ void xf_load(const XfArgs& a, const float* in, int64_t j, bool vec, float (&v)[3][4]) {
-    if (vec && IN == kXfPlanes) {
+    if (vec && IN == kCoordPlanes) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) xf_load4(in + c * a.cs + j, v[c]);
-    } else if (vec && IN == kXfDense) {
+        for (int c = 0; c < 3; ++c) xf_load4(in + c * a.in.c + j, v[c]);
+    } else if (vec && IN == kCoordDense) {
         float q[3][4];
 #pragma unroll
         for (int i = 0; i < 3; ++i) xf_load4(in + 3 * j + 4 * i, q[i]);
@@ -89,16 +87,16 @@ __device__ __forceinline__ void xf_load(const XfArgs& a, const float* in, int64_
         for (int e = 0; e < 4; ++e)
 #pragma unroll
             for (int c = 0; c < 3; ++c)
-                v[c][e] = j + e >= 0 && j + e < a.n_atoms ? __builtin_nontemporal_load(in + (j + e) * a.as + c * a.cs) : 0.0f;
+                v[c][e] = j + e >= 0 && j + e < a.n_atoms ? __builtin_nontemporal_load(in + (j + e) * a.in.a + c * a.in.c) : 0.0f;
     }
 }
 
 template <int OUT>
 __device__ __forceinline__ void xf_store(const XfArgs& a, float* out, int64_t j, bool vec, const float (&o)[3][4]) {
-    if (vec && OUT == kXfPlanes) {
+    if (vec && OUT == kCoordPlanes) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) xf_store4(out + c * a.ocs + j, o[c][0], o[c][1], o[c][2], o[c][3]);
-    } else if (vec && OUT == kXfDense) {
+        for (int c = 0; c < 3; ++c) xf_store4(out + c * a.outs.c + j, o[c][0], o[c][1], o[c][2], o[c][3]);
+    } else if (vec && OUT == kCoordDense) {
         float* p = out + 3 * j;
         xf_store4(p, o[0][0], o[1][0], o[2][0], o[0][1]);
         xf_store4(p + 4, o[1][1], o[2][1], o[0][2], o[1][2]);
@@ -108,7 +106,7 @@ __device__ __forceinline__ void xf_store(const XfArgs& a, float* out, int64_t j,
         for (int e = 0; e < 4; ++e)
 #pragma unroll
             for (int c = 0; c < 3; ++c)
-                if (j + e >= 0 && j + e < a.n_atoms) __builtin_nontemporal_store(o[c][e], out + (j + e) * a.oas + c * a.ocs);
+                if (j + e >= 0 && j + e < a.n_atoms) __builtin_nontemporal_store(o[c][e], out + (j + e) * a.outs.a + c * a.outs.c);
     }
 }
 
@@ -147,8 +145,8 @@ __global__ __launch_bounds__(kXfThreads) void transform_frames_kernel(const XfAr
         const int64_t f = fb + q;
         if (f >= a.n_frames) continue;   // no barrier and no shuffle below
         int m = 0;
-        if (a.grid_on == 1) m = xf_shift<OUT>(a.out_word, f, a.ofs);
-        else if (a.grid_on == 2) m = xf_shift<IN>(a.x_word, f, a.fs);
+        if (a.grid_on == 1) m = xf_shift<OUT>(a.out_word, f, a.outs.f);
+        else if (a.grid_on == 2) m = xf_shift<IN>(a.x_word, f, a.in.f);
         int64_t j = 4 * (int64_t)k - m;
         if (j >= a.n_atoms) continue;
         // the ragged first and last group of a row move inside it: their lanes take the same 16-byte accesses as every other
@@ -161,7 +159,7 @@ __global__ __launch_bounds__(kXfThreads) void transform_frames_kernel(const XfAr
 #pragma unroll
         for (int i = 0; i < 15; ++i) t[i] = T[fc * a.ldt + i];
         float v[3][4], o[3][4];
-        xf_load<IN>(a, x + f * a.fs, j, vec, v);
+        xf_load<IN>(a, x + f * a.in.f, j, vec, v);
         for (;;) {
             if (f == fc) {
                 xf_apply(t, v, o);
@@ -171,28 +169,15 @@ __global__ __launch_bounds__(kXfThreads) void transform_frames_kernel(const XfAr
 #pragma unroll
             for (int i = 0; i < 15; ++i) t[i] = T[fc * a.ldt + i];
         }
-        xf_store<OUT>(a, out + f * a.ofs, j, vec, o);
+        xf_store<OUT>(a, out + f * a.outs.f, j, vec, o);
     }
-}
-
-static XfForm xf_form(int64_t atom_stride, int64_t comp_stride) {
-    return atom_stride == 1 ? kXfPlanes : (atom_stride == 3 && comp_stride == 1 ? kXfDense : kXfStrided);
-}
-
-// last element a layout reaches, false when that does not fit 62 bits
-static bool xf_extent(int64_t n_frames, int64_t n_atoms, int64_t fs, int64_t as, int64_t cs, int64_t& last) {
-    int64_t a, b, c;
-    if (__builtin_mul_overflow(n_frames - 1, fs, &a) || __builtin_mul_overflow(n_atoms - 1, as, &b) || __builtin_mul_overflow((int64_t)2, cs, &c))
-        return false;
-    if (__builtin_add_overflow(a, b, &last) || __builtin_add_overflow(last, c, &last)) return false;
-    return last < (int64_t)1 << 60;
 }
 
 template <int IN>
 static void xf_launch(int out_form, dim3 grid, hipStream_t s, const XfArgs& a, const float* x, const double* T, float* out) {
-    if (out_form == kXfPlanes) hipLaunchKernelGGL((transform_frames_kernel<IN, kXfPlanes>), grid, dim3(kXfThreads), 0, s, a, x, T, out);
-    else if (out_form == kXfDense) hipLaunchKernelGGL((transform_frames_kernel<IN, kXfDense>), grid, dim3(kXfThreads), 0, s, a, x, T, out);
-    else hipLaunchKernelGGL((transform_frames_kernel<IN, kXfStrided>), grid, dim3(kXfThreads), 0, s, a, x, T, out);
+    if (out_form == kCoordPlanes) hipLaunchKernelGGL((transform_frames_kernel<IN, kCoordPlanes>), grid, dim3(kXfThreads), 0, s, a, x, T, out);
+    else if (out_form == kCoordDense) hipLaunchKernelGGL((transform_frames_kernel<IN, kCoordDense>), grid, dim3(kXfThreads), 0, s, a, x, T, out);
+    else hipLaunchKernelGGL((transform_frames_kernel<IN, kCoordStrided>), grid, dim3(kXfThreads), 0, s, a, x, T, out);
 }
 
 }  // namespace dcv
@@ -206,48 +191,45 @@ extern "C" int dcv_transform_frames(const float* xyz_d, int64_t n_frames, int64_
     DCV_REQUIRE(xyz_d && transform_d && out_d && n_atoms > 0 && n_frames >= 0, "dcv_transform_frames: bad arguments (n_atoms=%d n_frames=%lld)",
                 n_atoms, (long long)n_frames);
     DCV_REQUIRE_COORD_STRIDES("dcv_transform_frames", frame_stride, atom_stride, comp_stride);
-    DCV_REQUIRE(out_frame_stride >= 1 && out_atom_stride >= 1 && out_comp_stride >= 1,
-                "dcv_transform_frames: output strides (%lld, %lld, %lld) must all be >= 1", (long long)out_frame_stride,
-                (long long)out_atom_stride, (long long)out_comp_stride);
+    const CoordStrides in{frame_stride, atom_stride, comp_stride}, outs{out_frame_stride, out_atom_stride, out_comp_stride};
+    DCV_REQUIRE_STRIDES_GE1("dcv_transform_frames", "output strides", outs);
     DCV_REQUIRE((reinterpret_cast<uintptr_t>(xyz_d) & 3) == 0 && (reinterpret_cast<uintptr_t>(out_d) & 3) == 0 &&
                     (reinterpret_cast<uintptr_t>(transform_d) & 7) == 0,
                 "dcv_transform_frames: the coordinates must be 4-byte aligned and the transforms 8-byte aligned");
     DCV_REQUIRE(ldt >= 15,"dcv_transform_frames: a transform row holds 15 doubles, ldt is %lld", (long long)ldt);
     if (n_frames == 0) return DCV_OK;
     int64_t in_last, out_last;
-    DCV_REQUIRE(xf_extent(n_frames, n_atoms, frame_stride, atom_stride, comp_stride, in_last) &&
-                    xf_extent(n_frames, n_atoms, out_frame_stride, out_atom_stride, out_comp_stride, out_last),
-                "dcv_transform_frames: %lld frames of %d atoms with these strides do not fit the address space", (long long)n_frames, n_atoms);
-    const uintptr_t in_lo = reinterpret_cast<uintptr_t>(xyz_d), in_hi = in_lo + 4 * (uintptr_t)in_last + 4;
-    const uintptr_t out_lo = reinterpret_cast<uintptr_t>(out_d), out_hi = out_lo + 4 * (uintptr_t)out_last + 4;
-    DCV_REQUIRE(in_hi <= out_lo || out_hi <= in_lo,
+    DCV_REQUIRE_COORDS_FIT("dcv_transform_frames", coord_extent(n_frames, n_atoms, in, in_last) && coord_extent(n_frames, n_atoms, outs, out_last),
+                           n_frames, n_atoms);
+    const Span in_out[2] = {coord_span(xyz_d, in_last), coord_span(out_d, out_last)};
+    DCV_REQUIRE(spans_disjoint(in_out, 2),
                 "dcv_transform_frames: the input elements [0, %lld] and the output elements [0, %lld] overlap in memory: the map is not in place",
                 (long long)in_last, (long long)out_last);
     int64_t t_last;   // the kernel reads the rows through a __restrict__ pointer: they must not be written either
     DCV_REQUIRE(!__builtin_mul_overflow(n_frames - 1, ldt, &t_last) && t_last < (int64_t)1 << 59,
                 "dcv_transform_frames: %lld transform rows %lld doubles apart do not fit the address space", (long long)n_frames, (long long)ldt);
-    const uintptr_t t_lo = reinterpret_cast<uintptr_t>(transform_d), t_hi = t_lo + 8 * ((uintptr_t)t_last + 15);
-    DCV_REQUIRE(t_hi <= out_lo || out_hi <= t_lo, "dcv_transform_frames: the transform rows and the output elements [0, %lld] overlap in memory",
+    const Span t_out[2] = {span_of(transform_d, 8 * ((uintptr_t)t_last + 15)), in_out[1]};
+    DCV_REQUIRE(spans_disjoint(t_out, 2), "dcv_transform_frames: the transform rows and the output elements [0, %lld] overlap in memory",
                 (long long)out_last);
     const int64_t slots = ((int64_t)n_atoms + 6) >> 2;
     DCV_REQUIRE(n_frames <= (((int64_t)1 << 62) / slots), "dcv_transform_frames: %lld frames x %d atoms are too many work items",
                 (long long)n_frames, n_atoms);
 
     XfArgs a{};
-    a.fs = frame_stride; a.as = atom_stride; a.cs = comp_stride;
+    a.in = in;
     a.ldt = ldt;
-    a.ofs = out_frame_stride; a.oas = out_atom_stride; a.ocs = out_comp_stride;
+    a.outs = outs;
     a.n_frames = n_frames; a.n_atoms = n_atoms;
     a.slots = slots; a.total = n_frames * slots;
-    a.x_word = (uint32_t)((in_lo >> 2) & 3); a.out_word = (uint32_t)((out_lo >> 2) & 3);
-    const XfForm in_form = xf_form(atom_stride, comp_stride), out_form = xf_form(out_atom_stride, out_comp_stride);
-    a.grid_on = out_form != kXfStrided ? 1 : (in_form != kXfStrided ? 2 : 0);
+    a.x_word = (uint32_t)((in_out[0].lo >> 2) & 3); a.out_word = (uint32_t)((in_out[1].lo >> 2) & 3);
+    const CoordForm in_form = coord_form(in), out_form = coord_form(outs);
+    a.grid_on = out_form != kCoordStrided ? 1 : (in_form != kCoordStrided ? 2 : 0);
     const int64_t want = cdiv(a.total, kXfThreads);
     const dim3 grid((unsigned)(want < kXfMaxGroups ? want : kXfMaxGroups));
     hipStream_t s = as_stream(stream);
-    if (in_form == kXfPlanes) xf_launch<kXfPlanes>(out_form, grid, s, a, xyz_d, transform_d, out_d);
-    else if (in_form == kXfDense) xf_launch<kXfDense>(out_form, grid, s, a, xyz_d, transform_d, out_d);
-    else xf_launch<kXfStrided>(out_form, grid, s, a, xyz_d, transform_d, out_d);
+    if (in_form == kCoordPlanes) xf_launch<kCoordPlanes>(out_form, grid, s, a, xyz_d, transform_d, out_d);
+    else if (in_form == kCoordDense) xf_launch<kCoordDense>(out_form, grid, s, a, xyz_d, transform_d, out_d);
+    else xf_launch<kCoordStrided>(out_form, grid, s, a, xyz_d, transform_d, out_d);
     DCV_CHECK_LAUNCH();
     return DCV_OK;
 }

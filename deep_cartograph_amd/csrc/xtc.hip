@@ -21,7 +21,7 @@
 // below); the atom counter of every frame is checked before each of those stores.  7.3 KB of LDS a wave, no atomics.
 #include <cmath>
 
-#include "common.h"
+#include "coords.h"
 #include "xtc_decode_frame.h"
 
 namespace dcv {
@@ -32,32 +32,25 @@ struct XtcArgs {
     float* out;
     int32_t* status;
     int64_t n_frames;
-    int64_t ofs, oas, ocs;
+    CoordStrides outs;
     int32_t n_atoms;
     float scale;
 };
 
 // The staging of a wave (64 frames) in LDS: a lane keeps its last kXtcRing atoms, word ((slot*3 + c)*65 + lane) -- lanes on
 // consecutive banks when they write, and the 24 words of a frame's block on different banks when the wave reads them
-// back --, and when every live lane has written the atoms of a block of kXtcBlock the WAVE stores the 64 blocks: lane j
-// of store i takes element 64 i + j of [frame][atom][component] (component fastest where the output has it fastest,
-// atom fastest for planes), so a store covers contiguous pieces of 96 bytes (dense rows) or 32 bytes (planes) instead
-// of 64 single floats in 64 different lines.  A block is flushed when decoded == kXtcBlock (b + 1) + 1: every live lane
-// has then written at least kXtcBlock (b + 1) atoms and at most one more, kXtcBlock + 1 atoms from the block's first:
-// the ring.  The atoms a marked frame did not write are not stored (cnt[] holds every lane's count).
+// back --, and when every live lane has written the atoms of a block of kXtcBlock the WAVE stores the 64 blocks in
+// xtc_format.h's block walk: contiguous pieces of 96 bytes (dense rows) or 32 bytes (planes).  A block is flushed when
+// decoded == kXtcBlock (b + 1) + 1: every live lane has then written at least kXtcBlock (b + 1) atoms and at most one
+// more, kXtcBlock + 1 atoms from the block's first: the ring.  The atoms a marked frame did not write are not stored
+// (cnt[] holds every lane's count).
 constexpr int kXtcBlock = 8, kXtcRing = kXtcBlock + 1, kXtcPitch = kXtcThreads + 1;
 
 __device__ __forceinline__ void xtc_flush(const XtcArgs& a, const float* ring, const int32_t* cnt, int64_t f0, int32_t block, bool comp_fast) {
-    constexpr int kPer = 3 * kXtcBlock;   // floats of one frame's block
-#pragma unroll 4
-    for (int i = 0; i < kPer; ++i) {
-        const int e = i * kXtcThreads + (int)threadIdx.x;
-        const int L = e / kPer, k = e - L * kPer;
-        const int s = comp_fast ? k / 3 : k % kXtcBlock, c = comp_fast ? k - 3 * s : k / kXtcBlock;
-        const int32_t atom = block * kXtcBlock + s;
+    xtc_block_walk<kXtcBlock>(block, comp_fast, [&](int L, int32_t atom, int c) {
         if (f0 + L < a.n_frames && atom < cnt[L])
-            a.out[(f0 + L) * a.ofs + (int64_t)atom * a.oas + c * a.ocs] = ring[((atom % kXtcRing) * 3 + c) * kXtcPitch + L];
-    }
+            a.out[(f0 + L) * a.outs.f + (int64_t)atom * a.outs.a + c * a.outs.c] = ring[((atom % kXtcRing) * 3 + c) * kXtcPitch + L];
+    });
 }
 
 __global__ __launch_bounds__(kXtcThreads) void xtc_decode_kernel(const XtcArgs a) {
@@ -72,15 +65,15 @@ __global__ __launch_bounds__(kXtcThreads) void xtc_decode_kernel(const XtcArgs a
 #pragma clang fp contract(off)
         if (live) {
             const uint32_t* w = reinterpret_cast<const uint32_t*>(a.bytes + d.offset);
-            float* out = a.out + f * a.ofs;
+            float* out = a.out + f * a.outs.f;
             for (int32_t i = 0; i < a.n_atoms; ++i)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) out[i * a.oas + c * a.ocs] = __builtin_bit_cast(float, __builtin_bswap32(w[3 * i + c])) * a.scale;
+                for (int c = 0; c < 3; ++c) out[i * a.outs.a + c * a.outs.c] = __builtin_bit_cast(float, __builtin_bswap32(w[3 * i + c])) * a.scale;
             a.status[f] = DCV_XTC_OK;
         }
         return;
     }
-    const bool comp_fast = a.ocs < a.oas;
+    const bool comp_fast = coord_comp_fast(a.outs);
     int32_t flushed = 0, written = 0;   // blocks stored, atoms this lane has written
     const int status = xtc_decode_frame(
         a.bytes, d, a.n_atoms, a.scale, live,
@@ -120,9 +113,8 @@ extern "C" int dcv_xtc_decode(const void* bytes_d, int64_t n_bytes, const dcv_xt
     DCV_REQUIRE(n_atoms > 0 && n_frames >= 0 && n_frames <= ((int64_t)1 << 40) && n_bytes >= 0 && n_bytes < ((int64_t)1 << 60),
                 "dcv_xtc_decode: bad arguments (n_atoms=%d n_frames=%lld n_bytes=%lld)", n_atoms, (long long)n_frames, (long long)n_bytes);
     DCV_REQUIRE(n_frames == 0 || (bytes_d && frames_h && out_d && status_d), "dcv_xtc_decode: a NULL pointer with %lld frames", (long long)n_frames);
-    DCV_REQUIRE(out_frame_stride >= 1 && out_atom_stride >= 1 && out_comp_stride >= 1,
-                "dcv_xtc_decode: output strides (%lld, %lld, %lld) must all be >= 1", (long long)out_frame_stride, (long long)out_atom_stride,
-                (long long)out_comp_stride);
+    const CoordStrides outs{out_frame_stride, out_atom_stride, out_comp_stride};
+    DCV_REQUIRE_STRIDES_GE1("dcv_xtc_decode", "output strides", outs);
     DCV_REQUIRE((reinterpret_cast<uintptr_t>(bytes_d) & 3) == 0 && (reinterpret_cast<uintptr_t>(out_d) & 3) == 0 &&
                     (reinterpret_cast<uintptr_t>(status_d) & 3) == 0 && (reinterpret_cast<uintptr_t>(ws_d) & 7) == 0,
                 "dcv_xtc_decode: the bytes, the output and the status must be 4-byte aligned, the workspace 8-byte aligned");
@@ -137,23 +129,15 @@ extern "C" int dcv_xtc_decode(const void* bytes_d, int64_t n_bytes, const dcv_xt
                     (long long)f, (long long)len, (long long)d.offset, (long long)n_bytes);
     }
     const size_t need = dcv_xtc_decode_workspace(n_frames);
-    if (n_frames > 0 && (!ws_d || ws_bytes < need)) {
-        set_error("dcv_xtc_decode: workspace too small (%zu bytes, need %zu)", ws_bytes, need);
-        return DCV_ENOMEM;
-    }
+    if (n_frames > 0) DCV_REQUIRE_WORKSPACE("dcv_xtc_decode", ws_d, ws_bytes, need);
     if (n_frames == 0) return DCV_OK;
     int64_t out_last;
-    DCV_REQUIRE(xtc_extent(n_frames, n_atoms, out_frame_stride, out_atom_stride, out_comp_stride, out_last),
-                "dcv_xtc_decode: %lld frames of %d atoms with these strides do not fit the address space", (long long)n_frames, n_atoms);
-    const uintptr_t in_lo = reinterpret_cast<uintptr_t>(bytes_d), in_hi = in_lo + (uintptr_t)n_bytes;
-    const uintptr_t out_lo = reinterpret_cast<uintptr_t>(out_d), out_hi = out_lo + 4 * (uintptr_t)out_last + 4;
-    const uintptr_t st_lo = reinterpret_cast<uintptr_t>(status_d), st_hi = st_lo + 4 * (uintptr_t)n_frames;
-    const uintptr_t ws_lo = reinterpret_cast<uintptr_t>(ws_d), ws_hi = ws_lo + need;
-    DCV_REQUIRE(xtc_disjoint(in_lo, in_hi, out_lo, out_hi),
+    DCV_REQUIRE_COORDS_FIT("dcv_xtc_decode", coord_extent(n_frames, n_atoms, outs, out_last), n_frames, n_atoms);
+    const Span spans[4] = {span_of(bytes_d, (uintptr_t)n_bytes), coord_span(out_d, out_last), span_of(status_d, 4 * (uintptr_t)n_frames),
+                           span_of(ws_d, need)};
+    DCV_REQUIRE(spans_disjoint(spans, 2),
                 "dcv_xtc_decode: the %lld input bytes and the output elements [0, %lld] overlap in memory", (long long)n_bytes, (long long)out_last);
-    DCV_REQUIRE(xtc_disjoint(in_lo, in_hi, st_lo, st_hi) && xtc_disjoint(out_lo, out_hi, st_lo, st_hi) && xtc_disjoint(in_lo, in_hi, ws_lo, ws_hi) &&
-                    xtc_disjoint(out_lo, out_hi, ws_lo, ws_hi) && xtc_disjoint(st_lo, st_hi, ws_lo, ws_hi),
-                "dcv_xtc_decode: the input bytes, the output, the status words and the workspace must not overlap");
+    DCV_REQUIRE(spans_disjoint(spans, 4), "dcv_xtc_decode: the input bytes, the output, the status words and the workspace must not overlap");
     DCV_REQUIRE(cdiv(n_frames, kXtcThreads) <= 0x7fffffffLL, "dcv_xtc_decode: %lld frames need more than 2^31 - 1 workgroups", (long long)n_frames);
 
     hipStream_t s = as_stream(stream);
@@ -165,7 +149,7 @@ extern "C" int dcv_xtc_decode(const void* bytes_d, int64_t n_bytes, const dcv_xt
     a.out = out_d;
     a.status = status_d;
     a.n_frames = n_frames;
-    a.ofs = out_frame_stride; a.oas = out_atom_stride; a.ocs = out_comp_stride;
+    a.outs = outs;
     a.n_atoms = n_atoms;
     a.scale = scale;
     hipLaunchKernelGGL(xtc_decode_kernel, dim3((unsigned)cdiv(n_frames, kXtcThreads)), dim3(kXtcThreads), 0, s, a);

@@ -11,15 +11,15 @@
 //
 // Loads.  A lane that read its own frame from global memory would make every load of the wave touch 64 lines, one per
 // frame -- the decoder's first store pattern in mirror image.  The WAVE instead stages blocks of
-// kXtcEncBlock atoms of its 64 frames in LDS (xtc_stage below): lane j of load i takes element 64 i + j of
-// [frame][atom][component] (component fastest where the input has it fastest, atom fastest for planes), contiguous
-// pieces of 192 bytes (dense rows) or 64 bytes (planes).  Two blocks are resident: at atom p the encoder looks at most
-// kXtcLookahead = 8 atoms ahead, which never leaves the block of p and the one behind it.  The coordinates are staged
-// as floats and quantised where they are used; both passes stage the same way.  24.4 KB of LDS a wave, no atomics.
+// kXtcEncBlock atoms of its 64 frames in LDS (xtc_stage below) in xtc_format.h's block walk, the one the decoder stores
+// with: contiguous pieces of 192 bytes (dense rows) or 64 bytes (planes).  Two blocks are resident: at atom p the
+// encoder looks at most kXtcLookahead = 8 atoms ahead, which never leaves the block of p and the one behind it.  The
+// coordinates are staged as floats and quantised where they are used; both passes stage the same way.  24.4 KB of LDS a
+// wave, no atomics.
 #include <cmath>
 #include <vector>
 
-#include "common.h"
+#include "coords.h"
 #include "xtc_encode_frame.h"
 
 namespace dcv {
@@ -34,7 +34,7 @@ struct XtcEncArgs {
     dcv_xtc_frame* desc;
     int32_t* status;
     int64_t n_frames;
-    int64_t fs, as, cs;
+    CoordStrides in;
     int64_t slot_bytes;
     int32_t n_atoms;
     float inv_scale, precision;
@@ -42,16 +42,10 @@ struct XtcEncArgs {
 
 // block `block` of the atoms of the wave's 64 frames, global memory -> LDS word ((atom % ring) * 3 + c) * pitch + frame
 __device__ __forceinline__ void xtc_stage(const XtcEncArgs& a, float* ring, const int64_t* src, int64_t f0, int32_t block, bool comp_fast) {
-    constexpr int kPer = 3 * kXtcEncBlock;   // floats of one frame's block
-#pragma unroll 4
-    for (int i = 0; i < kPer; ++i) {
-        const int e = i * kXtcThreads + (int)threadIdx.x;
-        const int L = e / kPer, k = e - L * kPer;
-        const int s = comp_fast ? k / 3 : k % kXtcEncBlock, c = comp_fast ? k - 3 * s : k / kXtcEncBlock;
-        const int64_t atom = (int64_t)block * kXtcEncBlock + s;
+    xtc_block_walk<kXtcEncBlock>((int64_t)block, comp_fast, [&](int L, int64_t atom, int c) {
         if (f0 + L < a.n_frames && atom < a.n_atoms)
-            ring[((int)(atom % kXtcEncRing) * 3 + c) * kXtcEncPitch + L] = a.xyz[src[L] * a.fs + atom * a.as + c * a.cs];
-    }
+            ring[((int)(atom % kXtcEncRing) * 3 + c) * kXtcEncPitch + L] = a.xyz[src[L] * a.in.f + atom * a.in.a + c * a.in.c];
+    });
 }
 
 __global__ __launch_bounds__(kXtcThreads) void xtc_encode_kernel(const XtcEncArgs a) {
@@ -67,15 +61,15 @@ __global__ __launch_bounds__(kXtcThreads) void xtc_encode_kernel(const XtcEncArg
     if (a.n_atoms <= 9) {   // the raw form: big-endian floats of x * inv_scale, nothing else
 #pragma clang fp contract(off)
         if (live) {
-            const float* x = a.xyz + from * a.fs;
+            const float* x = a.xyz + from * a.in.f;
             bool finite = true;
             for (int32_t i = 0; i < a.n_atoms; ++i)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(x[i * a.as + c * a.cs]);
+                for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(x[i * a.in.a + c * a.in.c]);
             if (finite)
                 for (int32_t i = 0; i < a.n_atoms; ++i)
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) slot[3 * i + c] = __builtin_bswap32(__builtin_bit_cast(uint32_t, x[i * a.as + c * a.cs] * a.inv_scale));
+                    for (int c = 0; c < 3; ++c) slot[3 * i + c] = __builtin_bswap32(__builtin_bit_cast(uint32_t, x[i * a.in.a + c * a.in.c] * a.inv_scale));
             d.raw = 1;
             a.desc[f] = d;
             a.status[f] = finite ? DCV_XTC_OK : DCV_XTC_ENC_NONFINITE;
@@ -83,7 +77,7 @@ __global__ __launch_bounds__(kXtcThreads) void xtc_encode_kernel(const XtcEncArg
         return;
     }
     src[lane] = from;
-    const bool comp_fast = a.cs < a.as;
+    const bool comp_fast = coord_comp_fast(a.in);
     const int status = xtc_encode_frame(
         a.n_atoms, a.inv_scale, a.precision, live, slot, (uint32_t)(a.slot_bytes / 4), d,
         [&](int32_t atom, float (&x)[3]) {
@@ -151,8 +145,8 @@ extern "C" int dcv_xtc_encode(const float* xyz_d, int64_t n_src_frames, int64_t 
     DCV_REQUIRE(std::isfinite(precision) && precision > 0.0f && std::isfinite(inv_scale),
                 "dcv_xtc_encode: the precision (%g) must be finite and positive, inv_scale (%g) finite", (double)precision, (double)inv_scale);
     DCV_REQUIRE(n_frames == 0 || (xyz_d && slots_d && desc_d && status_d), "dcv_xtc_encode: a NULL pointer with %lld frames", (long long)n_frames);
-    DCV_REQUIRE(frame_stride >= 1 && atom_stride >= 1 && comp_stride >= 1, "dcv_xtc_encode: strides (%lld, %lld, %lld) must all be >= 1",
-                (long long)frame_stride, (long long)atom_stride, (long long)comp_stride);
+    const CoordStrides in{frame_stride, atom_stride, comp_stride};
+    DCV_REQUIRE_STRIDES_GE1("dcv_xtc_encode", "strides", in);
     DCV_REQUIRE((reinterpret_cast<uintptr_t>(xyz_d) & 3) == 0 && (reinterpret_cast<uintptr_t>(slots_d) & 3) == 0 &&
                     (reinterpret_cast<uintptr_t>(status_d) & 3) == 0 && (reinterpret_cast<uintptr_t>(desc_d) & 7) == 0 &&
                     (reinterpret_cast<uintptr_t>(ws_d) & 7) == 0,
@@ -166,28 +160,19 @@ extern "C" int dcv_xtc_encode(const float* xyz_d, int64_t n_src_frames, int64_t 
     }
     const size_t need = frames_h ? dcv_xtc_encode_workspace(n_frames) : 0;
     const size_t slot = (size_t)xtc_slot_bytes(n_atoms);
-    if (n_frames > 0 && need > 0 && (!ws_d || ws_bytes < need)) {
-        set_error("dcv_xtc_encode: workspace too small (%zu bytes, need %zu)", ws_bytes, need);
-        return DCV_ENOMEM;
-    }
+    if (n_frames > 0 && need > 0) DCV_REQUIRE_WORKSPACE("dcv_xtc_encode", ws_d, ws_bytes, need);
     if (n_frames > 0 && slots_bytes / slot < (size_t)n_frames) {
         set_error("dcv_xtc_encode: slot buffer too small (%zu bytes, need %lld slots of %zu)", slots_bytes, (long long)n_frames, slot);
         return DCV_ENOMEM;
     }
     if (n_frames == 0) return DCV_OK;
     int64_t in_last;
-    DCV_REQUIRE(xtc_extent(n_src_frames, n_atoms, frame_stride, atom_stride, comp_stride, in_last),
-                "dcv_xtc_encode: %lld frames of %d atoms with these strides do not fit the address space", (long long)n_src_frames, n_atoms);
-    const uintptr_t in_lo = reinterpret_cast<uintptr_t>(xyz_d), in_hi = in_lo + 4 * (uintptr_t)in_last + 4;
-    const uintptr_t sl_lo = reinterpret_cast<uintptr_t>(slots_d), sl_hi = sl_lo + (uintptr_t)n_frames * slot;
-    const uintptr_t de_lo = reinterpret_cast<uintptr_t>(desc_d), de_hi = de_lo + (uintptr_t)n_frames * sizeof(dcv_xtc_frame);
-    const uintptr_t st_lo = reinterpret_cast<uintptr_t>(status_d), st_hi = st_lo + 4 * (uintptr_t)n_frames;
-    const uintptr_t ws_lo = reinterpret_cast<uintptr_t>(ws_d), ws_hi = ws_lo + need;
-    const uintptr_t lo[5] = {in_lo, sl_lo, de_lo, st_lo, ws_lo}, hi[5] = {in_hi, sl_hi, de_hi, st_hi, ws_hi};
-    for (int i = 0; i < 5; ++i)
-        for (int j = i + 1; j < 5; ++j)
-            DCV_REQUIRE(lo[j] == hi[j] || xtc_disjoint(lo[i], hi[i], lo[j], hi[j]),
-                        "dcv_xtc_encode: the coordinates, the slots, the descriptors, the status words and the workspace must not overlap");
+    DCV_REQUIRE_COORDS_FIT("dcv_xtc_encode", coord_extent(n_src_frames, n_atoms, in, in_last), n_src_frames, n_atoms);
+    const Span spans[5] = {coord_span(xyz_d, in_last), span_of(slots_d, (uintptr_t)n_frames * slot),
+                           span_of(desc_d, (uintptr_t)n_frames * sizeof(dcv_xtc_frame)), span_of(status_d, 4 * (uintptr_t)n_frames),
+                           span_of(ws_d, need)};   // without indices the workspace is empty
+    DCV_REQUIRE(spans_disjoint(spans, 5),
+                "dcv_xtc_encode: the coordinates, the slots, the descriptors, the status words and the workspace must not overlap");
     DCV_REQUIRE(cdiv(n_frames, kXtcThreads) <= 0x7fffffffLL, "dcv_xtc_encode: %lld frames need more than 2^31 - 1 workgroups", (long long)n_frames);
 
     hipStream_t s = as_stream(stream);
@@ -200,7 +185,7 @@ extern "C" int dcv_xtc_encode(const float* xyz_d, int64_t n_src_frames, int64_t 
     a.desc = desc_d;
     a.status = status_d;
     a.n_frames = n_frames;
-    a.fs = frame_stride; a.as = atom_stride; a.cs = comp_stride;
+    a.in = in;
     a.slot_bytes = (int64_t)slot;
     a.n_atoms = n_atoms;
     a.inv_scale = inv_scale;
@@ -245,16 +230,10 @@ extern "C" int dcv_xtc_pack(const void* slots_d, size_t slots_bytes, const dcv_x
         end = image_offset_h[f] + whole;
     }
     const size_t need = dcv_xtc_pack_workspace(n_frames);
-    if (n_frames > 0 && (!ws_d || ws_bytes < need)) {
-        set_error("dcv_xtc_pack: workspace too small (%zu bytes, need %zu)", ws_bytes, need);
-        return DCV_ENOMEM;
-    }
+    if (n_frames > 0) DCV_REQUIRE_WORKSPACE("dcv_xtc_pack", ws_d, ws_bytes, need);
     if (n_frames == 0) return DCV_OK;
-    const uintptr_t sl_lo = reinterpret_cast<uintptr_t>(slots_d), sl_hi = sl_lo + slots_bytes;
-    const uintptr_t im_lo = reinterpret_cast<uintptr_t>(image_d), im_hi = im_lo + image_bytes;
-    const uintptr_t ws_lo = reinterpret_cast<uintptr_t>(ws_d), ws_hi = ws_lo + need;
-    DCV_REQUIRE(xtc_disjoint(sl_lo, sl_hi, im_lo, im_hi) && xtc_disjoint(sl_lo, sl_hi, ws_lo, ws_hi) && xtc_disjoint(im_lo, im_hi, ws_lo, ws_hi),
-                "dcv_xtc_pack: the slots, the image and the workspace must not overlap");
+    const Span spans[3] = {span_of(slots_d, slots_bytes), span_of(image_d, image_bytes), span_of(ws_d, need)};
+    DCV_REQUIRE(spans_disjoint(spans, 3), "dcv_xtc_pack: the slots, the image and the workspace must not overlap");
     DCV_REQUIRE(cdiv(n_frames, kXtcPackWaves) <= 0x7fffffffLL, "dcv_xtc_pack: %lld frames need more than 2^31 - 1 workgroups", (long long)n_frames);
 
     std::vector<XtcPackRec> recs((size_t)n_frames);

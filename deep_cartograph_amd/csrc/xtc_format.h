@@ -1,6 +1,6 @@
 // What the XTC decoder (xtc.hip) and the XTC encoder (xtc_encode.hip) share: the constants and the table of the format,
-// the bit lengths of its fields, the limb type of its packed integers and the host-side range checks of both entry
-// points.  The format itself is written out in include/dcv.h.
+// the bit lengths of its fields, the limb type of its packed integers and the walk in which a wave exchanges a block of
+// atoms of its 64 frames between LDS and global memory.  The format itself is written out in include/dcv.h.
 #pragma once
 #include "common.h"
 
@@ -34,15 +34,21 @@ __host__ __device__ __forceinline__ int xtc_product_bits(uint32_t a, uint32_t b,
     return hi ? 96 - __builtin_clzll(hi) : 32 - __builtin_clz((uint32_t)lo | 1u);   // a, b, c >= 1: the product is not 0
 }
 
-// last element a coordinate layout reaches, false when that does not fit 60 bits
-inline bool xtc_extent(int64_t n_frames, int64_t n_atoms, int64_t fs, int64_t as, int64_t cs, int64_t& last) {
-    int64_t x, y, z;
-    if (__builtin_mul_overflow(n_frames - 1, fs, &x) || __builtin_mul_overflow(n_atoms - 1, as, &y) || __builtin_mul_overflow((int64_t)2, cs, &z))
-        return false;
-    if (__builtin_add_overflow(x, y, &last) || __builtin_add_overflow(last, z, &last)) return false;
-    return last < (int64_t)1 << 60;
+// Block `block` of kBlock atoms of the 64 frames of a wave, moved by the WAVE between LDS and global memory (the decoder's
+// stores, the encoder's loads): lane j of pass i takes element 64 i + j of [frame][atom][component] -- component fastest
+// where the layout in global memory has it fastest (comp_fast), atom fastest for planes --, so a pass covers contiguous
+// pieces of 12 kBlock bytes (dense rows) or 4 kBlock bytes (planes) instead of 64 single floats in 64 different lines.
+// fn(frame of the wave, atom, component) guards and moves one element; atoms are counted in the type of `block`.
+template <int kBlock, typename Block, typename Fn>
+__device__ __forceinline__ void xtc_block_walk(Block block, bool comp_fast, Fn&& fn) {
+    constexpr int kPer = 3 * kBlock;   // floats of one frame's block
+#pragma unroll 4
+    for (int i = 0; i < kPer; ++i) {
+        const int e = i * kXtcThreads + (int)threadIdx.x;
+        const int L = e / kPer, k = e - L * kPer;
+        const int s = comp_fast ? k / 3 : k % kBlock, c = comp_fast ? k - 3 * s : k / kBlock;
+        fn(L, block * kBlock + s, c);
+    }
 }
-
-inline bool xtc_disjoint(uintptr_t a_lo, uintptr_t a_hi, uintptr_t b_lo, uintptr_t b_hi) { return a_hi <= b_lo || b_hi <= a_lo; }
 
 }  // namespace dcv

@@ -109,7 +109,10 @@ int dcv_dip_sorted(const float* Xs_d, int64_t n, int32_t C, int64_t ld, double* 
  * boundaries are NOT applied.  Non-finite coordinates propagate to the output.
  * Every record is validated before anything is launched: an atom index outside [0, n_atoms), an output column that
  * does not fit ldo or an unknown kind is DCV_EINVAL; so is a set of used atoms of which one frame does not fit LDS
- * (5461 atoms).  The records are copied into the workspace; one that is too small is DCV_ENOMEM, nothing launched.
+ * (5461 atoms), or, with n_frames > 0, a layout whose last element -- (n_frames - 1) frame_stride + (n_atoms - 1)
+ * atom_stride + 2 comp_stride -- overflows or does not lie below 2^60 ("do not fit the address space"; so for every
+ * entry that takes these strides).  The records are copied into the workspace; one that is too small is DCV_ENOMEM,
+ * nothing launched.
  * A workgroup owns 16 frames (fewer when 16 frames of the staged atoms exceed 48 KB of LDS).  Staged per frame: the
  * index range [min, max] of the atoms the records name when the innermost stride is 1 and they fill at least half of
  * it, otherwise exactly the named atoms.  Algorithmic traffic per frame: 12 bytes per staged atom + 4 per output column. */
@@ -142,7 +145,8 @@ int dcv_featurize(const float* xyz_d, int64_t n_frames, int64_t frame_stride, in
  * Validated before anything is launched (DCV_EINVAL): kinds, atom indices, feature indices in [-1, F) with at least one
  * >= 0 per record, every feature in [0, F) written by exactly one record, 1 <= d <= 16, ldo >= d, fmean / frange both or
  * neither, the strides, one frame of the staged atoms within LDS (5461 atoms); a workspace that is too small is
- * DCV_ENOMEM.  n_frames = 0 is DCV_OK.  Algorithmic traffic per frame: 12 bytes per staged atom + 4*d. */
+ * DCV_ENOMEM; then, with n_frames > 0, a layout that does not fit the address space (DCV_EINVAL, as in dcv_featurize).
+ * n_frames = 0 is DCV_OK.  Algorithmic traffic per frame: 12 bytes per staged atom + 4*d. */
 size_t dcv_featurize_project_workspace(int64_t n_frames, int32_t n_atoms, int32_t n_rec, int32_t F, int32_t d);
 int dcv_featurize_project(const float* xyz_d, int64_t n_frames, int64_t frame_stride, int64_t atom_stride, int64_t comp_stride,
                           int32_t n_atoms, const int32_t* rec_h, int32_t n_rec, int32_t F, double unit,
@@ -177,7 +181,8 @@ int dcv_featurize_project(const float* xyz_d, int64_t n_frames, int64_t frame_st
  * Everything is validated before anything is launched.  DCV_EINVAL: an index outside [0, n_atoms); n_fit < 1; a
  * weight that is negative or not finite, or weights that do not sum to a positive number; lda < 3 n_sel; moments
  * without sel_ref_h; bad strides; one frame of the staged atoms above 64 KB of LDS (5461 atoms), or that frame plus
- * the parked transform (96 bytes, with aligned_d or moments_d) and the moment partials above 64 KB.  DCV_ENOMEM: a
+ * the parked transform (96 bytes, with aligned_d or moments_d) and the moment partials above 64 KB; with n_frames > 0
+ * and behind every other refusal, a layout that does not fit the address space (as in dcv_featurize).  DCV_ENOMEM: a
  * workspace that is too small.  n_frames = 0 is DCV_OK.  The reference and both atom lists are copied into the
  * workspace.  Algorithmic traffic per frame: 12 bytes per staged atom, plus 12 per selected atom with aligned_d. */
 #define DCV_SUPERPOSE_MAX_GROUPS 768   /* upper bound of workgroups (and of moment partials) of one call */
@@ -219,7 +224,9 @@ int dcv_superpose(const float* xyz_d, int64_t n_frames, int64_t frame_stride, in
  *     Non-finite values are left out of G.
  * A non-finite input coordinate spoils its own column only.
  * Everything is validated before anything is launched.  DCV_EINVAL: an unknown kind; n_knots < 2 (< 3 for makima); a
- * selection index outside [0, n_atoms); n_sel < 1 with a selection; bad strides; a decreasing or non-finite time.
+ * selection index outside [0, n_atoms); n_sel < 1 with a selection; bad strides; a decreasing or non-finite time; with
+ * n_out > 0 and behind every other refusal, an input layout (n_knots frames of n_atoms atoms) or an output layout (n_out
+ * frames of n_sel atoms) that does not fit the address space (as in dcv_featurize).
  * DCV_ENOMEM: a workspace that is too small.  n_out = 0 is DCV_OK.
  * A wave owns 64 adjacent coordinate columns and a run of at least 64 consecutive output frames; a lane walks its run
  * in ascending t with the six knots around floor(t) and the following one in registers and loads one knot whenever
