@@ -389,6 +389,13 @@ static bool snet_build(dcv_mlp* m) {
     }
     const char* e = getenv("DCV_SNET_STAMPS");
     if (e && e[0] == '1' && snet_grow(&pl->stamps, &stamps_n, 64)) (void)hipMemset(pl->stamps, 0, 64 * sizeof(unsigned long long));
+    // the plan is built inside an engine's first step and the memsets above went to the null stream: they must have
+    // landed before that step launches on the caller's stream, which need not wait for the null stream (dcv.h: all work
+    // of an entry is on its stream).  Once per engine, next to the allocations.
+    if (hipDeviceSynchronize() != hipSuccess) {
+        (void)hipGetLastError();
+        return fail();
+    }
     return true;
 }
 

@@ -466,6 +466,11 @@ static bool snet_dt_build(dcv_mlp* m) {
             pl->ev_ticket_n = 0;
         }
     }
+    // as in snet_build: the null-stream memset above must have landed before the first step launches on the caller's stream
+    if (hipDeviceSynchronize() != hipSuccess) {
+        (void)hipGetLastError();
+        return fail();
+    }
     return true;
 }
 

@@ -17,6 +17,12 @@
  *   - matrices are row-major; `ld` is the row stride in ELEMENTS;
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); all work is
  *     enqueued asynchronously on it, functions with *_h outputs synchronise that stream;
+ *   - host arrays (*_h inputs) are taken at the call: the caller may overwrite or free them once the function has
+ *     returned, whether or not it synchronised (a function that takes one may hold the host until the stream reaches it);
+ *   - the library keeps no device state outside the caller's buffers and the dcv_mlp / dcv_comm handles: calls whose
+ *     buffers (workspaces included) do not overlap, and calls on different dcv_mlp handles, may be in flight on different
+ *     streams at the same time; one handle is driven from one stream at a time, and calls are made from one host thread
+ *     at a time (the arithmetic mode, the launch-plan log and the profiling hooks are process-wide host state);
  *   - workspace sizes are queried with the matching *_workspace() call; workspaces are
  *     plain device memory with no state between calls;
  *   - one process drives one GPU; multi-GPU runs shard frames over ranks and all-reduce the
